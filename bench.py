@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Conv-TasNet training-step throughput on MI355X (BASELINE.json metric: 4 s / 8 kHz / 2-spk utterances per second, fwd+bwd).
 
-    python bench.py [--gpus N --steps K --warmup W] [--config paper|causal|c3]
+    python bench.py [--gpus N --steps K --warmup W] [--config paper|causal|c3] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -10,6 +10,15 @@ A step = one pass of the hot path over one synthetic minibatch resident in HBM: 
 Default workload: BASELINE configs[1], paper config N256 L20 B256 H512 P3 X8 R4 gLN C2, 8 utterances of 4 s @ 8 kHz per
 GPU (weak scaling: global batch = 8 * N).  --config causal = configs[3] (cLN, causal), --config c3 = configs[4]
 (3 speakers, L=16, 16 kHz).  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the line.  Everything else the benchmark measures runs only
+with `--full`, after the timed region: `<arith>_arithmetic` (the same step on the other GEMM arithmetics), `roofline`,
+`other_configs` + `inference` (paper config only) and `cpu_baseline`; the `--no-*` switches drop single legs of a full run.
+`--dump-outputs DIR` (rank 0) writes what the last timed step returned to its caller as DIR/<name>.npy, float32: the loss,
+`max_snr`, the masked estimate, the reordered estimate, and the flat gradient and flat parameters after the optimiser step
+(`estimate*` are not returned by the graphed step).  Arrays are written whole while the files fit in 64 MB; beyond that
+the largest are cut to a seeded sample of their flattened elements (numpy default_rng(0), sorted indices; the same sample
+for the same arguments).  The inputs are seeded: the same arguments give the same inputs in every run.
 
 `roofline` (rank 0): after the timed region a few more training steps run with a HIP-event pair around EVERY launch
 group of the block kernels (the per-kernel entry points driven from Python: the same kernels in the same order as the
@@ -30,7 +39,7 @@ sys.path.insert(0, ROOT)
 import torch  # noqa: E402
 
 _T_PROC = time.time()         # the driver's clock runs from process start: the CPU leg is bounded against it (WALL_LIMIT_S)
-WALL_LIMIT_S = 540.0          # whole default run, import torch on a cold box included (the driver allows 600 s)
+WALL_LIMIT_S = 540.0          # whole --full run, import torch on a cold host included (the driver allows 600 s)
 
 PEAK_F32_MFMA_TFLOPS = 157.3   # /opt/skills/guides/MI355X_MICROARCH.md, "Peak FP32 (matrix)" (154.5 measured on the box:
                                # benchmarks/mfma_probe.hip, profiles/r02_a_mfma_probe.txt)
@@ -354,6 +363,25 @@ def roofline(rows, probe_steps, ms_per_step, fused_min_bytes):
             "families": rows}
 
 
+DUMP_LIMIT_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(out_dir, arrays):
+    """arrays: name -> tensor.  Written as out_dir/<name>.npy in float32; smallest first, each array whole if it fits its
+    fair share of what is left of DUMP_LIMIT_BYTES, else a fixed sample of its flattened elements (default_rng(0), sorted)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    host = {k: v.detach().float().cpu().numpy() for k, v in arrays.items() if v is not None}
+    left = DUMP_LIMIT_BYTES - 4096 * len(host)             # headroom for the .npy headers
+    for i, (name, a) in enumerate(sorted(host.items(), key=lambda kv: kv[1].size)):
+        keep = max(1, left // (4 * (len(host) - i)))
+        if a.size > keep:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, keep, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), a.astype(np.float32, copy=False))
+        left -= 4 * a.size
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -364,10 +392,15 @@ def main():
                     help="GEMM arithmetic: h3 = the composite stacks on two fp16 pieces per fp32 operand under tracked power-of-two scales, "
                          "three f16 MFMAs per product step (fp32-faithful products; library default), b6 = three bf16 pieces per fp32 "
                          "operand, six bf16 MFMAs (fp32-faithful), fp32 = fp32-MFMA kernels")
-    ap.add_argument("--no-side-arith", action="store_true", help="skip the short runs on the other arithmetics after the timed region")
-    ap.add_argument("--no-side-configs", action="store_true", help="skip the short side records (causal, c3, inference, streaming) after the timed region")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also measure the side records: other arithmetics, roofline, other configs + "
+                         "inference (paper config), cpu_baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (loss, estimates, gradients, parameters) as DIR/<name>.npy")
+    ap.add_argument("--no-side-arith", action="store_true", help="--full: skip the short runs on the other arithmetics after the timed region")
+    ap.add_argument("--no-side-configs", action="store_true", help="--full: skip the short side records (causal, c3, inference, streaming) after the timed region")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the oracle's step on the host cores")
+    ap.add_argument("--no-roofline", action="store_true", help="--full: skip the per-family in-step timing")
     ap.add_argument("--graph", type=int, default=int(os.environ.get("CTN_BENCH_GRAPH", "0")),
                     help="1: replay zero_grad+fwd+loss+bwd from one captured HIP graph (conv_tasnet_amd.graphed)")
     args = ap.parse_args()
@@ -406,15 +439,18 @@ def main():
         graphed = GraphedBackprop(model, opt, (mix, lens, src))
 
     AR_PROBE = None
+    last = {}                   # what the latest step returned to its caller (--dump-outputs)
 
     def step():
         if graphed is not None:
             loss = graphed(mix, lens, src)
+            last.update(loss=loss, max_snr=graphed.max_snr)
         else:
             opt.zero_grad()
             est = model(mix)
-            loss, _, _, _ = ctn.cal_loss(src, est, lens)
+            loss, max_snr, est, reordered = ctn.cal_loss(src, est, lens)
             loss.backward()
+            last.update(loss=loss, max_snr=max_snr, estimate=est, estimate_reordered=reordered)
         if AR_PROBE is not None and world > 1:      # roofline leg: the exposed part of the gradient all-reduce (what the step waits for)
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
@@ -447,6 +483,8 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t)
     mean_loss = float(loss_acc) / max(args.steps, 1)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, dict(last, flat_grads=opt.flat_grads, flat_params=opt.flat_params))
 
     if rank == 0:
         ffwd, K = flops_fwd(cfg["model"], cfg["T"])
@@ -472,7 +510,7 @@ def main():
             out["model_frac_of_f32_mfma_peak"] = round(value * ftrain / 1e12 / (PEAK_F32_MFMA_TFLOPS * world), 4)
         else:                          # executed bf16 / f16 MFMA FLOPs of the whole step (nprod per algorithmic product) over the dense peak
             out["executed_mfma_frac_of_bf16_peak"] = round(MFMA_PER_STEP[args.arith] * value * ftrain / 1e12 / (PEAK_BF16_MFMA_TFLOPS * world), 4)
-    if graphed is None and not args.no_side_arith:
+    if args.full and graphed is None and not args.no_side_arith:
         # the same workload on the other arithmetics, timed the same way right after the main measurement (every rank takes
         # part): `value` above is the run's own arithmetic; these side records show, on the same box in the same process, what
         # the other reference-precision arithmetics (bit-exact fp32 MFMA, b6) cost
@@ -509,7 +547,7 @@ def main():
                 side[name + "_arithmetic"] = r
         if rank == 0:
             out.update(side)
-    if not args.no_roofline and graphed is None:
+    if args.full and not args.no_roofline and graphed is None:
         # every rank takes part (the steps contain the gradient all-reduce); rank 0 keeps the table.  The steps run exactly as
         # in the timed region (composite stacks, second stream): the library brackets every launch group of the stacks with a
         # HIP-event pair on its stream (ctn_probe_enable), lib.probe does the same for the calls made from Python (front end,
@@ -550,7 +588,7 @@ def main():
 
     # ---- side records: the other BASELINE configs and the inference callers, short runs in the same process (every rank takes
     # part: the training records contain the gradient all-reduce) -------------------------------------------------------------
-    if not args.no_side_configs and graphed is None and args.config == "paper":
+    if args.full and not args.no_side_configs and graphed is None and args.config == "paper":
         def sync_time(fn, n):
             if world > 1:
                 dist.barrier()
@@ -685,7 +723,7 @@ def main():
         dist.barrier()
         dist.destroy_process_group()
     if rank == 0:
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(cfg)
             out["wall_s_since_process_start"] = round(time.time() - _T_PROC, 1)
         print(json.dumps(out), flush=True)

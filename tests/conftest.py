@@ -96,7 +96,7 @@ def pytest_collection_finish(session):
 
 
 def _spawn_bench_children(session):
-    """`bench.py --gpus 2 --steps 3 --warmup 1 --config tiny` as two env-rendezvous ranks on cuda:0 over gloo."""
+    """`bench.py --gpus 2 --steps 3 --warmup 1 --config tiny --full` as two env-rendezvous ranks on cuda:0 over gloo."""
     if not any(it.nodeid.endswith("test_bench_two_ranks_prints_one_complete_line") for it in session.items):
         return
     import subprocess
@@ -113,7 +113,7 @@ def _spawn_bench_children(session):
                    CTN_DIST_BACKEND="gloo")
         outs[name], logs[name] = os.path.join(tmp, name + ".out"), os.path.join(tmp, name + ".log")
         procs[name] = subprocess.Popen([sys.executable, os.path.join(ROOT, "tests", "bench_worker.py"), os.path.join(tmp, "go"), "--gpus", "2",
-                                        "--steps", "3", "--warmup", "1", "--config", "tiny"],
+                                        "--steps", "3", "--warmup", "1", "--config", "tiny", "--full"],
                                        stdout=open(outs[name], "w"), stderr=open(logs[name], "w"), cwd=ROOT, env=env)
     _DP["bench"] = (procs, outs, logs)
     _DP["bench_go"] = os.path.join(tmp, "go")

@@ -1,4 +1,4 @@
-"""GPU: `bench.py --gpus 2` as the driver launches it -- two ranks under torch.distributed env rendezvous -- rehearsed on ONE GPU
+"""GPU: `bench.py --gpus 2 --full` as the driver launches it -- two ranks under torch.distributed env rendezvous -- rehearsed on ONE GPU
 with the gloo backend (RCCL needs distinct devices; the ranks share cuda:0), on BASELINE configs[0] (tiny) so that the whole
 line, `roofline` and `cpu_baseline` included, takes seconds.  The two ranks are child processes started by conftest.py BEFORE
 this process touches the GPU (tests/conftest.py: pytest_collection_finish) and only collected here."""

@@ -18,7 +18,14 @@ def _free_port():
     return p
 
 
+def _cpu_host():
+    """The CPU path of parallel.init_distributed (gloo, torch.device("cpu")) also where a GPU is visible: these ranks are
+    spawned children, so the patch stays inside them."""
+    torch.cuda.is_available = lambda: False
+
+
 def _worker(rank, world, port, out_dir):
+    _cpu_host()
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world),
                       LOCAL_RANK=str(rank))
     torch.set_num_threads(2)
@@ -74,6 +81,7 @@ def test_shard_batch_rejects_ragged_split():
 
 
 def _loss_worker(rank, world, port, out_dir):
+    _cpu_host()
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world),
                       LOCAL_RANK=str(rank))
     from conv_tasnet_amd import parallel
@@ -104,6 +112,7 @@ def test_global_minibatch_loss_weights_ragged_shards(tmp_path):
 
 
 def _bucket_worker(rank, world, port, out_dir):
+    _cpu_host()
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank))
     from conv_tasnet_amd import parallel
     parallel.init_distributed(backend="gloo")
