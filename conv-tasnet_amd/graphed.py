@@ -5,10 +5,11 @@ minibatches of Conv-TasNet all have one shape (4 s segments, src/data.py:287-296
 once with stream capture -- including the weight-gradient kernels forked onto the second stream -- and replayed with a
 single ``hipGraphLaunch``; the host then only copies the next minibatch into the static input buffers.
 
-The gradient all-reduce and the clip + Adam kernels stay outside the graph (three launches): the step counter and the
-learning rate are host values of ``FlatAdam.step`` and RCCL keeps its own stream semantics.
+The gradient all-reduce and the clip + optimiser kernels stay outside the graph (three launches): the step counter, the
+learning rate and the other hyper-parameters are host values of ``FlatAdam.step`` / ``FlatSGD.step`` and RCCL keeps its
+own stream semantics.
 
-    opt  = FlatAdam(model.parameters(), lr=1e-3)
+    opt  = FlatAdam(model.parameters(), lr=1e-3)      # or FlatSGD(model.parameters(), lr=1e-2, momentum=0.9)
     step = GraphedBackprop(model, opt, sample_batch=(mix, lens, src))
     for mix, lens, src in loader:
         loss = step(mix, lens, src)          # device scalar; gradients are in opt.flat_grads
@@ -30,7 +31,7 @@ class GraphedBackprop:
         if dev.type != "cuda":
             raise ValueError("GraphedBackprop needs the model on the GPU")
         if not hasattr(optimizer, "flat_grads"):
-            raise ValueError("GraphedBackprop needs FlatAdam (gradients must live at fixed addresses)")
+            raise ValueError("GraphedBackprop needs a flat optimiser, FlatAdam or FlatSGD (gradients must live at fixed addresses)")
         self.model, self.opt = model, optimizer
         self.mix = mix.to(dev, torch.float32).clone()
         self.lens = lens.to(dev).clone()

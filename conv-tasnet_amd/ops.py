@@ -98,7 +98,7 @@ def _c(t):
 
 
 def _sink(p):
-    """Destination view registered by FlatAdam: parameter gradients are then written straight into the flat
+    """Destination view registered by a flat optimiser (FlatAdam, FlatSGD): parameter gradients are then written straight into the flat
     gradient buffer (one use of the parameter per step: overwrite, not accumulate) and autograd gets None."""
     return getattr(p, "_ctn_grad_sink", None)
 
@@ -110,8 +110,9 @@ def _claim_sinks(p):
     owner = getattr(p, "_ctn_sink_owner", None)
     if owner is not None:
         if id(p) in owner._written:
-            raise CtnError("a second backward pass wrote into FlatAdam's gradient buffer without zero_grad() in between: "
-                           "direct gradients overwrite -- use FlatAdam(..., direct_grads=False) to accumulate over passes")
+            raise CtnError("a second backward pass wrote into the flat optimiser's gradient buffer without zero_grad() in "
+                           "between: direct gradients overwrite -- use FlatAdam / FlatSGD(..., direct_grads=False) to "
+                           "accumulate over passes")
         owner._written.add(id(p))
 
 
@@ -364,7 +365,7 @@ _ws_cache = {}
 
 # Weight-gradient GEMMs do not feed the backward chain (their results are only read by the optimiser), so in
 # direct-gradient mode they run on a second HIP stream and overlap the latency-bound tails of the chain kernels.
-# FlatAdam.step()/the gradient all-reduce join the stream again (join_side_stream()).
+# FlatAdam.step() / FlatSGD.step() / the gradient all-reduce join the stream again (join_side_stream()).
 _side = {}
 _SIDE_ENABLED = os.environ.get("CTN_SIDE_STREAM", "1") != "0"
 _CLN_SIDE = os.environ.get("CTN_CLN_SIDE", "1") != "0"     # round 2 (w4 weight-gradient kernel, 5 us slab reduce): 20.07 vs 21.7 ms/step
@@ -475,8 +476,8 @@ def cln_fwd(Y, gamma, beta, alpha, K):
 
 
 def cln_bwd(dOut, Y, mean, rstd, gamma, alpha, K, add=None, relu_ref=None, sinks=None):
-    """-> dY, dgamma[Ch], dbeta[Ch], dalpha[1]|None.  sinks = (dgamma, dbeta, dalpha) destinations (FlatAdam's flat
-    gradient views): the fixed-order finishing reductions then write there directly and None is returned for them."""
+    """-> dY, dgamma[Ch], dbeta[Ch], dalpha[1]|None.  sinks = (dgamma, dbeta, dalpha) destinations (a flat
+    optimiser's gradient views): the fixed-order finishing reductions then write there directly and None is returned for them."""
     M, Ch, Kp = Y.shape
     dY = torch.empty_like(Y)
     pc = torch.empty((lib.ctn_cln_bwd_pc_floats(M, Ch, Kp),), dtype=F32, device=Y.device)
@@ -570,7 +571,7 @@ class Frontend(torch.autograd.Function):
         dU = pw_wgrad(g, xcol, N, L, K, out=sU)
         # the first stage of the forward pass is the last node of the backward pass: every weight-gradient kernel of the
         # second stream has been issued by now -- order the current stream after them, so that p.grad / flat_grads may be
-        # read right after loss.backward() (not only by FlatAdam.step / the all-reduce, which join as well)
+        # read right after loss.backward() (not only by the flat optimiser's step / the all-reduce, which join as well)
         join_side_stream(w.device)
         return (None, None if sU is not None else dU.view(N, 1, L), _emit(dg0.view(1, N, 1), sg0),
                 _emit(db0.view(1, N, 1), sb0), None if sWb is not None else dWb.view(B, N, 1))
@@ -1007,7 +1008,7 @@ class ClnBlock(torch.autograd.Function):
         P = D.shape[-1]
         dev = x.device
         sk = ctx.sinks
-        direct = all(t is not None for t in sk)       # FlatAdam: gradients go straight into the flat buffer
+        direct = all(t is not None for t in sk)       # flat optimiser: gradients go straight into the flat buffer
         if direct:
             _claim_sinks(w1)
         # Weight gradients on the second stream: with the round-1 weight-gradient kernel this lost (22.7 vs 22.3 ms/step: the

@@ -54,7 +54,7 @@ def broadcast_parameters(model_or_flat, src=0):
 class GradientBuckets:
     """The gradient all-reduce in buckets, issued while the backward pass is still running.
 
-    FlatAdam's flat gradient is contiguous per TemporalBlock (9 tensors each, model order), so the blocks of one repeat
+    A flat optimiser's gradient (FlatAdam, FlatSGD) is contiguous per TemporalBlock (9 tensors each, model order), so the blocks of one repeat
     are one slice of it.  With this object installed (enable_overlap) the composite backward of the stack (ops.TcnGln /
     ops.TcnCln) is issued repeat by repeat -- each call ends with the weight-gradient stream joined into the main stream --
     and after each one `bucket_ready(sinks)` starts an asynchronous all-reduce of that repeat's slice: with the RCCL backend
@@ -72,7 +72,7 @@ class GradientBuckets:
         """Forget the buckets of a backward pass that was not followed by allreduce_gradients() (an exception, a skipped step,
         a diagnostic backward): wait for what was started -- every rank started the same collectives, or the job is lost
         anyway -- and drop the covered ranges, so that the next finish() reduces every slice of the NEW gradients.
-        Called by FlatAdam.zero_grad().  A backward pass under enable_overlap must be followed by allreduce_gradients() on
+        Called by the flat optimisers' zero_grad().  A backward pass under enable_overlap must be followed by allreduce_gradients() on
         every rank (or by zero_grad() on every rank)."""
         for w in self.works:
             w.wait()
@@ -102,7 +102,7 @@ class GradientBuckets:
 
 
 def enable_overlap(optimizer, blocks_per_bucket):
-    """Install bucketed, overlapped gradient all-reduce for a FlatAdam optimiser (no-op for one process).
+    """Install bucketed, overlapped gradient all-reduce for a flat optimiser (FlatAdam, FlatSGD) (no-op for one process).
     blocks_per_bucket = TemporalBlocks per bucket, normally X (one bucket per repeat)."""
     from . import ops
     if world_size() == 1 or getattr(optimizer, "flat_grads", None) is None or os.environ.get("CTN_DP_OVERLAP", "1") == "0":
@@ -116,10 +116,10 @@ def enable_overlap(optimizer, blocks_per_bucket):
 
 
 def allreduce_gradients(optimizer_or_params):
-    """Sum gradients over ranks: FlatAdam's flat buffer (one collective, or the buckets of enable_overlap that were
+    """Sum gradients over ranks: a flat optimiser's gradient buffer (one collective, or the buckets of enable_overlap that were
     started during the backward pass plus the remainder), else one flattened bucket.
 
-    Returns the scale (1/world) the caller applies (FlatAdam.step(grad_scale=...)); for plain parameter lists the
+    Returns the scale (1/world) the caller applies (FlatAdam.step / FlatSGD.step(grad_scale=...)); for plain parameter lists the
     gradients are already averaged in place and 1.0 is returned."""
     w = world_size()
     if w == 1:

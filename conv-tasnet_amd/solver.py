@@ -9,8 +9,8 @@ quirks included:
   * best-validation model saved to save_folder/model_path, optional per-epoch checkpoints      (:94-101,135-146)
 
 Underneath, one step (:188-196) is: HIP forward -> HIP PIT loss -> HIP backward -> [RCCL all-reduce of the
-flat gradient when torch.distributed is initialised] -> fused clip + Adam kernel (FlatAdam) or, for any other
-torch optimiser, clip_grad_norm_ + optimizer.step().  The model may be bare or anything exposing ``.module``.
+flat gradient when torch.distributed is initialised] -> fused clip + Adam / SGD kernel (FlatAdam, FlatSGD) or, for any
+other torch optimiser, clip_grad_norm_ + optimizer.step().  The model may be bare or anything exposing ``.module``.
 visdom is optional and only imported when one of the visdom flags is set.
 
 Data parallel (one process per GPU) keeps the reference's single-decision semantics of nn.DataParallel
@@ -26,7 +26,7 @@ import time
 import torch
 
 from . import parallel
-from .optim import FlatAdam
+from .optim import FlatOptimizer
 from .pit_criterion import cal_loss
 
 SolverArgs = collections.namedtuple(
@@ -72,7 +72,7 @@ class Solver(object):
         self.iter_losses = []                         # every batch loss seen, python floats
         self._plot = self._make_plotter() if (a.visdom_enabled or a.visdom_epoch) else None
         self._rank0 = (not torch.distributed.is_initialized()) or torch.distributed.get_rank() == 0
-        if isinstance(optimizer, FlatAdam):
+        if isinstance(optimizer, FlatOptimizer):
             # N > 1: the gradient all-reduce goes out in one bucket per repeat while the backward pass is still running
             parallel.enable_overlap(optimizer, int(getattr(self.net, "X", 0) or 0))
         self._reset()
@@ -195,7 +195,7 @@ class Solver(object):
         opt = self.optimizer
         opt.zero_grad()
         loss.backward()
-        if isinstance(opt, FlatAdam):
+        if isinstance(opt, FlatOptimizer):
             opt.step(max_grad_norm=self.max_norm, grad_scale=parallel.allreduce_gradients(opt))
             return
         params = list(self.model.parameters())

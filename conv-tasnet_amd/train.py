@@ -1,4 +1,4 @@
-"""train(): launcher mirroring src/train.py:14-102 (paper config, Adam lr 1e-3, clip 5, half-lr, early stop).
+"""train(): launcher mirroring src/train.py:14-102 (paper config, Adam lr 1e-3 or SGD, L2, clip 5, half-lr, early stop).
 
 The reference's train() hard-codes librosa/json data loading; here the loaders are arguments (any iterables of
 (padded_mixture [B,T], mixture_lengths [B], padded_source [B,C,T]) -- the AudioDataLoader contract) and a synthetic
@@ -12,7 +12,7 @@ import torch
 
 from . import parallel
 from .conv_tasnet import ConvTasNet
-from .optim import FlatAdam
+from .optim import FlatAdam, FlatSGD
 from .solver import Solver
 
 PAPER = dict(N=256, L=20, B=256, H=512, P=3, X=8, R=4, C=2, norm_type='gLN', causal=0, mask_nonlinear='relu')
@@ -49,15 +49,25 @@ class SyntheticLoader:
 
 
 def train(data, epochs, model_path, save_folder="exp/models", continue_from="", config=None, lr=1e-3,
-          max_grad_norm=5, half_lr=1, early_stop=1, print_freq=10, enable_checkpoint=0):
-    """data = {'tr_loader': ..., 'cv_loader': ...}.  Returns the Solver after training."""
+          max_grad_norm=5, half_lr=1, early_stop=1, print_freq=10, enable_checkpoint=0, optimizer_type='adam',
+          momentum=0.0, l2=0.0):
+    """data = {'tr_loader': ..., 'cv_loader': ...}.  Returns the Solver after training.
+
+    optimizer_type 'sgd' -> FlatSGD(lr, momentum, weight_decay=l2), 'adam' -> FlatAdam(lr, weight_decay=l2)
+    (src/train.py:87-98); any other value prints 'Not support optimizer' and returns None, as the reference does."""
+    if optimizer_type not in ('sgd', 'adam'):
+        print("Not support optimizer")
+        return None
     world, rank, device = parallel.init_distributed()
     cfg = dict(PAPER if config is None else config)
     torch.manual_seed(0)
     model = ConvTasNet(cfg['N'], cfg['L'], cfg['B'], cfg['H'], cfg['P'], cfg['X'], cfg['R'], cfg['C'],
                        norm_type=cfg.get('norm_type', 'gLN'), causal=cfg.get('causal', 0),
                        mask_nonlinear=cfg.get('mask_nonlinear', 'relu')).to(device)
-    optimizer = FlatAdam(model.parameters(), lr=lr)
+    if optimizer_type == 'sgd':
+        optimizer = FlatSGD(model.parameters(), lr=lr, momentum=momentum, weight_decay=l2)
+    else:
+        optimizer = FlatAdam(model.parameters(), lr=lr, weight_decay=l2)
     parallel.broadcast_parameters(optimizer.flat_params)
     arg_solver = (1, epochs, half_lr, early_stop, max_grad_norm, save_folder, enable_checkpoint, continue_from,
                   model_path, print_freq, 0, 0, "Conv-TasNet Training")
@@ -75,6 +85,10 @@ def main():
                     "(the reference's manifest layout); default: synthetic mixtures")
     ap.add_argument("--model-path", default="final.pth.tar")
     ap.add_argument("--save-folder", default="exp/models")
+    ap.add_argument("--optimizer", choices=("adam", "sgd"), default="adam")
+    ap.add_argument("--lr", type=float, default=1e-3)
+    ap.add_argument("--momentum", type=float, default=0.0, help="SGD momentum")
+    ap.add_argument("--l2", type=float, default=0.0, help="weight decay (coupled L2) of either optimiser")
     a = ap.parse_args()
     world, rank, _ = parallel.init_distributed()
     if a.data_dir:
@@ -87,7 +101,8 @@ def main():
     else:
         tr = SyntheticLoader(a.batches, a.batch_size, rank=rank, world=world)
         cv = SyntheticLoader(1, a.batch_size, first_utt=10 ** 6, rank=rank, world=world)
-    train({'tr_loader': tr, 'cv_loader': cv}, a.epochs, a.model_path, save_folder=a.save_folder)
+    train({'tr_loader': tr, 'cv_loader': cv}, a.epochs, a.model_path, save_folder=a.save_folder, lr=a.lr,
+          optimizer_type=a.optimizer, momentum=a.momentum, l2=a.l2)
 
 
 if __name__ == "__main__":

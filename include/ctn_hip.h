@@ -450,6 +450,20 @@ int ctn_clip_adam_step(float* params, const float* grads, float* exp_avg, float*
                        float grad_scale, float max_norm, float lr, float beta1, float beta2, float eps, int step,
                        float* total_norm_out, double* workspace, void* stream);
 int ctn_optim_parts(void);
+/* The same clip (the norm is of the clipped gradient g' only; the decay term comes after it, as the reference Solver clips
+ * before optimizer.step() adds it), then the torch.optim.SGD update of src/train.py:87-91 (optimizer_type 'sgd',
+ * momentum, weight_decay = l2):  d = g' + weight_decay*p;  with momentum != 0:  buf = first_step ? d :
+ * momentum*buf + (1-dampening)*d,  d = nesterov ? d + momentum*buf : buf;  p -= lr*d.
+ * momentum_buf may be NULL (and is never touched) when momentum == 0; nesterov needs momentum > 0, dampening == 0.
+ * params, grads, momentum_buf 16-byte aligned.  workspace: ctn_optim_parts() doubles. */
+int ctn_clip_sgd_step(float* params, const float* grads, float* momentum_buf, long long n, float grad_scale,
+                      float max_norm, float lr, float momentum, float dampening, float weight_decay, int nesterov,
+                      int first_step, float* total_norm_out, double* workspace, void* stream);
+/* ctn_clip_adam_step with coupled L2 (src/train.py:92-95 with weight_decay = l2 > 0, torch.optim.Adam(weight_decay=...),
+ * not AdamW): the Adam update of g' + weight_decay*p.  All four buffers 16-byte aligned. */
+int ctn_clip_adam_l2_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, long long n,
+                          float grad_scale, float max_norm, float lr, float beta1, float beta2, float eps, int step,
+                          float weight_decay, float* total_norm_out, double* workspace, void* stream);
 
 #ifdef __cplusplus
 }
