@@ -3,12 +3,14 @@
 ``evaluate(model_path, data_dir, calc_sdr, use_cuda, sample_rate, batch_size)`` is the reference's entry point
 (src/evaluate.py:21): it loads the checkpoint, reads data_dir/{mix,s1,s2}.json through data.AudioDataset (full
 utterances, scipy wav reader) and prints per-utterance and average SI-SNRi.  ``evaluate_loader(model, data_loader)`` is
-the same loop over any iterable of (padded_mixture, mixture_lengths, padded_source) batches.  calc_sdr needs mir_eval's
-bss_eval_sources (third party, CPU, "very very slow" :78): outside the hot-path scope, an explicit error here.
+the same loop over any iterable of (padded_mixture, mixture_lengths, padded_source) batches.  SDRi (cal_SDRi, :76-91) is
+BSS Eval v3 on the GPU in fp64 (bss_eval.py): ``cal_SDRi`` for one utterance, ``evaluate_loader(..., calc_sdr=True)`` for
+a whole loader, one bss_eval_batch call per batch with the mixture as an extra estimate row.
 """
 import numpy as np
 import torch
 
+from .bss_eval import bss_eval_batch, sdr_improvement
 from .conv_tasnet import ConvTasNet
 from .pit_criterion import cal_loss
 from .utils import remove_pad
@@ -31,11 +33,26 @@ def cal_SISNRi(src_ref, src_est, mix):
     return (gains[0] + gains[1]) / 2
 
 
+def cal_SDRi(src_ref, src_est, mix):
+    """SDR improvement over using the mixture itself; two speakers, like src/evaluate.py:76-91.  src_ref, src_est [2, n],
+    mix [n] (numpy or torch) -> float: ((sdr[0]-sdr0[0]) + (sdr[1]-sdr0[1])) / 2 with sdr from bss_eval_sources(src_ref,
+    src_est) and sdr0 from bss_eval_sources(src_ref, [mix, mix]), both in one GPU call (the anchor is one extra row)."""
+    ref, est, mx = (torch.as_tensor(np.asarray(x) if not torch.is_tensor(x) else x) for x in (src_ref, src_est, mix))
+    if ref.shape != est.shape or ref.dim() != 2 or mx.shape != ref.shape[1:]:
+        raise ValueError("cal_SDRi: src_ref %s, src_est %s and mix %s do not match" % (tuple(ref.shape), tuple(est.shape),
+                                                                                   tuple(mx.shape)))
+    dev = torch.device("cuda", torch.cuda.current_device())
+    rows = torch.cat([est.reshape(ref.shape), mx.reshape(1, -1)], 0).to(dev, torch.float32)
+    sdr, sir, _, _ = bss_eval_batch(ref.to(dev, torch.float32).unsqueeze(0), rows.unsqueeze(0),
+                                    torch.tensor([ref.shape[1]], device=dev))
+    return float(sdr_improvement(sdr, sir)[0])
+
+
 def evaluate(model_path, data_dir, calc_sdr=0, use_cuda=1, sample_rate=8000, batch_size=1):
     """The reference's signature (src/evaluate.py:21-73).  -> average SI-SNRi over data_dir's utterances."""
     if calc_sdr:
-        raise NotImplementedError("calc_sdr needs mir_eval.separation.bss_eval_sources (third party, CPU only): outside "
-                                  "the hot-path scope -- SI-SNRi is computed, SDRi is not")
+        raise NotImplementedError("evaluate(calc_sdr=1) is not switched on: SDRi is computed by "
+                                  "evaluate_loader(..., calc_sdr=True) and cal_SDRi (GPU BSS Eval, bss_eval.py)")
     from .data import AudioDataLoader, AudioDataset
     model = ConvTasNet.load_model(model_path)
     print(model)
@@ -44,8 +61,10 @@ def evaluate(model_path, data_dir, calc_sdr=0, use_cuda=1, sample_rate=8000, bat
     return evaluate_loader(model, data_loader, use_cuda=bool(use_cuda))
 
 
-def evaluate_loader(model, data_loader, use_cuda=True, verbose=True):
-    """-> average SI-SNRi over every utterance of the loader.  `model` is a ConvTasNet or a checkpoint path."""
+def evaluate_loader(model, data_loader, use_cuda=True, verbose=True, calc_sdr=False):
+    """-> average SI-SNRi over every utterance of the loader; with calc_sdr (src/evaluate.py:62-72) -> (average SI-SNRi,
+    average SDRi), every batch scored by one bss_eval_batch call (the mixture is an extra estimate row, so its anchor
+    SDRs come out of the same call).  `model` is a ConvTasNet or a checkpoint path."""
     if isinstance(model, str):
         model = ConvTasNet.load_model(model)
     model.eval()
@@ -53,6 +72,7 @@ def evaluate_loader(model, data_loader, use_cuda=True, verbose=True):
         model.cuda()
     dev = next(model.parameters()).device
     total, count = 0.0, 0
+    total_sdri = 0.0
     with torch.no_grad():
         for padded_mixture, mixture_lengths, padded_source in data_loader:
             padded_mixture = padded_mixture.to(dev)
@@ -63,13 +83,28 @@ def evaluate_loader(model, data_loader, use_cuda=True, verbose=True):
             mixture = remove_pad(padded_mixture, mixture_lengths)
             source = remove_pad(padded_source, mixture_lengths)
             est = remove_pad(reorder, mixture_lengths)       # NOTE: the reordered estimate, as the reference does
-            for mix, ref, out in zip(mixture, source, est):
+            sdri = None
+            if calc_sdr:
+                rows = torch.cat([reorder, padded_mixture.unsqueeze(1)], 1)
+                sdr, sir, _, _ = bss_eval_batch(padded_source, rows, mixture_lengths)
+                sdri = sdr_improvement(sdr, sir).tolist()
+            for u, (mix, ref, out) in enumerate(zip(mixture, source, est)):
+                if sdri is not None:
+                    total_sdri += sdri[u]
+                    if verbose:
+                        print("\tSDRi=%.2f" % sdri[u])
                 v = cal_SISNRi(ref.astype(np.float64), out.astype(np.float64), mix.astype(np.float64))
                 if verbose:
                     print("Utt %d\tSI-SNRi=%.2f" % (count + 1, v))
                 total += v
                 count += 1
     avg = total / max(count, 1)
+    if calc_sdr:
+        avg_sdri = total_sdri / max(count, 1)
+        if verbose:
+            print("Average SDR improvement: {0:.2f}".format(avg_sdri))
+            print("Average SISNR improvement: {0:.2f}".format(avg))
+        return avg, avg_sdri
     if verbose:
         print("Average SISNR improvement: {0:.2f}".format(avg))
     return avg

@@ -465,6 +465,44 @@ int ctn_clip_adam_l2_step(float* params, const float* grads, float* exp_avg, flo
                           float grad_scale, float max_norm, float lr, float beta1, float beta2, float eps, int step,
                           float weight_decay, float* total_norm_out, double* workspace, void* stream);
 
+/* ---- BSS Eval v3: SDR / SIR / SAR in fp64 ------------------------------------------------------------------------------
+ * replaces mir_eval.separation.bss_eval_sources(reference_sources, estimated_sources) (compute_permutation=True, 512-tap
+ * distortion filters) as called by cal_SDRi, src/evaluate.py:76-91, and by the calc_sdr branch of evaluate, :62-72.
+ * ref: [B,C,T] fp32 references, est: [B,E,T] fp32 estimate rows (cal_SDRi's mixture anchor can be one extra row), lengths:
+ * [B] int64; samples at t >= lengths[b] count as zero in both.  2 <= C <= 4, E >= 1, T >= 1; all arithmetic fp64.
+ * The time partition of every reduction depends on lengths[b] only: an utterance scores bitwise the same in any batch.
+ *   ctn_bss_eval: everything below in one call -> sdr, sir, sar [B,E,C] fp64 (row e scored against reference j; the SIR
+ *     permutation choice over them is the caller's), status [B,C] int32 (0: factorised; else 1 + the first pivot that was
+ *     not finite or not above dim*eps*max diag: [b,0] = G (C*512 square, whose leading block also serves G_00), [b,j] = G_jj;
+ *     an utterance with a non-zero status has undefined numbers and must be redone another way).
+ *     workspace: ctn_bss_workspace() bytes, grows as B*(C*512)^2*8.
+ * The stages, each on caller buffers:
+ *   ctn_bss_corr: r [B,C,C,512] r[b,i,k,tau] = sum_t s_i[t] s_k[t+tau]; d [B,E,C,512] d[b,e,i,a] = sum_t s_i[t] e[t+a];
+ *     enorm [B,E] = sum_t e[t]^2.  workspace: ctn_bss_corr_workspace() bytes.
+ *   ctn_bss_factor: Gram matrices from r and their Cholesky factors (lower triangle) in factors (ctn_bss_factor_doubles()
+ *     doubles: B matrices of (C*512)^2, then B*(C-1) of 512^2 for G_11.. G_{C-1,C-1}), status as above.
+ *   ctn_bss_solve: coef_all [B,E,C*512] = G^-1 d[b,e];  coef_own [B,E,C,512] = G_jj^-1 d[b,e,j].
+ *   ctn_bss_project: P_all e, P_j e as 512-tap FIRs of the references over the n+511 samples of the padded signals; the
+ *     residual energies accumulated explicitly -> sdr, sir, sar; energies [B,E,3C+2] (nullable): per j ||P_j e||^2,
+ *     ||e - P_j e||^2, ||P_all e - P_j e||^2, then ||P_all e||^2, ||e - P_all e||^2.  workspace: ctn_bss_project_workspace().
+ *   sdr = 10 log10(||P_j e||^2 / ||e - P_j e||^2), sir = 10 log10(||P_j e||^2 / ||P_all e - P_j e||^2),
+ *   sar = 10 log10(||P_all e||^2 / ||e - P_all e||^2); a zero denominator gives +inf. */
+#define CTN_BSS_FLEN 512
+size_t ctn_bss_workspace(long long B, int C, long long E, long long T);
+int ctn_bss_eval(const float* ref, const float* est, const long long* lengths, long long B, int C, long long E, long long T,
+                 double* sdr, double* sir, double* sar, int* status, void* workspace, size_t workspace_bytes, void* stream);
+size_t ctn_bss_corr_workspace(long long B, int C, long long E, long long T);
+int ctn_bss_corr(const float* ref, const float* est, const long long* lengths, long long B, int C, long long E, long long T,
+                 double* r, double* d, double* enorm, void* workspace, size_t workspace_bytes, void* stream);
+size_t ctn_bss_factor_doubles(long long B, int C);
+int ctn_bss_factor(const double* r, long long B, int C, double* factors, int* status, void* stream);
+int ctn_bss_solve(const double* factors, const double* d, long long B, int C, long long E, double* coef_all, double* coef_own,
+                  void* stream);
+size_t ctn_bss_project_workspace(long long B, int C, long long E, long long T);
+int ctn_bss_project(const float* ref, const float* est, const long long* lengths, const double* coef_all, const double* coef_own,
+                    long long B, int C, long long E, long long T, double* sdr, double* sir, double* sar, double* energies,
+                    void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
