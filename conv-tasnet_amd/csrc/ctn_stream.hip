@@ -1,0 +1,641 @@
+// Fused low-latency streaming inference for the causal cLN model (include/ctn_hip.h, "streaming" section).
+//
+// Everything of the causal stack except the depthwise taps is frame-local, so one workgroup carries a tile of ST_TC frame columns of
+// ONE stream through   depthwise -> PReLU -> cLN -> 1x1 + residual -> next block's 1x1 -> PReLU -> cLN   in LDS (a "stage").  The only
+// data that crosses workgroups is the depthwise history; it lives in one ring buffer per block, written by stage j and read by
+// stage j+1 (the next launch).  nblocks + 1 stage launches per chunk instead of 9 per block, no cat / pad copies, no 64-frame padding.
+// Chunks of at most one tile per stream (the low-latency case) run the same block boundary as two launches whose workgroups split
+// the GEMMs' output rows, so that one stream's weights are streamed by up to 16 CUs instead of one (stream_rows_a / _b below).
+//
+// Arithmetic is frame-local and fixed-order: every output value of frame k of stream m is a k-ordered fp32 FMA chain
+// (v_mfma_f32_16x16x4_f32) or a fixed-order sum over the channels of that frame alone, so it does not depend on the chunk the frame
+// arrived in, on its column position in a tile, or on the other streams.
+#include "ctn_common.h"
+#include <algorithm>
+
+namespace {
+
+constexpr int ST_NT = 1024;       // threads per workgroup: 4 waves per SIMD hide the weight-load latency of the one resident tile
+constexpr int ST_NW = ST_NT / 64; // waves
+constexpr int ST_TC = 16;         // frame columns per tile (the N of the 16x16x4 MFMA)
+constexpr int ST_GRP = ST_NT / ST_TC;   // channel groups of the cLN partial sums
+constexpr int ST_MAXP = 8;        // depthwise taps
+constexpr int ST_MAXC = 8;        // speakers (softmax mask)
+constexpr int ST_HDR = 64;        // floats in front of the rings: word 0 = frame position
+constexpr size_t ST_MAX_LDS = 64 * 1024;
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+inline int c16(int n) { return (n + 15) / 16; }
+inline long long pow2ceil(long long n) { long long r = 1; while (r < n) r <<= 1; return r; }
+inline long long ring_len(int P, int d, int max_frames) { return pow2ceil((long long)(P - 1) * d + max_frames); }
+// one block of the packed stack: W1 fragments [H,B], W2 fragments [B,H], (alpha1, alpha2, 0, 0), gamma1, beta1, gamma2, beta2 [H], D [H,P]
+inline size_t block_floats(int B, int H, int P) { return (size_t)2 * H * B + 4 + (size_t)4 * H + (size_t)H * P; }
+
+enum { EPI_STORE = 0, EPI_ADD = 1, EPI_RELU = 2 };
+
+// ---- weights -> MFMA fragment order --------------------------------------------------------------------------------
+// W [R, Cn] row-major -> float4 [ceil(R/16)][ceil(Cn/16)][64 lanes]: element i of lane l in (row tile rt, k group g) is
+// W[rt*16 + (l & 15)][g*16 + i*4 + (l >> 4)] = the A operand of k-step g*4+i; rows / columns past R / Cn are exact zeros.
+__global__ __launch_bounds__(256) void stream_pack_kernel(const float* __restrict__ W, float* __restrict__ out, int R, int Cn) {
+    const int Rt = (R + 15) / 16, G = (Cn + 15) / 16;
+    const long long n = (long long)Rt * G * 256;
+    for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < n; e += (long long)gridDim.x * 256) {
+        const int i = (int)(e & 3), l = (int)((e >> 2) & 63);
+        const long long t = e >> 8;
+        const int g = (int)(t % G), rt = (int)(t / G);
+        const int row = rt * 16 + (l & 15), k = g * 16 + i * 4 + (l >> 4);
+        out[e] = (row < R && k < Cn) ? W[(size_t)row * Cn + k] : 0.f;
+    }
+}
+
+__global__ __launch_bounds__(256) void stream_pack_vec_kernel(const float* __restrict__ a1, const float* __restrict__ g1,
+                                                             const float* __restrict__ b1, const float* __restrict__ D,
+                                                             const float* __restrict__ a2, const float* __restrict__ g2,
+                                                             const float* __restrict__ b2, float* __restrict__ out, int H, int P) {
+    const int n = 4 + 4 * H + H * P;
+    for (int e = blockIdx.x * 256 + threadIdx.x; e < n; e += gridDim.x * 256) {
+        float v;
+        if (e < 4) v = e == 0 ? a1[0] : e == 1 ? a2[0] : 0.f;
+        else if (e < 4 + H) v = g1[e - 4];
+        else if (e < 4 + 2 * H) v = b1[e - 4 - H];
+        else if (e < 4 + 3 * H) v = g2[e - 4 - 2 * H];
+        else if (e < 4 + 4 * H) v = b2[e - 4 - 3 * H];
+        else v = D[e - 4 - 4 * H];
+        out[e] = v;
+    }
+}
+
+// ---- tile primitives (all operands in LDS as [channels][ST_TC]) -----------------------------------------------------
+// NB k groups (16 k values each) of NTILE row tiles: every weight fragment of the batch is requested before the first MFMA, so a
+// wave has NB * NTILE KB in flight and pays one memory latency per batch, not per k group (the loads return in order, the MFMAs wait
+// with counted vmcnt).  No conditional around a load.  The B operand of k-step s is act[4s + (l>>4)][l&15] = 64 consecutive floats.
+template <int NTILE, int NB>
+__device__ __forceinline__ void gemm_batch(const float4* __restrict__ ap, int G, const float* b, f32x4 (&c)[NTILE]) {
+    float4 a[NTILE][NB];
+#pragma unroll
+    for (int i = 0; i < NB; ++i)
+#pragma unroll
+        for (int t = 0; t < NTILE; ++t) a[t][i] = ap[((size_t)t * G + i) * 64];
+    __builtin_amdgcn_sched_barrier(0);      // the scheduler otherwise sinks every load to just in front of its MFMAs
+#pragma unroll
+    for (int i = 0; i < NB; ++i) {
+        const float b0 = b[i * 256], b1 = b[i * 256 + 64], b2 = b[i * 256 + 128], b3 = b[i * 256 + 192];
+#pragma unroll
+        for (int t = 0; t < NTILE; ++t) c[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[t][i].x, b0, c[t], 0, 0, 0);
+#pragma unroll
+        for (int t = 0; t < NTILE; ++t) c[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[t][i].y, b1, c[t], 0, 0, 0);
+#pragma unroll
+        for (int t = 0; t < NTILE; ++t) c[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[t][i].z, b2, c[t], 0, 0, 0);
+#pragma unroll
+        for (int t = 0; t < NTILE; ++t) c[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[t][i].w, b3, c[t], 0, 0, 0);
+    }
+}
+
+// NTILE consecutive row tiles from rt on: one k-ordered FMA chain per output element, whatever NTILE and the batch sizes are.
+template <int EPI, int NTILE>
+__device__ __forceinline__ void gemm_rows(const float4* __restrict__ Wp, int rt, int G, const float* act, float* out) {
+    const int lane = threadIdx.x & 63;
+    const float4* __restrict__ ap = Wp + (size_t)rt * G * 64 + lane;
+    const float* b = act + lane;
+    f32x4 c[NTILE];
+#pragma unroll
+    for (int t = 0; t < NTILE; ++t) c[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+    int g = 0;
+    if (NTILE == 1)
+        for (; g + 16 <= G; g += 16) gemm_batch<NTILE, 16>(ap + (size_t)g * 64, G, b + g * 256, c);
+    for (; g + 8 <= G; g += 8) gemm_batch<NTILE, 8>(ap + (size_t)g * 64, G, b + g * 256, c);
+    if (g + 4 <= G) { gemm_batch<NTILE, 4>(ap + (size_t)g * 64, G, b + g * 256, c); g += 4; }
+    if (g + 2 <= G) { gemm_batch<NTILE, 2>(ap + (size_t)g * 64, G, b + g * 256, c); g += 2; }
+    if (g < G) gemm_batch<NTILE, 1>(ap + (size_t)g * 64, G, b + g * 256, c);
+    // C/D map: column = lane & 15, row = (lane >> 4) * 4 + register
+#pragma unroll
+    for (int t = 0; t < NTILE; ++t) {
+        float* o = out + ((size_t)(rt + t) * 16 + (lane >> 4) * 4) * ST_TC + (lane & 15);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            if (EPI == EPI_ADD) o[r * ST_TC] += c[t][r];
+            else o[r * ST_TC] = EPI == EPI_RELU ? fmaxf(c[t][r], 0.f) : c[t][r];
+        }
+    }
+}
+
+// out[Rt tiles of 16 rows][ST_TC] (op)= Wp . act[G*16][ST_TC].  A wave owns two row tiles at a time when there are enough of them (two
+// independent accumulators cover the 40-cycle dependent latency of the 32-cycle MFMA), else one, so that no wave idles.
+template <int EPI>
+__device__ __forceinline__ void tile_gemm(const float* __restrict__ Wp_, int Rt, int G, const float* act, float* out) {
+    const float4* __restrict__ Wp = reinterpret_cast<const float4*>(Wp_);
+    const int wave = threadIdx.x >> 6;
+    if (Rt >= 2 * ST_NW) {
+        int rt = wave * 2;
+        for (; rt + 1 < Rt; rt += ST_NW * 2) gemm_rows<EPI, 2>(Wp, rt, G, act, out);
+        if (rt < Rt) gemm_rows<EPI, 1>(Wp, rt, G, act, out);
+    } else {
+        for (int rt = wave; rt < Rt; rt += ST_NW) gemm_rows<EPI, 1>(Wp, rt, G, act, out);
+    }
+}
+
+// In place: t = gamma * ((prelu(t) - mean) * rstd) + beta per column over the Ch rows (src/conv_tasnet.py:313-335: biased variance,
+// eps 1e-8), two passes over the values held in LDS.  Thread (group g, column c) sums rows g, g+ST_GRP, ...; the ST_GRP partials of a
+// column are then added in ascending group order by every thread: one fixed order for every column.  part: ST_GRP*ST_TC floats.
+// Starts and ends with a workgroup barrier.
+__device__ __forceinline__ void tile_cln(float* t, int Ch, const float* __restrict__ alpha_p, const float* __restrict__ gamma,
+                                         const float* __restrict__ beta, float* part) {
+    const int col = threadIdx.x & (ST_TC - 1), grp = threadIdx.x / ST_TC;
+    const bool has_a = alpha_p != nullptr;
+    const float al = has_a ? alpha_p[0] : 1.f;
+    __syncthreads();
+    float s = 0.f;
+    for (int r = grp; r < Ch; r += ST_GRP) {
+        float v = t[r * ST_TC + col];
+        if (has_a) { v = prelu_f(v, al); t[r * ST_TC + col] = v; }
+        s += v;
+    }
+    part[grp * ST_TC + col] = s;
+    __syncthreads();
+    float tot = 0.f;
+#pragma unroll
+    for (int i = 0; i < ST_GRP; ++i) tot += part[i * ST_TC + col];
+    const float mu = tot / (float)Ch;
+    __syncthreads();
+    float q = 0.f;
+    for (int r = grp; r < Ch; r += ST_GRP) {
+        const float v = t[r * ST_TC + col] - mu;
+        q += v * v;
+    }
+    part[grp * ST_TC + col] = q;
+    __syncthreads();
+    tot = 0.f;
+#pragma unroll
+    for (int i = 0; i < ST_GRP; ++i) tot += part[i * ST_TC + col];
+    const float rs = 1.0f / sqrtf(tot / (float)Ch + CTN_EPS);
+    for (int r = grp; r < Ch; r += ST_GRP) t[r * ST_TC + col] = gamma[r] * ((t[r * ST_TC + col] - mu) * rs) + beta[r];
+    __syncthreads();
+}
+
+// global [rows][ld] columns k0 .. k0+nvalid-1 <-> LDS [rows][ST_TC]; columns past nvalid are zeros in LDS and are never stored
+__device__ __forceinline__ void tile_load(float* t, const float* __restrict__ g, int rows, int ld, int k0, int nvalid) {
+    for (int e = threadIdx.x; e < rows * ST_TC; e += ST_NT) {
+        const int r = e / ST_TC, c = e & (ST_TC - 1);
+        const float v = g[(size_t)r * ld + k0 + min(c, nvalid - 1)];      // unconditional (clamped) load, then select: no branch per element
+        t[e] = c < nvalid ? v : 0.f;
+    }
+}
+__device__ __forceinline__ void tile_store(const float* t, float* __restrict__ g, int rows, int ld, int k0, int nvalid) {
+    for (int e = threadIdx.x; e < rows * ST_TC; e += ST_NT) {
+        const int r = e / ST_TC, c = e & (ST_TC - 1);
+        if (c < nvalid) g[(size_t)r * ld + k0 + c] = t[e];
+    }
+}
+
+// Causal depthwise taps of a tile: z[h][c] = sum_t D[h,t] * n1[h][frame(c) - (P-1-t)*d], the current frame (t = P-1) and the past, one
+// ascending-t FMA chain per element.  n1 comes from the block's ring; with INTILE the frames of this tile are taken from `cur`
+// (LDS [H][ST_TC], column 0 = frame pos) instead, because the ring does not hold them yet (same values either way).  Every ring load
+// is unconditional (clamped) and issued before the first FMA: one memory latency for the whole tile.  Thread t owns elements
+// t, t + ST_NT, ...: z[i] (NI = ceil(H * ST_TC / ST_NT)); PT = P when specialised, 0 = run-time tap count.
+template <int NI, int PT, bool INTILE>
+__device__ __forceinline__ void tile_dw(float (&z)[NI], const float* __restrict__ ring, int R, unsigned pos, int d, int H, int P,
+                                        const float* __restrict__ D, const float* cur) {
+    const unsigned mask = (unsigned)R - 1u;
+    const int last = H * ST_TC - 1;
+    if (PT > 0) {
+        float v[NI][PT > 0 ? PT : 1], w[NI][PT > 0 ? PT : 1];
+#pragma unroll
+        for (int i = 0; i < NI; ++i) {
+            const int e = min((int)threadIdx.x + i * ST_NT, last), h = e / ST_TC, c = e & (ST_TC - 1);
+#pragma unroll
+            for (int t = 0; t < PT; ++t) {
+                v[i][t] = ring[(size_t)h * R + ((pos + (unsigned)c - (unsigned)((PT - 1 - t) * d)) & mask)];
+                w[i][t] = D[h * PT + t];
+            }
+        }
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int i = 0; i < NI; ++i) {
+            const int e = min((int)threadIdx.x + i * ST_NT, last), c = e & (ST_TC - 1);
+            float acc = 0.f;
+#pragma unroll
+            for (int t = 0; t < PT; ++t) {
+                const int off = (PT - 1 - t) * d;
+                float x = v[i][t];
+                if (INTILE && off <= c) x = cur[e - off];
+                acc = fmaf(w[i][t], x, acc);
+            }
+            z[i] = acc;
+        }
+    } else {
+#pragma unroll
+        for (int i = 0; i < NI; ++i) {
+            const int e = min((int)threadIdx.x + i * ST_NT, last), h = e / ST_TC, c = e & (ST_TC - 1);
+            float acc = 0.f;
+            for (int t = 0; t < P; ++t) {
+                const int off = (P - 1 - t) * d;
+                float x = ring[(size_t)h * R + ((pos + (unsigned)c - (unsigned)off) & mask)];
+                if (INTILE && off <= c) x = cur[e - off];
+                acc = fmaf(D[h * P + t], x, acc);
+            }
+            z[i] = acc;
+        }
+    }
+}
+
+// dst (LDS [H][ST_TC]) = taps; dst may be `cur` (the values are held in registers across a barrier).
+template <int NI, bool INTILE>
+__device__ __forceinline__ void tile_dw_to(float* dst, const float* __restrict__ ring, int R, unsigned pos, int d, int H, int P,
+                                           const float* __restrict__ D, const float* cur) {
+    float z[NI];
+    if (P == 3) tile_dw<NI, 3, INTILE>(z, ring, R, pos, d, H, P, D, cur);
+    else tile_dw<NI, 0, INTILE>(z, ring, R, pos, d, H, P, D, cur);
+    if (INTILE) __syncthreads();
+#pragma unroll
+    for (int i = 0; i < NI; ++i) {
+        const int e = (int)threadIdx.x + i * ST_NT;
+        if (e < H * ST_TC) dst[e] = z[i];
+    }
+}
+template <bool INTILE>
+__device__ __forceinline__ void tile_dw_any(float* dst, const float* __restrict__ ring, int R, unsigned pos, int d, int H, int P,
+                                            const float* __restrict__ D, const float* cur) {
+    const int ni = (H * ST_TC + ST_NT - 1) / ST_NT;        // H <= 1024: at most 16 elements per thread
+    if (ni <= 1) tile_dw_to<1, INTILE>(dst, ring, R, pos, d, H, P, D, cur);
+    else if (ni <= 4) tile_dw_to<4, INTILE>(dst, ring, R, pos, d, H, P, D, cur);
+    else if (ni <= 8) tile_dw_to<8, INTILE>(dst, ring, R, pos, d, H, P, D, cur);
+    else tile_dw_to<16, INTILE>(dst, ring, R, pos, d, H, P, D, cur);
+}
+
+__device__ __forceinline__ void ring_store(float* __restrict__ ring, int R, unsigned pos, const float* t, int H, int nvalid) {
+    const unsigned mask = (unsigned)R - 1u;
+    for (int e = threadIdx.x; e < H * ST_TC; e += ST_NT) {
+        const int h = e / ST_TC, c = e & (ST_TC - 1);
+        if (c < nvalid) ring[(size_t)h * R + ((pos + (unsigned)c) & mask)] = t[e];
+    }
+}
+
+// ---- stage j of the stack -------------------------------------------------------------------------------------------
+struct StageArgs {
+    const float* prev;      // packed block j-1 (null for j = 0)
+    const float* cur;       // packed block j   (null for j = nblocks)
+    float* y;               // [M,B,F], in place
+    const float* ring_prev; // [M,H,Rp]   (j >= 1)
+    float* ring_cur;        // [M,H,Rc]   (j < nblocks)
+    const unsigned* pos;    // device word: index of this chunk's first frame
+    int Rp, dp, Rc;
+    int B, H, P, F, tiles;
+};
+
+__global__ __launch_bounds__(ST_NT) void stream_stage_kernel(StageArgs a) {
+    extern __shared__ float lds[];
+    float* ybuf = lds;                              // [B][16]
+    float* hbuf = ybuf + (size_t)a.B * ST_TC;       // [H][16]
+    float* part = hbuf + (size_t)a.H * ST_TC;       // [ST_GRP][16]
+    const int m = blockIdx.x / a.tiles, k0 = (blockIdx.x % a.tiles) * ST_TC;
+    const int nvalid = min(ST_TC, a.F - k0);
+    const unsigned pos = a.pos[0] + (unsigned)k0;
+    const int B = a.B, H = a.H, P = a.P;
+    float* yg = a.y + (size_t)m * B * a.F;
+    tile_load(ybuf, yg, B, a.F, k0, nvalid);
+    if (a.prev) {
+        const float* vec = a.prev + (size_t)2 * H * B;
+        tile_dw_any<false>(hbuf, a.ring_prev + (size_t)m * H * a.Rp, a.Rp, pos, a.dp, H, P, vec + 4 + 4 * H, nullptr);
+        tile_cln(hbuf, H, vec + 1, vec + 4 + 2 * H, vec + 4 + 3 * H, part);
+        tile_gemm<EPI_ADD>(a.prev + (size_t)H * B, B / 16, H / 16, hbuf, ybuf);
+        __syncthreads();
+        tile_store(ybuf, yg, B, a.F, k0, nvalid);
+    }
+    if (a.cur) {
+        const float* vec = a.cur + (size_t)2 * H * B;
+        __syncthreads();
+        tile_gemm<EPI_STORE>(a.cur, H / 16, B / 16, ybuf, hbuf);
+        tile_cln(hbuf, H, vec, vec + 4, vec + 4 + H, part);
+        ring_store(a.ring_cur + (size_t)m * H * a.Rc, a.Rc, pos, hbuf, H, nvalid);
+    }
+}
+
+// ---- the same block boundary for chunks of at most one tile per stream, spread over `nsplit` workgroups per stream ------------------
+// One workgroup per tile leaves a single stream on ONE CU, which then streams 2*H*B weights by itself.  With at most ST_TC frames per
+// stream a block is two launches whose workgroups each own a slice of a GEMM's output rows (= of its weights):
+//   rows_a:  h[slice] = W1[slice] . y                                              -> hraw [M,H,F] (scratch behind the rings)
+//   rows_b:  n1 = cLN(PReLU(h)) (every workgroup, from the whole hraw column; slice 0 stores it in the ring) -> taps -> cLN(PReLU)
+//            -> y[slice] += W2[slice] . n2
+// Same device functions, same per-element FMA chains and sum orders as the stage kernel: bitwise the same values.
+struct RowsArgs {
+    const float* blk;       // packed block
+    float* y;               // [M,B,F]
+    float* hraw;            // [M,H,F]
+    float* ring;            // [M,H,R]
+    const unsigned* pos;
+    int R, d;
+    int B, H, P, F, nsplit;
+};
+
+__global__ __launch_bounds__(ST_NT) void stream_rows_a_kernel(RowsArgs a) {
+    extern __shared__ float lds[];
+    float* ybuf = lds;
+    float* hbuf = ybuf + (size_t)a.B * ST_TC;
+    const int m = blockIdx.x / a.nsplit, sp = blockIdx.x % a.nsplit, wave = threadIdx.x >> 6;
+    const int Rt = a.H / 16, per = (Rt + a.nsplit - 1) / a.nsplit, rt0 = min(sp * per, Rt), rt1 = min(rt0 + per, Rt);
+    tile_load(ybuf, a.y + (size_t)m * a.B * a.F, a.B, a.F, 0, a.F);
+    __syncthreads();
+    for (int rt = rt0 + wave; rt < rt1; rt += ST_NW) gemm_rows<EPI_STORE, 1>(reinterpret_cast<const float4*>(a.blk), rt, a.B / 16, ybuf, hbuf);
+    __syncthreads();
+    tile_store(hbuf + (size_t)rt0 * 16 * ST_TC, a.hraw + ((size_t)m * a.H + rt0 * 16) * a.F, (rt1 - rt0) * 16, a.F, 0, a.F);
+}
+
+__global__ __launch_bounds__(ST_NT) void stream_rows_b_kernel(RowsArgs a) {
+    extern __shared__ float lds[];
+    float* ybuf = lds;
+    float* hbuf = ybuf + (size_t)a.B * ST_TC;
+    float* part = hbuf + (size_t)a.H * ST_TC;
+    const int m = blockIdx.x / a.nsplit, sp = blockIdx.x % a.nsplit, wave = threadIdx.x >> 6;
+    const int B = a.B, H = a.H;
+    const int Rt = B / 16, per = (Rt + a.nsplit - 1) / a.nsplit, rt0 = min(sp * per, Rt), rt1 = min(rt0 + per, Rt);
+    const unsigned pos = a.pos[0];
+    const float* vec = a.blk + (size_t)2 * H * B;
+    float* yg = a.y + ((size_t)m * B + rt0 * 16) * a.F;
+    float* ring = a.ring + (size_t)m * H * a.R;
+    tile_load(hbuf, a.hraw + (size_t)m * H * a.F, H, a.F, 0, a.F);
+    tile_load(ybuf + (size_t)rt0 * 16 * ST_TC, yg, (rt1 - rt0) * 16, a.F, 0, a.F);
+    tile_cln(hbuf, H, vec, vec + 4, vec + 4 + H, part);
+    if (sp == 0) ring_store(ring, a.R, pos, hbuf, H, a.F);
+    tile_dw_any<true>(hbuf, ring, a.R, pos, a.d, H, a.P, vec + 4 + 4 * H, hbuf);
+    tile_cln(hbuf, H, vec + 1, vec + 4 + 2 * H, vec + 4 + 3 * H, part);
+    for (int rt = rt0 + wave; rt < rt1; rt += ST_NW)
+        gemm_rows<EPI_ADD, 1>(reinterpret_cast<const float4*>(a.blk + (size_t)H * B), rt, H / 16, hbuf, ybuf);
+    __syncthreads();
+    tile_store(ybuf + (size_t)rt0 * 16 * ST_TC, yg, (rt1 - rt0) * 16, a.F, 0, a.F);
+}
+
+__global__ void stream_advance_kernel(unsigned* pos, int frames) {
+    if (threadIdx.x == 0 && blockIdx.x == 0) pos[0] += (unsigned)frames;
+}
+
+// ---- front end: frames of the sample buffer -> relu(U x) = w -> cLN -> bottleneck 1x1 = y ---------------------------
+struct FrontArgs {
+    const float* x; int xld;        // [M][xld] samples; frame k = x[k*S .. k*S+L)
+    const float* Up; const float* g0; const float* b0; const float* Wbp;
+    float* w; float* y;             // [M,N,F], [M,B,F]
+    int N, L, B, F, tiles;
+};
+
+__global__ __launch_bounds__(ST_NT) void stream_front_kernel(FrontArgs a) {
+    extern __shared__ float lds[];
+    const int Lp = (a.L + 15) / 16 * 16, S = a.L / 2;
+    float* xin = lds;                               // [Lp][16]
+    float* wbuf = xin + (size_t)Lp * ST_TC;         // [N][16]
+    float* ybuf = wbuf + (size_t)a.N * ST_TC;       // [B][16]
+    float* part = ybuf + (size_t)a.B * ST_TC;
+    const int m = blockIdx.x / a.tiles, k0 = (blockIdx.x % a.tiles) * ST_TC;
+    const int nvalid = min(ST_TC, a.F - k0);
+    const float* xg = a.x + (size_t)m * a.xld;
+    for (int e = threadIdx.x; e < Lp * ST_TC; e += ST_NT) {
+        const int i = e / ST_TC, c = e & (ST_TC - 1);
+        const float v = xg[(size_t)(k0 + min(c, nvalid - 1)) * S + min(i, a.L - 1)];
+        xin[e] = (i < a.L && c < nvalid) ? v : 0.f;
+    }
+    __syncthreads();
+    tile_gemm<EPI_RELU>(a.Up, a.N / 16, Lp / 16, xin, wbuf);
+    __syncthreads();
+    tile_store(wbuf, a.w + (size_t)m * a.N * a.F, a.N, a.F, k0, nvalid);
+    tile_cln(wbuf, a.N, nullptr, a.g0, a.b0, part);
+    tile_gemm<EPI_STORE>(a.Wbp, a.B / 16, a.N / 16, wbuf, ybuf);
+    __syncthreads();
+    tile_store(ybuf, a.y + (size_t)m * a.B * a.F, a.B, a.F, k0, nvalid);
+}
+
+// ---- back end: mask 1x1 -> relu / softmax over speakers -> * w -> decoder basis -> frames [M,C,L,F] -----------------
+struct BackArgs {
+    const float* y; const float* w; const float* Wmp; const float* Vp;
+    float* fr;                      // [M,C,L,F]
+    int N, L, B, C, F, tiles, softmax;
+};
+
+__global__ __launch_bounds__(ST_NT) void stream_back_kernel(BackArgs a) {
+    extern __shared__ float lds[];
+    const int Lp = (a.L + 15) / 16 * 16, N = a.N, C = a.C;
+    float* ybuf = lds;                                  // [B][16]
+    float* sbuf = ybuf + (size_t)a.B * ST_TC;           // [C*N][16]
+    float* fbuf = sbuf + (size_t)C * N * ST_TC;         // [C][Lp][16]
+    const int m = blockIdx.x / a.tiles, k0 = (blockIdx.x % a.tiles) * ST_TC;
+    const int nvalid = min(ST_TC, a.F - k0);
+    tile_load(ybuf, a.y + (size_t)m * a.B * a.F, a.B, a.F, k0, nvalid);
+    __syncthreads();
+    tile_gemm<EPI_STORE>(a.Wmp, C * N / 16, a.B / 16, ybuf, sbuf);
+    __syncthreads();
+    const float* wg = a.w + (size_t)m * N * a.F;
+    for (int e = threadIdx.x; e < N * ST_TC; e += ST_NT) {
+        const int n = e / ST_TC, c = e & (ST_TC - 1);
+        const float wl = wg[(size_t)n * a.F + k0 + min(c, nvalid - 1)];
+        const float wv = c < nvalid ? wl : 0.f;
+        if (!a.softmax) {
+            for (int s = 0; s < C; ++s) sbuf[(size_t)s * N * ST_TC + e] = wv * fmaxf(sbuf[(size_t)s * N * ST_TC + e], 0.f);
+        } else {
+            float mx = -INFINITY, den = 0.f;
+            for (int s = 0; s < C; ++s) mx = fmaxf(mx, sbuf[(size_t)s * N * ST_TC + e]);
+            for (int s = 0; s < C; ++s) {
+                const float ex = expf(sbuf[(size_t)s * N * ST_TC + e] - mx);
+                sbuf[(size_t)s * N * ST_TC + e] = ex;
+                den += ex;
+            }
+            for (int s = 0; s < C; ++s) sbuf[(size_t)s * N * ST_TC + e] = wv * (sbuf[(size_t)s * N * ST_TC + e] / den);
+        }
+    }
+    __syncthreads();
+    for (int s = 0; s < C; ++s) tile_gemm<EPI_STORE>(a.Vp, Lp / 16, N / 16, sbuf + (size_t)s * N * ST_TC, fbuf + (size_t)s * Lp * ST_TC);
+    __syncthreads();
+    for (int s = 0; s < C; ++s)
+        tile_store(fbuf + (size_t)s * Lp * ST_TC, a.fr + ((size_t)m * C + s) * a.L * a.F, a.L, a.F, k0, nvalid);
+}
+
+// Overlap-add with the carried half frame (L = 2S: at most two frames meet in a sample, and a two-term sum commutes), then the carries:
+// tail = second half of the last frame; the first S samples of the sample buffer = its last S consumed ones.  One thread per (row, r).
+__global__ __launch_bounds__(256) void stream_ola_kernel(const float* __restrict__ fr, float* __restrict__ out, float* __restrict__ tail,
+                                                         float* __restrict__ x, int xld, int M, int MC, int L, int F) {
+    const int S = L / 2;
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e < MC * S) {
+        const int mc = e / S, r = e % S;
+        const float* f = fr + (size_t)mc * L * F;
+        float prev = tail[e];
+        float* o = out + (size_t)mc * F * S + r;
+        for (int k = 0; k < F; ++k) {
+            o[(size_t)k * S] = f[(size_t)r * F + k] + prev;
+            prev = f[(size_t)(r + S) * F + k];
+        }
+        tail[e] = prev;
+    }
+    if (e < M * S) {
+        const int m = e / S, i = e % S;
+        x[(size_t)m * xld + i] = x[(size_t)m * xld + (size_t)F * S + i];
+    }
+}
+
+bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+}  // namespace
+
+// =====================================================================================================================
+extern "C" {
+
+size_t ctn_stream_state_bytes(int M, int H, int P, const int* dilation, int nblocks, int max_frames) {
+    if (M < 1 || H < 1 || P < 1 || !dilation || nblocks < 1 || max_frames < 1) return 0;
+    size_t n = ST_HDR;
+    for (int j = 0; j < nblocks; ++j) {
+        if (dilation[j] < 1) return 0;
+        n += (size_t)M * H * (size_t)ring_len(P, dilation[j], max_frames);
+    }
+    n += (size_t)M * H * ST_TC;      // hraw: one tile of first-1x1 outputs per stream (row-split form)
+    return n * sizeof(float);
+}
+
+size_t ctn_stream_pack_gemm_bytes(int R, int Cn) {
+    if (R < 1 || Cn < 1) return 0;
+    return (size_t)c16(R) * c16(Cn) * 256 * sizeof(float);
+}
+
+int ctn_stream_pack_gemm(const float* W, int R, int Cn, void* packed, void* stream) {
+    CTN_REQUIRE(W && packed, "ctn_stream_pack_gemm: null pointer");
+    CTN_REQUIRE(R > 0 && Cn > 0, "ctn_stream_pack_gemm: bad sizes");
+    CTN_REQUIRE(aligned16(packed), "ctn_stream_pack_gemm: packed must be 16-byte aligned");
+    const long long n = (long long)c16(R) * c16(Cn) * 256;
+    hipLaunchKernelGGL(stream_pack_kernel, dim3((unsigned)ctn_cdivll(n, 256)), dim3(256), 0, (hipStream_t)stream, W, (float*)packed, R, Cn);
+    CTN_CHECK_LAUNCH("ctn_stream_pack_gemm");
+    return CTN_OK;
+}
+
+size_t ctn_stream_pack_bytes(int B, int H, int P, int nblocks) {
+    if (B < 1 || H < 1 || P < 1 || nblocks < 1 || B % 16 || H % 16) return 0;
+    return (size_t)nblocks * block_floats(B, H, P) * sizeof(float);
+}
+
+int ctn_stream_pack(const void* const* params, int nblocks, int B, int H, int P, void* packed, void* stream) {
+    CTN_REQUIRE(params && packed, "ctn_stream_pack: null pointer");
+    CTN_REQUIRE(nblocks > 0 && B > 0 && H > 0 && B % 16 == 0 && H % 16 == 0, "ctn_stream_pack: B and H must be positive multiples of 16");
+    CTN_REQUIRE(P >= 1 && P <= ST_MAXP, "ctn_stream_pack: kernel size must be 1..%d", ST_MAXP);
+    CTN_REQUIRE(aligned16(packed), "ctn_stream_pack: packed must be 16-byte aligned");
+    for (int i = 0; i < nblocks * 9; ++i) CTN_REQUIRE(params[i], "ctn_stream_pack: block %d parameter %d is null", i / 9, i % 9);
+    const size_t bf = block_floats(B, H, P);
+    for (int i = 0; i < nblocks; ++i) {
+        const float* const* p = (const float* const*)(params + (size_t)i * 9);
+        float* o = (float*)packed + (size_t)i * bf;
+        const unsigned g = (unsigned)ctn_cdivll((long long)H * B, 256);
+        hipLaunchKernelGGL(stream_pack_kernel, dim3(g), dim3(256), 0, (hipStream_t)stream, p[0], o, H, B);
+        hipLaunchKernelGGL(stream_pack_kernel, dim3(g), dim3(256), 0, (hipStream_t)stream, p[8], o + (size_t)H * B, B, H);
+        hipLaunchKernelGGL(stream_pack_vec_kernel, dim3((unsigned)ctn_cdiv(4 + 4 * H + H * P, 256)), dim3(256), 0, (hipStream_t)stream,
+                           p[1], p[2], p[3], p[4], p[5], p[6], p[7], o + (size_t)2 * H * B, H, P);
+    }
+    CTN_CHECK_LAUNCH("ctn_stream_pack");
+    return CTN_OK;
+}
+
+int ctn_stream_reset(void* state, size_t bytes, void* stream) {
+    CTN_REQUIRE(state, "ctn_stream_reset: null pointer");
+    CTN_REQUIRE(bytes >= ST_HDR * sizeof(float), "ctn_stream_reset: state smaller than its header");
+    if (hipMemsetAsync(state, 0, bytes, (hipStream_t)stream) != hipSuccess) {
+        ctn_set_error("ctn_stream_reset: %s", hipGetErrorString(hipGetLastError()));
+        return CTN_ERR_LAUNCH;
+    }
+    return CTN_OK;
+}
+
+int ctn_stream_tcn_cln(const void* packed, const int* dilation, int nblocks, float* y, void* state, int M, int B, int H, int P,
+                       int frames, int max_frames, void* stream) {
+    CTN_REQUIRE(packed && dilation && y && state, "ctn_stream_tcn_cln: null pointer");
+    CTN_REQUIRE(nblocks > 0 && M > 0, "ctn_stream_tcn_cln: bad sizes");
+    CTN_REQUIRE(B > 0 && H > 0 && B % 16 == 0 && H % 16 == 0, "ctn_stream_tcn_cln: B and H must be positive multiples of 16 (got %d, %d)", B, H);
+    CTN_REQUIRE(P >= 1 && P <= ST_MAXP, "ctn_stream_tcn_cln: kernel size must be 1..%d (got %d)", ST_MAXP, P);
+    CTN_REQUIRE(max_frames >= 1 && max_frames <= (1 << 20), "ctn_stream_tcn_cln: bad max_frames");
+    CTN_REQUIRE(frames >= 1 && frames <= max_frames, "ctn_stream_tcn_cln: frames must be 1..max_frames (got %d, max_frames %d)", frames, max_frames);
+    CTN_REQUIRE(aligned16(packed) && aligned16(state), "ctn_stream_tcn_cln: packed and state must be 16-byte aligned");
+    for (int j = 0; j < nblocks; ++j)
+        CTN_REQUIRE(dilation[j] >= 1 && dilation[j] <= (1 << 20), "ctn_stream_tcn_cln: bad dilation %d of block %d", dilation[j], j);
+    const size_t lds = ((size_t)(B + H) * ST_TC + ST_GRP * ST_TC) * sizeof(float);
+    CTN_REQUIRE(lds <= ST_MAX_LDS, "ctn_stream_tcn_cln: B + H = %d needs %zu bytes of LDS per tile (limit %zu)", B + H, lds, ST_MAX_LDS);
+    const int tiles = ctn_cdiv(frames, ST_TC);
+    const size_t bf = block_floats(B, H, P);
+    float* ring = (float*)state + ST_HDR;
+    // at most one tile per stream and room for >= 2 workgroups per stream in one round of the CUs: two row-split launches per block
+    const int cap = 256 / M;
+    if (frames <= ST_TC && cap >= 2) {
+        float* hraw = ring;
+        for (int j = 0; j < nblocks; ++j) hraw += (size_t)M * H * (size_t)ring_len(P, dilation[j], max_frames);
+        for (int j = 0; j < nblocks; ++j) {
+            RowsArgs a;
+            a.blk = (const float*)packed + (size_t)j * bf;
+            a.y = y; a.hraw = hraw; a.ring = ring; a.pos = (const unsigned*)state;
+            a.R = (int)ring_len(P, dilation[j], max_frames); a.d = dilation[j];
+            a.B = B; a.H = H; a.P = P; a.F = frames;
+            a.nsplit = std::max(1, std::min(std::min(H / 16, 16), cap));
+            hipLaunchKernelGGL(stream_rows_a_kernel, dim3((unsigned)(M * a.nsplit)), dim3(ST_NT), lds, (hipStream_t)stream, a);
+            a.nsplit = std::max(1, std::min(std::min(B / 16, 16), cap));
+            hipLaunchKernelGGL(stream_rows_b_kernel, dim3((unsigned)(M * a.nsplit)), dim3(ST_NT), lds, (hipStream_t)stream, a);
+            ring += (size_t)M * H * a.R;
+        }
+        hipLaunchKernelGGL(stream_advance_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (unsigned*)state, frames);
+        CTN_CHECK_LAUNCH("ctn_stream_tcn_cln");
+        return CTN_OK;
+    }
+    float* ring_prev = nullptr;
+    int Rp = 0;
+    for (int j = 0; j <= nblocks; ++j) {
+        StageArgs a;
+        a.prev = j >= 1 ? (const float*)packed + (size_t)(j - 1) * bf : nullptr;
+        a.cur = j < nblocks ? (const float*)packed + (size_t)j * bf : nullptr;
+        a.y = y;
+        a.ring_prev = ring_prev;
+        a.Rp = Rp;
+        a.dp = j >= 1 ? dilation[j - 1] : 0;
+        a.ring_cur = j < nblocks ? ring : nullptr;
+        a.Rc = j < nblocks ? (int)ring_len(P, dilation[j], max_frames) : 0;
+        a.pos = (const unsigned*)state;
+        a.B = B; a.H = H; a.P = P; a.F = frames; a.tiles = tiles;
+        hipLaunchKernelGGL(stream_stage_kernel, dim3((unsigned)(M * tiles)), dim3(ST_NT), lds, (hipStream_t)stream, a);
+        ring_prev = ring;
+        Rp = a.Rc;
+        ring += (size_t)M * H * a.Rc;
+    }
+    hipLaunchKernelGGL(stream_advance_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (unsigned*)state, frames);
+    CTN_CHECK_LAUNCH("ctn_stream_tcn_cln");
+    return CTN_OK;
+}
+
+int ctn_stream_front(const float* x, int xld, const void* Up, const float* g0, const float* b0, const void* Wbp, float* w, float* y,
+                     int M, int N, int L, int B, int frames, void* stream) {
+    CTN_REQUIRE(x && Up && g0 && b0 && Wbp && w && y, "ctn_stream_front: null pointer");
+    CTN_REQUIRE(M > 0 && frames > 0, "ctn_stream_front: bad sizes");
+    CTN_REQUIRE(N > 0 && B > 0 && N % 16 == 0 && B % 16 == 0, "ctn_stream_front: N and B must be positive multiples of 16 (got %d, %d)", N, B);
+    CTN_REQUIRE(L >= 4 && L % 4 == 0, "ctn_stream_front: L must be a multiple of 4 (got %d)", L);
+    CTN_REQUIRE((long long)xld >= (long long)(frames + 1) * (L / 2), "ctn_stream_front: sample buffer row shorter than frames + 1 hops");
+    CTN_REQUIRE(aligned16(Up) && aligned16(Wbp), "ctn_stream_front: packed weights must be 16-byte aligned");
+    const size_t lds = ((size_t)(c16(L) * 16 + N + B) * ST_TC + ST_GRP * ST_TC) * sizeof(float);
+    CTN_REQUIRE(lds <= ST_MAX_LDS, "ctn_stream_front: N + B = %d needs %zu bytes of LDS per tile (limit %zu)", N + B, lds, ST_MAX_LDS);
+    FrontArgs a;
+    a.x = x; a.xld = xld; a.Up = (const float*)Up; a.g0 = g0; a.b0 = b0; a.Wbp = (const float*)Wbp; a.w = w; a.y = y;
+    a.N = N; a.L = L; a.B = B; a.F = frames; a.tiles = ctn_cdiv(frames, ST_TC);
+    hipLaunchKernelGGL(stream_front_kernel, dim3((unsigned)(M * a.tiles)), dim3(ST_NT), lds, (hipStream_t)stream, a);
+    CTN_CHECK_LAUNCH("ctn_stream_front");
+    return CTN_OK;
+}
+
+int ctn_stream_back(const float* y, const float* w, const void* Wmp, const void* Vp, float* fr, float* out, float* ola_tail,
+                    float* x, int xld, int M, int N, int L, int B, int C, int frames, int softmax, void* stream) {
+    CTN_REQUIRE(y && w && Wmp && Vp && fr && out && ola_tail && x, "ctn_stream_back: null pointer");
+    CTN_REQUIRE(M > 0 && frames > 0 && C > 0, "ctn_stream_back: bad sizes");
+    CTN_REQUIRE(N > 0 && B > 0 && N % 16 == 0 && B % 16 == 0, "ctn_stream_back: N and B must be positive multiples of 16 (got %d, %d)", N, B);
+    CTN_REQUIRE(L >= 4 && L % 4 == 0, "ctn_stream_back: L must be a multiple of 4 (got %d)", L);
+    CTN_REQUIRE(softmax == 0 || softmax == 1, "ctn_stream_back: mask must be 0 (relu) or 1 (softmax)");
+    CTN_REQUIRE(C <= ST_MAXC, "ctn_stream_back: at most %d speakers", ST_MAXC);
+    CTN_REQUIRE((long long)xld >= (long long)(frames + 1) * (L / 2), "ctn_stream_back: sample buffer row shorter than frames + 1 hops");
+    CTN_REQUIRE(aligned16(Wmp) && aligned16(Vp), "ctn_stream_back: packed weights must be 16-byte aligned");
+    const size_t lds = ((size_t)B + (size_t)C * N + (size_t)C * c16(L) * 16) * ST_TC * sizeof(float);
+    CTN_REQUIRE(lds <= ST_MAX_LDS, "ctn_stream_back: B + C*N = %d needs %zu bytes of LDS per tile (limit %zu)", B + C * N, lds, ST_MAX_LDS);
+    BackArgs a;
+    a.y = y; a.w = w; a.Wmp = (const float*)Wmp; a.Vp = (const float*)Vp; a.fr = fr;
+    a.N = N; a.L = L; a.B = B; a.C = C; a.F = frames; a.tiles = ctn_cdiv(frames, ST_TC); a.softmax = softmax;
+    hipLaunchKernelGGL(stream_back_kernel, dim3((unsigned)(M * a.tiles)), dim3(ST_NT), lds, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(stream_ola_kernel, dim3((unsigned)ctn_cdiv(M * C * (L / 2), 256)), dim3(256), 0, (hipStream_t)stream,
+                       (const float*)fr, out, ola_tail, x, xld, M, M * C, L, frames);
+    CTN_CHECK_LAUNCH("ctn_stream_back");
+    return CTN_OK;
+}
+
+}  // extern "C"

@@ -503,6 +503,43 @@ int ctn_bss_project(const float* ref, const float* est, const long long* lengths
                     long long B, int C, long long E, long long T, double* sdr, double* sir, double* sar, double* energies,
                     void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- fused low-latency streaming inference of the causal cLN model (csrc/ctn_stream.hip) -----------------------------
+ * Chunk-wise TemporalConvNet.forward (src/conv_tasnet.py:176-186 with causal = True, norm_type = 'cLN') on UNPADDED chunks:
+ * activations here are [M, Ch, F] with F = the frames of this chunk (no 64-frame padding).  One workgroup carries a tile of 16
+ * frame columns of one stream through a whole block boundary in LDS; the depthwise history of block j is a ring buffer
+ * ring[j] [M,H,Rj], Rj = the power of two >= (P-1)*dilation[j] + max_frames, inside `state`, whose first word is the write
+ * position (device memory: a captured step replays without new arguments).  nblocks + 1 stage launches + one that advances the
+ * position (frames <= 16 and M <= 128: two launches per block whose workgroups split the GEMMs' output rows, bitwise the same
+ * values); a straight chain on `stream`.  Arithmetic is frame-local and in a fixed order (exact fp32 MFMA chains, two-pass
+ * per-frame cLN): a frame's values do not depend on the chunk it arrived in, its position in the chunk, or the other streams.
+ *   ctn_stream_state_bytes: host-only; 256 bytes of header + 4*M*H*(sum_j Rj + 16: one tile of scratch per stream).  A zeroed state
+ *     = the start of a stream.
+ *   ctn_stream_pack: the stack's parameters (`params` HOST [nblocks][9] device pointers in the order of ctn_tcn_cln_fwd)
+ *     -> `packed` (ctn_stream_pack_bytes): per block the two 1x1 weights in MFMA fragment order, then the small vectors.
+ *     Weights are constants at inference: pack once, again after they change.
+ *   ctn_stream_tcn_cln: y [M,B,frames] in place through the nblocks blocks, state advanced.  B, H multiples of 16 with
+ *     (B + H + 64) * 64 bytes of LDS <= 64 KiB, 1 <= P <= 8, any dilation >= 1, 1 <= frames <= max_frames (the value
+ *     the state was sized with).
+ *   ctn_stream_pack_gemm: one weight W [R,Cn] row-major -> fragment order (rows / contraction zero-filled to multiples of 16).
+ *   ctn_stream_front: frames k = x[m][k*S .. k*S+L), S = L/2, of the sample buffer x [M][xld] -> w = relu(U frame) [M,N,frames]
+ *     -> cLN(g0, b0) -> bottleneck 1x1 -> y [M,B,frames]   (src/conv_tasnet.py:96-99, :152-156).  Up, Wbp: packed [N,L], [B,N].
+ *   ctn_stream_back: mask 1x1 (Wmp packed [C*N,B]) -> relu (softmax = 0) or softmax over speakers (1) -> * w -> basis (Vp packed
+ *     [L,N]) -> fr [M,C,L,frames] (scratch) -> overlap-add with the carried half frame ola_tail [M,C,S] -> out [M,C,frames*S];
+ *     then the carries: ola_tail = second half of the last frame, x[m][0..S) = x[m][frames*S .. frames*S+S)
+ *     (src/conv_tasnet.py:118-132, :199-211).  N, B multiples of 16, L a multiple of 4, C <= 8. */
+size_t ctn_stream_state_bytes(int M, int H, int P, const int* dilation, int nblocks, int max_frames);
+size_t ctn_stream_pack_bytes(int B, int H, int P, int nblocks);
+int ctn_stream_pack(const void* const* params, int nblocks, int B, int H, int P, void* packed, void* stream);
+int ctn_stream_tcn_cln(const void* packed, const int* dilation, int nblocks, float* y, void* state, int M, int B, int H, int P,
+                       int frames, int max_frames, void* stream);
+int ctn_stream_reset(void* state, size_t bytes, void* stream);
+size_t ctn_stream_pack_gemm_bytes(int R, int Cn);
+int ctn_stream_pack_gemm(const float* W, int R, int Cn, void* packed, void* stream);
+int ctn_stream_front(const float* x, int xld, const void* Up, const float* g0, const float* b0, const void* Wbp, float* w, float* y,
+                     int M, int N, int L, int B, int frames, void* stream);
+int ctn_stream_back(const float* y, const float* w, const void* Wmp, const void* Vp, float* fr, float* out, float* ola_tail,
+                    float* x, int xld, int M, int N, int L, int B, int C, int frames, int softmax, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
