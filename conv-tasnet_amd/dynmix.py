@@ -1,0 +1,241 @@
+"""On-device dynamic mixing: the single-speaker corpus lives in device memory, every training minibatch is drawn and built
+there (csrc/ctn_dynmix.hip: one plan launch + the gather per step, no host work, no host synchronisation).
+
+    corpus = DeviceCorpus.from_manifest("tr_sources.json", 8000, "cuda:0")      # [[wav_path, n_samples, speaker], ...]
+    loader = DynamicMixLoader(corpus, batch_size=8, segment_len=32000, steps_per_epoch=2500, seed=0)
+    for mixture, lengths, sources in loader: ...                                 # the AudioDataLoader contract, on the device
+
+What a mixture is (include/ctn_hip.h has the contract, the tests restate it in numpy): C distinct speakers, one
+eligible utterance of each, a uniform start, levels +q / -q hundredths of a dB with q in [1, 250) as the reference's list
+generator draws them (tools/create_txt_file_like_wsj0.py:21-22), sources at unit RMS times 10^(q/2000), summed, everything
+rescaled to a peak of 0.9 (tools/matlab-code/create_wav_2speakers.m:111-112).  A minibatch is a pure function of
+(seed, rank, epoch, step): a resumed run sees the minibatches of an uninterrupted one.
+
+Differences from the MATLAB tool, on purpose: the level is the plain RMS of the whole utterance (not ITU-T P.56 active
+level), the peak rescale is per drawn segment (not per whole utterance), and files must already be at `sample_rate`.
+There is no CPU fallback: like the rest of the product path the loader needs the GPU.
+"""
+import json
+
+import numpy as np
+import torch
+
+from . import data as _data
+from ._lib import lib
+
+GATHER_MODE = 0     # ctn_dynmix_gather: 0 = chunked, two launches; 1 = one workgroup per mixture (measured)
+
+
+def level_table():
+    """w[q + 249] = 10^(q / 2000), q = -249 .. 249: float32 rounded from float64 on the host."""
+    return np.array([10.0 ** (q / 2000.0) for q in range(-249, 250)], dtype=np.float64).astype(np.float32)
+
+
+def inverse_rms(meansq):
+    """1 / sqrt(meansq) in float64, rounded to float32; 0 for silent utterances (never eligible)."""
+    meansq = np.asarray(meansq, dtype=np.float64)
+    out = np.zeros(meansq.shape, dtype=np.float64)
+    live = meansq > 0
+    out[live] = 1.0 / np.sqrt(meansq[live])
+    return out.astype(np.float32)
+
+
+def build_tables(lens, meansq, speakers, segment_len, num_speakers=2):
+    """The sampler's tables for one segment length (pure host function).
+
+    Eligible: lens[u] >= segment_len and meansq[u] > 0.  Speakers (sorted by label) without an eligible utterance are
+    dropped; fewer than `num_speakers` left is a ValueError.  -> dict(spk_ptr [S+1] int32, utt_ids int32, speakers list,
+    lens int64, inv_rms float32, w float32)."""
+    lens = np.asarray(lens, dtype=np.int64)
+    meansq = np.asarray(meansq, dtype=np.float64)
+    if not (len(lens) == len(meansq) == len(speakers)):
+        raise ValueError("lens, meansq and speakers differ in length")
+    if segment_len <= 0:
+        raise ValueError("segment_len must be positive, got %d" % segment_len)
+    if len(lens) and int(lens.max()) - segment_len + 1 >= 1 << 32:
+        raise ValueError("an utterance of %d samples is too long for a 32-bit start draw" % int(lens.max()))
+    by_spk = {}
+    for u, s in enumerate(speakers):
+        if lens[u] >= segment_len and meansq[u] > 0:
+            by_spk.setdefault(str(s), []).append(u)
+    names = sorted(by_spk)
+    if len(names) < num_speakers:
+        raise ValueError("%d speaker(s) with an utterance of at least %d samples that is not silent; mixtures of %d need "
+                         "at least as many" % (len(names), segment_len, num_speakers))
+    spk_ptr, utt_ids = [0], []
+    for s in names:
+        utt_ids.extend(by_spk[s])
+        spk_ptr.append(len(utt_ids))
+    return dict(spk_ptr=np.asarray(spk_ptr, dtype=np.int32), utt_ids=np.asarray(utt_ids, dtype=np.int32), speakers=names,
+                lens=lens, inv_rms=inverse_rms(meansq), w=level_table())
+
+
+def _ptr(t):
+    return t.data_ptr() if t is not None else 0
+
+
+class DeviceCorpus:
+    """U single-speaker utterances back to back in one flat float32 device buffer, with their levels."""
+
+    def __init__(self, arrays, speakers, device):
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise ValueError("DeviceCorpus lives on the GPU: got device %s" % device)
+        if len(arrays) == 0 or len(arrays) != len(speakers):
+            raise ValueError("%d utterances with %d speaker labels" % (len(arrays), len(speakers)))
+        arrays = [np.ascontiguousarray(a, dtype=np.float32).reshape(-1) for a in arrays]
+        lens = np.array([a.shape[0] for a in arrays], dtype=np.int64)
+        if int(lens.min()) < 1:
+            raise ValueError("empty utterance in the corpus")
+        offsets = np.concatenate(([0], np.cumsum(lens)[:-1])).astype(np.int64)
+        self.device = device
+        self.speakers = [str(s) for s in speakers]
+        self.lens_host, self.offsets_host = lens, offsets
+        self.corpus = torch.from_numpy(np.concatenate(arrays)).to(device)
+        self.offsets = torch.from_numpy(offsets).to(device)
+        self.lens = torch.from_numpy(lens).to(device)
+        msq = torch.empty(len(arrays), dtype=torch.float64, device=device)
+        lib.call("ctn_dynmix_levels", _ptr(self.corpus), self.corpus.numel(), _ptr(self.offsets), _ptr(self.lens), len(arrays),
+                 _ptr(msq), torch.cuda.current_stream(device).cuda_stream)
+        self._meansq = msq.cpu().numpy()
+        self.inv_rms = torch.from_numpy(inverse_rms(self._meansq)).to(device)
+        self.w = torch.from_numpy(level_table()).to(device)
+        self._tables = {}
+
+    @classmethod
+    def from_arrays(cls, arrays, speakers, device):
+        return cls(arrays, speakers, device)
+
+    @classmethod
+    def from_manifest(cls, json_path, sample_rate, device, reader=_data.read_wav):
+        """json list of (wav_path, n_samples, speaker): every file is read once and uploaded."""
+        with open(json_path, "r") as f:
+            infos = json.load(f)
+        arrays = []
+        for path, n, _ in infos:
+            x = reader(path, sample_rate)
+            if x.shape[0] != int(n):
+                raise ValueError("%s has %d samples, the manifest says %d" % (path, x.shape[0], int(n)))
+            arrays.append(x)
+        return cls(arrays, [i[2] for i in infos], device)
+
+    num_utterances = property(lambda self: len(self.lens_host))
+    num_speakers = property(lambda self: len(set(self.speakers)))
+    num_samples = property(lambda self: int(self.corpus.numel()))
+    meansq = property(lambda self: self._meansq)
+
+    def device_bytes(self):
+        """4 * num_samples for the audio plus the per-utterance tables (offsets, lens, inv_rms) and the level table."""
+        return sum(t.numel() * t.element_size() for t in (self.corpus, self.offsets, self.lens, self.inv_rms, self.w))
+
+    def tables(self, segment_len, num_speakers):
+        """Sampler tables for one segment length: (host dict of build_tables, spk_ptr and utt_ids on the device)."""
+        key = (int(segment_len), int(num_speakers))
+        if key not in self._tables:
+            host = build_tables(self.lens_host, self._meansq, self.speakers, int(segment_len), int(num_speakers))
+            self._tables[key] = (host, torch.from_numpy(host["spk_ptr"]).to(self.device),
+                                 torch.from_numpy(host["utt_ids"]).to(self.device))
+        return self._tables[key]
+
+
+class DynamicMixLoader:
+    """Yields `steps_per_epoch` minibatches (mixture [B,T] f32, lengths [B] i64 = T, sources [B,C,T] f32) per epoch, all
+    on the corpus' device: the AudioDataLoader contract the Solver consumes.
+
+    Iterating rewinds the step word and yields steps 0 .. steps_per_epoch - 1 of the current epoch into fresh tensors
+    (`lengths` is one shared constant tensor).  `dataset.set_epoch(epoch)` (the Solver calls it) selects the epoch;
+    with reshuffle=False the epoch stays 0: the same minibatches every time, a fixed validation set without mixture files.
+    Every rank draws its own stream (`rank` enters the Philox key, the world size does not) and runs the same number of steps.
+    gather_mode: the form of ctn_dynmix_gather (None: GATHER_MODE); both give the same bits."""
+
+    def __init__(self, corpus, batch_size, segment_len, num_speakers=2, steps_per_epoch=1000, seed=0, rank=None,
+                 reshuffle=True, gather_mode=None):
+        if rank is None:
+            from . import parallel
+            rank = torch.distributed.get_rank() if parallel.world_size() > 1 else parallel.env_world()[1]
+        seed, rank = int(seed), int(rank)
+        if not 0 <= seed < 1 << 48:
+            raise ValueError("seed must be in [0, 2^48), got %d" % seed)
+        if not 0 <= rank < 1 << 16:
+            raise ValueError("rank must be in [0, 2^16), got %d" % rank)
+        if not 2 <= int(num_speakers) <= 4:
+            raise ValueError("mixtures of 2..4 speakers, got %d" % num_speakers)
+        if batch_size < 1 or steps_per_epoch < 1:
+            raise ValueError("batch_size and steps_per_epoch must be positive")
+        self.corpus, self.B, self.T, self.C = corpus, int(batch_size), int(segment_len), int(num_speakers)
+        self.steps_per_epoch, self.seed, self.rank, self.reshuffle = int(steps_per_epoch), seed, rank, bool(reshuffle)
+        self.gather_mode = GATHER_MODE if gather_mode is None else int(gather_mode)
+        self.epoch = 0
+        self.tables, self._spk_ptr, self._utt_ids = corpus.tables(self.T, self.C)
+        dev = corpus.device
+        self.device = dev
+        self._step = torch.zeros(1, dtype=torch.int32, device=dev)                  # the step word
+        self._plan_utt = torch.zeros(self.B, self.C, dtype=torch.int32, device=dev)
+        self._plan_start = torch.zeros(self.B, self.C, dtype=torch.int64, device=dev)
+        self._plan_q = torch.zeros(self.B, self.C, dtype=torch.int32, device=dev)
+        self._gain = torch.zeros(self.B, self.C, dtype=torch.float32, device=dev)
+        self._peak = torch.zeros(self.B, dtype=torch.float32, device=dev)
+        self._ws = torch.zeros(max(1, lib.ctn_dynmix_gather_workspace(self.B, self.T)), dtype=torch.uint8, device=dev)
+        self._lengths = torch.full((self.B,), self.T, dtype=torch.int64, device=dev)
+        self.dataset = self                                                          # Solver: loader.dataset.set_epoch(epoch)
+
+    def __len__(self):
+        return self.steps_per_epoch
+
+    def set_epoch(self, epoch):
+        """Select the epoch and rewind the step word (reshuffle=False: the epoch stays 0)."""
+        self.epoch = int(epoch) if self.reshuffle else 0
+        self._step.zero_()
+
+    def fill(self, mixture, sources, lengths=None):
+        """The next minibatch into caller buffers (float32, contiguous, on the corpus' device): the plan launch and the gather on
+        the current stream, no allocation, no host synchronisation; the step word advances on the device."""
+        B, C, T = self.B, self.C, self.T
+        for t, shape, name in ((mixture, (B, T), "mixture"), (sources, (B, C, T), "sources")):
+            if tuple(t.shape) != shape or t.dtype != torch.float32 or not t.is_contiguous() or t.device != self.device:
+                raise ValueError("%s must be a contiguous float32 %s tensor on %s" % (name, shape, self.device))
+        c = self.corpus
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        lib.call("ctn_dynmix_plan", _ptr(self._spk_ptr), _ptr(self._utt_ids), len(self.tables["spk_ptr"]) - 1, _ptr(c.lens),
+                 _ptr(c.inv_rms), _ptr(c.w), self.seed, self.epoch, self.rank, _ptr(self._step), B, C, T,
+                 _ptr(self._plan_utt), _ptr(self._plan_start), _ptr(self._plan_q), _ptr(self._gain), stream)
+        lib.call("ctn_dynmix_gather", _ptr(c.corpus), _ptr(c.offsets), _ptr(c.lens), c.num_utterances, _ptr(self._plan_utt),
+                 _ptr(self._plan_start), _ptr(self._gain), B, C, T, _ptr(mixture), _ptr(sources), _ptr(self._peak),
+                 _ptr(self._ws), self._ws.numel(), self.gather_mode, stream)
+        if lengths is not None:
+            lengths.copy_(self._lengths)
+
+    def last_plan(self):
+        """Copies of the last minibatch's plan: (plan_utt [B,C] i32, plan_start [B,C] i64, plan_q [B,C] i32, gain [B,C] f32)."""
+        return self._plan_utt.clone(), self._plan_start.clone(), self._plan_q.clone(), self._gain.clone()
+
+    def last_peak(self):
+        """peak [B] of the last minibatch before the rescale to 0.9."""
+        return self._peak.clone()
+
+    def __iter__(self):
+        self._step.zero_()
+        for _ in range(self.steps_per_epoch):
+            mixture = torch.empty(self.B, self.T, dtype=torch.float32, device=self.device)
+            sources = torch.empty(self.B, self.C, self.T, dtype=torch.float32, device=self.device)
+            self.fill(mixture, sources)
+            yield mixture, self._lengths, sources
+
+
+def gather(corpus, plan_utt, plan_start, gain, segment_len, mode=None):
+    """The minibatch of a caller-written plan: plan_utt [B,C] int32, plan_start [B,C] int64, gain [B,C] float32 on the
+    corpus' device -> (mixture [B,T], sources [B,C,T], peak [B])."""
+    dev = corpus.device
+    B, C = plan_utt.shape
+    T = int(segment_len)
+    plan_utt = plan_utt.to(device=dev, dtype=torch.int32).contiguous()
+    plan_start = plan_start.to(device=dev, dtype=torch.int64).contiguous()
+    gain = gain.to(device=dev, dtype=torch.float32).contiguous()
+    mixture = torch.empty(B, T, dtype=torch.float32, device=dev)
+    sources = torch.empty(B, C, T, dtype=torch.float32, device=dev)
+    peak = torch.empty(B, dtype=torch.float32, device=dev)
+    ws = torch.empty(max(1, lib.ctn_dynmix_gather_workspace(B, T)), dtype=torch.uint8, device=dev)
+    lib.call("ctn_dynmix_gather", _ptr(corpus.corpus), _ptr(corpus.offsets), _ptr(corpus.lens), corpus.num_utterances,
+             _ptr(plan_utt), _ptr(plan_start), _ptr(gain), B, C, T, _ptr(mixture), _ptr(sources), _ptr(peak), _ptr(ws),
+             ws.numel(), GATHER_MODE if mode is None else int(mode), torch.cuda.current_stream(dev).cuda_stream)
+    return mixture, sources, peak

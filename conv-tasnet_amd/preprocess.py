@@ -5,6 +5,10 @@ src/data.py:52-60 and by conv_tasnet_amd.data.AudioDataset), so manifests writte
 interchangeable.  The sample count comes from the wav header instead of decoding the audio with librosa; files
 must already be at `sample_rate` (resampling is outside the hot-path scope, and a mismatch is an error rather
 than a silent length change).
+
+preprocess_sources() writes the manifest of a single-speaker corpus for dynmix.DeviceCorpus.from_manifest:
+[[abs_wav_path, n_samples, speaker], ...], speaker = the name of the file's parent directory (the wsj0 layout
+si_tr_s/01t/01to030v.wav the reference's recipe assumes).
 """
 import argparse
 import json
@@ -42,6 +46,22 @@ def preprocess(data_dir, json_dir, sample_rate=8000, splits=("tr", "cv", "tt"), 
     for split in splits:
         for spk in ["mix"] + ["s%d" % (c + 1) for c in range(num_speakers)]:
             preprocess_one_dir(os.path.join(data_dir, split, spk), os.path.join(json_dir, split), spk, sample_rate)
+
+
+def preprocess_sources(in_dir, out_json, sample_rate=8000):
+    """Every .wav below in_dir (sorted walk) -> out_json, a list of (abs path, n_samples, parent directory name)."""
+    in_dir = os.path.abspath(in_dir)
+    infos = []
+    for root, dirs, files in os.walk(in_dir):
+        dirs.sort()
+        for name in sorted(files):
+            if name.endswith(".wav"):
+                p = os.path.join(root, name)
+                infos.append((p, wav_num_samples(p, sample_rate), os.path.basename(root)))
+    os.makedirs(os.path.dirname(os.path.abspath(out_json)), exist_ok=True)
+    with open(out_json, "w") as f:
+        json.dump(infos, f, indent=4)
+    return infos
 
 
 if __name__ == "__main__":

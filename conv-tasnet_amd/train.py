@@ -76,7 +76,7 @@ def train(data, epochs, model_path, save_folder="exp/models", continue_from="", 
     return solver
 
 
-def main():
+def build_parser():
     ap = argparse.ArgumentParser(description="Conv-TasNet training on MI355X (synthetic data demo)")
     ap.add_argument("--epochs", type=int, default=1)
     ap.add_argument("--batches", type=int, default=10)
@@ -89,17 +89,40 @@ def main():
     ap.add_argument("--lr", type=float, default=1e-3)
     ap.add_argument("--momentum", type=float, default=0.0, help="SGD momentum")
     ap.add_argument("--l2", type=float, default=0.0, help="weight decay (coupled L2) of either optimiser")
-    a = ap.parse_args()
-    world, rank, _ = parallel.init_distributed()
+    ap.add_argument("--dynamic-mix", default=None, metavar="TR_SOURCES_JSON", help="train on mixtures drawn on the device "
+                    "every step from this single-speaker manifest (preprocess.preprocess_sources); replaces the training loader")
+    ap.add_argument("--steps-per-epoch", type=int, default=1000, help="minibatches per epoch of the dynamic-mixing loaders")
+    ap.add_argument("--dynamic-mix-cv", default=None, metavar="CV_SOURCES_JSON", help="validate on a fixed set of mixtures drawn "
+                    "from this second manifest (the same minibatches every epoch); default: --data-dir's cv/")
+    ap.add_argument("--cv-steps", type=int, default=100, help="minibatches of the --dynamic-mix-cv validation set")
+    ap.add_argument("--seed", type=int, default=0, help="seed of the dynamic-mixing draw")
+    return ap
+
+
+def main():
+    import os
+    a = build_parser().parse_args()
+    world, rank, device = parallel.init_distributed()
+    tr = cv = None
+    if a.dynamic_mix or a.dynamic_mix_cv:
+        from .dynmix import DeviceCorpus, DynamicMixLoader
+        if a.dynamic_mix:
+            tr = DynamicMixLoader(DeviceCorpus.from_manifest(a.dynamic_mix, 8000, device), a.batch_size, 32000,
+                                  steps_per_epoch=a.steps_per_epoch, seed=a.seed, rank=rank)
+        if a.dynamic_mix_cv:
+            cv = DynamicMixLoader(DeviceCorpus.from_manifest(a.dynamic_mix_cv, 8000, device), a.batch_size, 32000,
+                                  steps_per_epoch=a.cv_steps, seed=a.seed + 1, rank=rank, reshuffle=False)
     if a.data_dir:
-        import os
         from .data import AudioDataLoader, AudioDataset
-        tr = AudioDataLoader(AudioDataset(os.path.join(a.data_dir, "tr"), a.batch_size, segment=4.0, rank=rank, world=world),
-                             shuffle=True, num_workers=4)
-        cv = AudioDataLoader(AudioDataset(os.path.join(a.data_dir, "cv"), 1, segment=-1, cv_maxlen=6, rank=rank, world=world),
-                             num_workers=0)
-    else:
+        if tr is None:
+            tr = AudioDataLoader(AudioDataset(os.path.join(a.data_dir, "tr"), a.batch_size, segment=4.0, rank=rank, world=world),
+                                 shuffle=True, num_workers=4)
+        if cv is None:
+            cv = AudioDataLoader(AudioDataset(os.path.join(a.data_dir, "cv"), 1, segment=-1, cv_maxlen=6, rank=rank, world=world),
+                                 num_workers=0)
+    if tr is None:
         tr = SyntheticLoader(a.batches, a.batch_size, rank=rank, world=world)
+    if cv is None:
         cv = SyntheticLoader(1, a.batch_size, first_utt=10 ** 6, rank=rank, world=world)
     train({'tr_loader': tr, 'cv_loader': cv}, a.epochs, a.model_path, save_folder=a.save_folder, lr=a.lr,
           optimizer_type=a.optimizer, momentum=a.momentum, l2=a.l2)

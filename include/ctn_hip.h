@@ -540,6 +540,55 @@ int ctn_stream_front(const float* x, int xld, const void* Up, const float* g0, c
 int ctn_stream_back(const float* y, const float* w, const void* Wmp, const void* Vp, float* fr, float* out, float* ola_tail,
                     float* x, int xld, int M, int N, int L, int B, int C, int frames, int softmax, void* stream);
 
+/* ---- on-device dynamic mixing: a resident single-speaker corpus and the minibatch sampler (csrc/ctn_dynmix.hip) ---------
+ * replaces the offline mixture set of the reference's recipe: the list tools/create_txt_file_like_wsj0.py draws (two
+ * speakers, snr_1 = randrange(1, 250) / 100 dB, snr_2 = -snr_1) and tools/matlab-code/create_wav_2speakers.m builds
+ * (sources at unit level, weighted by 10^(snr/20), added, everything rescaled to a peak of 0.9), with a fresh draw every step.
+ * corpus: one flat fp32 buffer of num_samples samples holding U utterances back to back; offsets [U], lens [U] int64.
+ *   ctn_dynmix_levels: meansq [U] fp64 = the mean of the squares of every utterance, one workgroup per utterance: thread t
+ *     of 256 sums samples t, t + 256, ... in fp64, then a fixed-order block sum.  The partition depends on the utterance's own
+ *     length only, so a value does not depend on the neighbours or on U.  An entry outside [0, num_samples) gives -1.
+ *   ctn_dynmix_plan: the plan of one minibatch, then *step += 1 ON THE DEVICE (the host passes the same arguments every
+ *     step: a captured call replays).  plan_utt [B,C] int32, plan_start [B,C] int64, plan_q [B,C] int32, gain [B,C] fp32.
+ *     Tables: spk_ptr [S+1] int32 (CSR over speakers), utt_ids [spk_ptr[S]] int32: the ELIGIBLE utterances of every speaker
+ *     (lens[u] >= seg_len and meansq[u] > 0; every speaker has at least one), inv_rms [U] fp32 = 1 / sqrt(meansq[u]),
+ *     w [499] fp32 = 10^(q / 2000) for q = -249 .. 249, both rounded from fp64 on the host: no pow or sqrt on the device.
+ *     The draw is a pure function of (seed, rank, epoch, step, b) through Philox4x32-10 (multipliers 0xD2511F53, 0xCD9E8D57,
+ *     key increments 0x9E3779B9, 0xBB67AE85):
+ *         counter = (c, b, step, epoch)      key = (seed bits 0..31, seed bits 32..47 | rank << 16)
+ *     one block of four words per source c of mixture b; 0 <= seed < 2^48, 0 <= rank < 2^16, epoch >= 0.  An integer in [0, n)
+ *     from a word r is (uint64(r) * n) >> 32 (bias below n / 2^32).  Of the block of source c:
+ *         word 0  speaker: s in [0, S - c), then stepped over the c speakers already taken, in ascending order (C distinct
+ *                 speakers, uniform without replacement, no rejection loop)
+ *         word 1  utterance: uniform among the speaker's eligible ones
+ *         word 2  start: uniform in [0, lens[u] - seg_len]
+ *         word 3  level q_c in hundredths of a dB: c = 0: 1 + [0, 249); c = 1: q_1 = -q_0 (word unused); c >= 2: v in [0, 498),
+ *                 q_c = 1 + v for v < 249, -(1 + v - 249) otherwise (uniform magnitude in [1, 250), random sign)
+ *     gain[b,c] = w[q_c + 249] * inv_rms[u]: one fp32 multiply.  2 <= C <= 4, S >= C.
+ *   ctn_dynmix_gather: the minibatch of a plan (the sampler's or the caller's); mixture [B,T], sources [B,C,T] fp32 (16-byte
+ *     aligned), peak [B], T = seg_len.  Every operation is one fp32 rounding, in this order:
+ *         s_c[t] = gain[b,c] * corpus[offsets[u_c] + start_c + t]
+ *         mix[t] = ((s_0[t] + s_1[t]) + s_2[t]) + ...
+ *         a      = max_t max(|mix[t]|, |s_0[t]|, ..., |s_{C-1}[t]|)          (create_wav_2speakers.m:111)
+ *         scale  = a > 0 ? 0.9f / a : 1.0f                                   (:112, IEEE division)
+ *         mixture[b,t] = scale * mix[t];  sources[b,c,t] = scale * s_c[t];  peak[b] = a
+ *     max is order-free, so the outputs are a bitwise function of the plan and the corpus, whatever the launch geometry.
+ *     mode 0: two launches of (ceil(T / 1024), B) workgroups (per-workgroup maxima into `workspace`,
+ *     ctn_dynmix_gather_workspace() bytes; then the scaled samples); mode 1: one launch of B workgroups that read their
+ *     segments twice (no workspace).  Same values.  A plan entry outside its utterance (u outside [0, U), start < 0 or
+ *     start + T > lens[u]) is never read: that source counts as silence and peak[b] = -1.
+ * Deliberate differences from create_wav_2speakers.m: the level is the plain RMS of the whole utterance, not the ITU-T P.56
+ * active level (activlev.m); the peak rescale is per drawn segment, not per whole utterance; no resampling. */
+int ctn_dynmix_levels(const float* corpus, long long num_samples, const long long* offsets, const long long* lens, long long U,
+                      double* meansq, void* stream);
+int ctn_dynmix_plan(const int* spk_ptr, const int* utt_ids, int S, const long long* lens, const float* inv_rms, const float* w,
+                    long long seed, int epoch, int rank, unsigned* step, int B, int C, int seg_len, int* plan_utt,
+                    long long* plan_start, int* plan_q, float* gain, void* stream);
+size_t ctn_dynmix_gather_workspace(int B, int T);
+int ctn_dynmix_gather(const float* corpus, const long long* offsets, const long long* lens, long long U, const int* plan_utt,
+                      const long long* plan_start, const float* gain, int B, int C, int T, float* mixture, float* sources,
+                      float* peak, void* workspace, size_t workspace_bytes, int mode, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
