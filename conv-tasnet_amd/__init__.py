@@ -10,5 +10,6 @@ from .utils import overlap_and_add, remove_pad  # noqa: F401
 from .ops import gemm_arith, gemm_arithmetic, set_gemm_arith  # noqa: F401
 from .streaming import StreamingSeparator, FusedStreamingSeparator  # noqa: F401
 from .dynmix import DeviceCorpus, DynamicMixLoader  # noqa: F401
+from . import resample  # noqa: F401
 
 __version__ = "0.1.0"

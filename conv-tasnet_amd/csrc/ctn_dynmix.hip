@@ -107,6 +107,62 @@ __global__ __launch_bounds__(DM_NT) void dynmix_plan_kernel(const int* __restric
     if (threadIdx.x == 0) *step_word = step + 1u;
 }
 
+// The plan with speed perturbation: the draws of dynmix_plan_kernel from the same Philox block, plus one more block per source,
+// counter (c + 256, b, step, epoch), whose word 0 picks the speed percent.  The start is drawn over the
+// need = ceil(seg_len * pct / 100) input samples the resampled segment spans.
+__global__ __launch_bounds__(DM_NT) void dynmix_plan_speed_kernel(const int* __restrict__ spk_ptr, const int* __restrict__ utt_ids, int S,
+                                                                  const long long* __restrict__ lens, const float* __restrict__ inv_rms,
+                                                                  const float* __restrict__ w, const int* __restrict__ pct_tab, int npct,
+                                                                  unsigned k0, unsigned k1, unsigned epoch, unsigned* step_word, int B, int C,
+                                                                  int seg_len, int* __restrict__ plan_utt, long long* __restrict__ plan_start,
+                                                                  int* __restrict__ plan_q, float* __restrict__ gain, int* __restrict__ plan_pct) {
+    const unsigned step = *step_word;
+    for (int b = threadIdx.x; b < B; b += DM_NT) {
+        int taken[4];
+        int q0 = 0;
+        for (int c = 0; c < C; ++c) {
+            const Philox4 r = philox4x32_10((unsigned)c, (unsigned)b, step, epoch, k0, k1);
+            const Philox4 rs = philox4x32_10((unsigned)c + 256u, (unsigned)b, step, epoch, k0, k1);
+            const int pct = pct_tab[below(rs.w[0], (unsigned long long)npct)];
+            const long long need = ((long long)seg_len * pct + 99) / 100;
+            int s = (int)below(r.w[0], (unsigned long long)(S - c));
+            for (int i = 0; i < c; ++i)
+                if (s >= taken[i]) ++s;
+            int pos = c;                              // keep `taken` ascending
+            while (pos > 0 && taken[pos - 1] > s) { taken[pos] = taken[pos - 1]; --pos; }
+            taken[pos] = s;
+            const int first = spk_ptr[s], count = spk_ptr[s + 1] - first;
+            const int o = b * C + c;
+            const int u = count > 0 ? utt_ids[first + (int)below(r.w[1], (unsigned long long)count)] : -1;
+            if (u < 0 || need < 1 || lens[u] < need) { // tables that break their contract: an entry the segments kernel flags
+                plan_utt[o] = -1;
+                plan_start[o] = 0;
+                plan_q[o] = 0;
+                gain[o] = 0.0f;
+                plan_pct[o] = 100;
+                continue;
+            }
+            const long long start = (long long)below(r.w[2], (unsigned long long)(lens[u] - need + 1));
+            int q;
+            if (c == 0) {
+                q = q0 = 1 + (int)below(r.w[3], 249ull);
+            } else if (c == 1) {
+                q = -q0;
+            } else {
+                const int v = (int)below(r.w[3], 498ull);
+                q = v < 249 ? 1 + v : -(1 + (v - 249));
+            }
+            plan_utt[o] = u;
+            plan_start[o] = start;
+            plan_q[o] = q;
+            gain[o] = __fmul_rn(w[q + 249], inv_rms[u]);
+            plan_pct[o] = pct;
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) *step_word = step + 1u;
+}
+
 // ---- gather ------------------------------------------------------------------------------------------------------------
 template <int C>
 struct Rows {
@@ -293,6 +349,27 @@ int ctn_dynmix_plan(const int* spk_ptr, const int* utt_ids, int S, const long lo
     dynmix_plan_kernel<<<dim3(1), dim3(DM_NT), 0, (hipStream_t)stream>>>(spk_ptr, utt_ids, S, lens, inv_rms, w, k0, k1, (unsigned)epoch, step,
                                                                          B, C, seg_len, plan_utt, plan_start, plan_q, gain);
     CTN_CHECK_LAUNCH("ctn_dynmix_plan");
+    return CTN_OK;
+}
+
+int ctn_dynmix_plan_speed(const int* spk_ptr, const int* utt_ids, int S, const long long* lens, const float* inv_rms, const float* w,
+                          const int* pct, int n, long long seed, int epoch, int rank, unsigned* step, int B, int C, int seg_len,
+                          int* plan_utt, long long* plan_start, int* plan_q, float* gain, int* plan_pct, void* stream) {
+    CTN_REQUIRE(spk_ptr && utt_ids && lens && inv_rms && w && pct && step && plan_utt && plan_start && plan_q && gain && plan_pct,
+                "ctn_dynmix_plan_speed: null pointer");
+    CTN_REQUIRE(n >= 1 && n <= 151, "ctn_dynmix_plan_speed: n = %d speed percents (1 .. 151)", n);
+    CTN_REQUIRE(C >= 2 && C <= 4, "ctn_dynmix_plan_speed: C = %d sources per mixture (2 .. 4)", C);
+    CTN_REQUIRE(S >= C, "ctn_dynmix_plan_speed: %d speakers for mixtures of %d", S, C);
+    CTN_REQUIRE(B >= 1 && B <= (1 << 20), "ctn_dynmix_plan_speed: B = %d mixtures (1 .. 2^20)", B);
+    CTN_REQUIRE(seg_len >= 1, "ctn_dynmix_plan_speed: seg_len = %d", seg_len);
+    CTN_REQUIRE(seed >= 0 && seed < (1LL << 48), "ctn_dynmix_plan_speed: seed %lld outside [0, 2^48)", seed);
+    CTN_REQUIRE(rank >= 0 && rank < (1 << 16), "ctn_dynmix_plan_speed: rank %d outside [0, 2^16)", rank);
+    CTN_REQUIRE(epoch >= 0, "ctn_dynmix_plan_speed: epoch %d", epoch);
+    const unsigned k0 = (unsigned)(seed & 0xffffffffLL), k1 = (unsigned)(seed >> 32) | ((unsigned)rank << 16);
+    dynmix_plan_speed_kernel<<<dim3(1), dim3(DM_NT), 0, (hipStream_t)stream>>>(spk_ptr, utt_ids, S, lens, inv_rms, w, pct, n, k0, k1,
+                                                                               (unsigned)epoch, step, B, C, seg_len, plan_utt, plan_start,
+                                                                               plan_q, gain, plan_pct);
+    CTN_CHECK_LAUNCH("ctn_dynmix_plan_speed");
     return CTN_OK;
 }
 

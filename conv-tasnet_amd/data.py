@@ -108,6 +108,18 @@ def read_wav(path, sample_rate):
     sr, x = wavfile.read(path)
     if sr != sample_rate:
         raise ValueError("%s is at %d Hz, expected %d (resampling is outside the hot-path scope)" % (path, sr, sample_rate))
+    return _to_mono_float(x)
+
+
+def read_wav_native(path):
+    """(mono float32 in [-1, 1), the file's own rate): for DeviceCorpus.from_manifest(resample=True), which resamples on the
+    device.  The wav-file loaders' worker processes do not resample: they use read_wav."""
+    from scipy.io import wavfile
+    sr, x = wavfile.read(path)
+    return _to_mono_float(x), int(sr)
+
+
+def _to_mono_float(x):
     if x.dtype == np.int16:
         x = x.astype(np.float32) / 32768.0
     elif x.dtype == np.int32:

@@ -11,8 +11,12 @@ generator draws them (tools/create_txt_file_like_wsj0.py:21-22), sources at unit
 rescaled to a peak of 0.9 (tools/matlab-code/create_wav_2speakers.m:111-112).  A minibatch is a pure function of
 (seed, rank, epoch, step): a resumed run sees the minibatches of an uninterrupted one.
 
+Files at another rate: `from_manifest(..., resample=True)` / `from_arrays(..., sample_rates=, target_rate=)` resample them on
+the device (resample.py, csrc/ctn_resample.hip) before the levels are taken.  Speed perturbation: `speeds=range(95, 106)`
+replays every source at a drawn integer percent of its speed, resampled on the device by 100 / pct each step.
+
 Differences from the MATLAB tool, on purpose: the level is the plain RMS of the whole utterance (not ITU-T P.56 active
-level), the peak rescale is per drawn segment (not per whole utterance), and files must already be at `sample_rate`.
+level) and the peak rescale is per drawn segment (not per whole utterance).
 There is no CPU fallback: like the rest of the product path the loader needs the GPU.
 """
 import json
@@ -77,21 +81,28 @@ def _ptr(t):
 class DeviceCorpus:
     """U single-speaker utterances back to back in one flat float32 device buffer, with their levels."""
 
-    def __init__(self, arrays, speakers, device):
+    def __init__(self, arrays, speakers, device, sample_rates=None, target_rate=None):
         device = torch.device(device)
         if device.type != "cuda":
             raise ValueError("DeviceCorpus lives on the GPU: got device %s" % device)
         if len(arrays) == 0 or len(arrays) != len(speakers):
             raise ValueError("%d utterances with %d speaker labels" % (len(arrays), len(speakers)))
+        if (sample_rates is None) != (target_rate is None):
+            raise ValueError("sample_rates and target_rate go together")
         arrays = [np.ascontiguousarray(a, dtype=np.float32).reshape(-1) for a in arrays]
         lens = np.array([a.shape[0] for a in arrays], dtype=np.int64)
         if int(lens.min()) < 1:
             raise ValueError("empty utterance in the corpus")
-        offsets = np.concatenate(([0], np.cumsum(lens)[:-1])).astype(np.int64)
         self.device = device
         self.speakers = [str(s) for s in speakers]
+        if sample_rates is not None and any(int(r) != int(target_rate) for r in sample_rates):
+            lens, offsets = self._upload_resampled(arrays, lens, sample_rates, int(target_rate))
+        else:
+            if sample_rates is not None and len(sample_rates) != len(arrays):
+                raise ValueError("%d utterances with %d sample rates" % (len(arrays), len(sample_rates)))
+            offsets = np.concatenate(([0], np.cumsum(lens)[:-1])).astype(np.int64)
+            self.corpus = torch.from_numpy(np.concatenate(arrays)).to(device)
         self.lens_host, self.offsets_host = lens, offsets
-        self.corpus = torch.from_numpy(np.concatenate(arrays)).to(device)
         self.offsets = torch.from_numpy(offsets).to(device)
         self.lens = torch.from_numpy(lens).to(device)
         msq = torch.empty(len(arrays), dtype=torch.float64, device=device)
@@ -102,21 +113,56 @@ class DeviceCorpus:
         self.w = torch.from_numpy(level_table()).to(device)
         self._tables = {}
 
-    @classmethod
-    def from_arrays(cls, arrays, speakers, device):
-        return cls(arrays, speakers, device)
+    def _upload_resampled(self, arrays, lens, sample_rates, target_rate):
+        """Utterances at `target_rate` are uploaded as they are; the others are uploaded at their own rate, one flat buffer per
+        source rate, and resampled on the device straight into their place in the corpus.  -> the corpus' (lens, offsets)."""
+        from . import resample as _rs
+        if len(sample_rates) != len(arrays):
+            raise ValueError("%d utterances with %d sample rates" % (len(arrays), len(sample_rates)))
+        rates = [int(r) for r in sample_rates]
+        ratios = [_rs.ratio(r, target_rate) for r in rates]
+        out_lens = np.array([_rs.out_len(n, up, down) for n, (up, down) in zip(lens, ratios)], dtype=np.int64)
+        offsets = np.concatenate(([0], np.cumsum(out_lens)[:-1])).astype(np.int64)
+        host = np.zeros(int(out_lens.sum()), dtype=np.float32)
+        for u, r in enumerate(rates):
+            if r == target_rate:
+                host[offsets[u]:offsets[u] + out_lens[u]] = arrays[u]
+        self.corpus = torch.from_numpy(host).to(self.device)
+        for r in sorted(set(rates) - {target_rate}):
+            rows = [u for u in range(len(arrays)) if rates[u] == r]
+            up, down = _rs.ratio(r, target_rate)
+            in_lens = lens[rows]
+            in_offsets = np.concatenate(([0], np.cumsum(in_lens)[:-1])).astype(np.int64)
+            x = torch.from_numpy(np.concatenate([arrays[u] for u in rows])).to(self.device)
+            _rs.resample_rows(x, in_offsets, in_lens, up, down, self.corpus, offsets[rows])
+        return out_lens, offsets
 
     @classmethod
-    def from_manifest(cls, json_path, sample_rate, device, reader=_data.read_wav):
-        """json list of (wav_path, n_samples, speaker): every file is read once and uploaded."""
+    def from_arrays(cls, arrays, speakers, device, sample_rates=None, target_rate=None):
+        """sample_rates (one per utterance) and target_rate: utterances at another rate are resampled on the device."""
+        return cls(arrays, speakers, device, sample_rates, target_rate)
+
+    @classmethod
+    def from_manifest(cls, json_path, sample_rate, device, reader=None, resample=False):
+        """json list of (wav_path, n_samples, speaker): every file is read once and uploaded.  reader(path, sample_rate) -> x
+        (default data.read_wav: a file at another rate is a ValueError).  resample=True: reader(path) -> (x, file_rate)
+        (default data.read_wav_native), files at other rates are resampled on the device; n_samples counts the FILE's samples."""
         with open(json_path, "r") as f:
             infos = json.load(f)
-        arrays = []
+        if reader is None:
+            reader = _data.read_wav_native if resample else _data.read_wav
+        arrays, rates = [], []
         for path, n, _ in infos:
-            x = reader(path, sample_rate)
+            if resample:
+                x, sr = reader(path)
+                rates.append(int(sr))
+            else:
+                x = reader(path, sample_rate)
             if x.shape[0] != int(n):
                 raise ValueError("%s has %d samples, the manifest says %d" % (path, x.shape[0], int(n)))
             arrays.append(x)
+        if resample:
+            return cls(arrays, [i[2] for i in infos], device, rates, int(sample_rate))
         return cls(arrays, [i[2] for i in infos], device)
 
     num_utterances = property(lambda self: len(self.lens_host))
@@ -146,10 +192,13 @@ class DynamicMixLoader:
     (`lengths` is one shared constant tensor).  `dataset.set_epoch(epoch)` (the Solver calls it) selects the epoch;
     with reshuffle=False the epoch stays 0: the same minibatches every time, a fixed validation set without mixture files.
     Every rank draws its own stream (`rank` enters the Philox key, the world size does not) and runs the same number of steps.
-    gather_mode: the form of ctn_dynmix_gather (None: GATHER_MODE); both give the same bits."""
+    gather_mode: the form of ctn_dynmix_gather (None: GATHER_MODE); both give the same bits.
+    speeds: None, or integer percents in [50, 200]: every source is replayed at a drawn percent of its speed (one more Philox
+    block per source; speaker, utterance and level draws are those of speeds=None), resampled on the device into a segment
+    buffer the gather then mixes.  Eligible utterances hold ceil(segment_len * max(speeds) / 100) samples."""
 
     def __init__(self, corpus, batch_size, segment_len, num_speakers=2, steps_per_epoch=1000, seed=0, rank=None,
-                 reshuffle=True, gather_mode=None):
+                 reshuffle=True, gather_mode=None, speeds=None):
         if rank is None:
             from . import parallel
             rank = torch.distributed.get_rank() if parallel.world_size() > 1 else parallel.env_world()[1]
@@ -166,7 +215,12 @@ class DynamicMixLoader:
         self.steps_per_epoch, self.seed, self.rank, self.reshuffle = int(steps_per_epoch), seed, rank, bool(reshuffle)
         self.gather_mode = GATHER_MODE if gather_mode is None else int(gather_mode)
         self.epoch = 0
-        self.tables, self._spk_ptr, self._utt_ids = corpus.tables(self.T, self.C)
+        self.speeds = None
+        if speeds is not None:
+            from . import resample as _rs
+            self.speeds = _rs.parse_speeds(speeds)
+        self.eligible_len = self.T if self.speeds is None else _rs.eligible_len(self.T, self.speeds)
+        self.tables, self._spk_ptr, self._utt_ids = corpus.tables(self.eligible_len, self.C)
         dev = corpus.device
         self.device = dev
         self._step = torch.zeros(1, dtype=torch.int32, device=dev)                  # the step word
@@ -177,7 +231,15 @@ class DynamicMixLoader:
         self._peak = torch.zeros(self.B, dtype=torch.float32, device=dev)
         self._ws = torch.zeros(max(1, lib.ctn_dynmix_gather_workspace(self.B, self.T)), dtype=torch.uint8, device=dev)
         self._lengths = torch.full((self.B,), self.T, dtype=torch.int64, device=dev)
-        self.dataset = self                                                          # Solver: loader.dataset.set_epoch(epoch)
+        if self.speeds is not None:
+            self._banks = _rs.speed_banks(self.speeds, dev)
+            self._pct = torch.tensor(self.speeds, dtype=torch.int32, device=dev)
+            self._plan_pct = torch.zeros(self.B, self.C, dtype=torch.int32, device=dev)
+            self._seg = _SegmentBuffer(self.B, self.C, self.T, dev)
+
+    # Solver: loader.dataset.set_epoch(epoch).  A property, not an attribute: `self.dataset = self` is a reference cycle, and a
+    # dropped loader's device buffers would then stay allocated until the cyclic collector happens to run
+    dataset = property(lambda self: self)
 
     def __len__(self):
         return self.steps_per_epoch
@@ -196,6 +258,16 @@ class DynamicMixLoader:
                 raise ValueError("%s must be a contiguous float32 %s tensor on %s" % (name, shape, self.device))
         c = self.corpus
         stream = torch.cuda.current_stream(self.device).cuda_stream
+        if self.speeds is not None:
+            lib.call("ctn_dynmix_plan_speed", _ptr(self._spk_ptr), _ptr(self._utt_ids), len(self.tables["spk_ptr"]) - 1,
+                     _ptr(c.lens), _ptr(c.inv_rms), _ptr(c.w), _ptr(self._pct), len(self.speeds), self.seed, self.epoch, self.rank,
+                     _ptr(self._step), B, C, T, _ptr(self._plan_utt), _ptr(self._plan_start), _ptr(self._plan_q), _ptr(self._gain),
+                     _ptr(self._plan_pct), stream)
+            self._seg.mix(c, self._banks, self._plan_utt, self._plan_start, self._plan_pct, self._gain, mixture, sources,
+                          self._peak, self._ws, self.gather_mode, stream)
+            if lengths is not None:
+                lengths.copy_(self._lengths)
+            return
         lib.call("ctn_dynmix_plan", _ptr(self._spk_ptr), _ptr(self._utt_ids), len(self.tables["spk_ptr"]) - 1, _ptr(c.lens),
                  _ptr(c.inv_rms), _ptr(c.w), self.seed, self.epoch, self.rank, _ptr(self._step), B, C, T,
                  _ptr(self._plan_utt), _ptr(self._plan_start), _ptr(self._plan_q), _ptr(self._gain), stream)
@@ -206,8 +278,10 @@ class DynamicMixLoader:
             lengths.copy_(self._lengths)
 
     def last_plan(self):
-        """Copies of the last minibatch's plan: (plan_utt [B,C] i32, plan_start [B,C] i64, plan_q [B,C] i32, gain [B,C] f32)."""
-        return self._plan_utt.clone(), self._plan_start.clone(), self._plan_q.clone(), self._gain.clone()
+        """Copies of the last minibatch's plan: (plan_utt [B,C] i32, plan_start [B,C] i64, plan_q [B,C] i32, gain [B,C] f32),
+        and with speeds the drawn percents plan_pct [B,C] i32 as a fifth element."""
+        plan = self._plan_utt.clone(), self._plan_start.clone(), self._plan_q.clone(), self._gain.clone()
+        return plan if self.speeds is None else plan + (self._plan_pct.clone(),)
 
     def last_peak(self):
         """peak [B] of the last minibatch before the rescale to 0.9."""
@@ -222,9 +296,31 @@ class DynamicMixLoader:
             yield mixture, self._lengths, sources
 
 
-def gather(corpus, plan_utt, plan_start, gain, segment_len, mode=None):
+class _SegmentBuffer:
+    """seg [B,C,T]: the unit-gain speed-perturbed segments of one minibatch, laid out as a corpus of B * C utterances of T
+    samples for ctn_dynmix_gather (offsets = arange * T, lens = T, start = 0; seg_utt = arange, -1 for a flagged entry)."""
+
+    def __init__(self, B, C, T, device):
+        self.B, self.C, self.T = B, C, T
+        self.seg = torch.zeros(B * C * T, dtype=torch.float32, device=device)
+        self.seg_utt = torch.zeros(B, C, dtype=torch.int32, device=device)
+        self.offsets = torch.arange(B * C, dtype=torch.int64, device=device) * T
+        self.lens = torch.full((B * C,), T, dtype=torch.int64, device=device)
+        self.start = torch.zeros(B, C, dtype=torch.int64, device=device)
+
+    def mix(self, corpus, banks, plan_utt, plan_start, plan_pct, gain, mixture, sources, peak, ws, mode, stream):
+        B, C, T = self.B, self.C, self.T
+        lib.call("ctn_dynmix_speed_segments", _ptr(corpus.corpus), _ptr(corpus.offsets), _ptr(corpus.lens), corpus.num_utterances,
+                 _ptr(plan_utt), _ptr(plan_start), _ptr(plan_pct), B, C, T, _ptr(banks.banks), banks.banks.numel(), _ptr(banks.table),
+                 banks.span_cap, banks.bank_cap, _ptr(self.seg), _ptr(self.seg_utt), stream)
+        lib.call("ctn_dynmix_gather", _ptr(self.seg), _ptr(self.offsets), _ptr(self.lens), B * C, _ptr(self.seg_utt),
+                 _ptr(self.start), _ptr(gain), B, C, T, _ptr(mixture), _ptr(sources), _ptr(peak), _ptr(ws), ws.numel(), mode, stream)
+
+
+def gather(corpus, plan_utt, plan_start, gain, segment_len, mode=None, plan_pct=None):
     """The minibatch of a caller-written plan: plan_utt [B,C] int32, plan_start [B,C] int64, gain [B,C] float32 on the
-    corpus' device -> (mixture [B,T], sources [B,C,T], peak [B])."""
+    corpus' device -> (mixture [B,T], sources [B,C,T], peak [B]).  plan_pct [B,C] int32: speed percents in [50, 200], the
+    sources replayed at these (plan_start + ceil(T * pct / 100) <= the utterance's length)."""
     dev = corpus.device
     B, C = plan_utt.shape
     T = int(segment_len)
@@ -235,6 +331,14 @@ def gather(corpus, plan_utt, plan_start, gain, segment_len, mode=None):
     sources = torch.empty(B, C, T, dtype=torch.float32, device=dev)
     peak = torch.empty(B, dtype=torch.float32, device=dev)
     ws = torch.empty(max(1, lib.ctn_dynmix_gather_workspace(B, T)), dtype=torch.uint8, device=dev)
+    if plan_pct is not None:
+        from . import resample as _rs
+        pcts = sorted(set(int(p) for p in plan_pct.reshape(-1).tolist()))
+        banks = _rs.speed_banks([p for p in pcts if _rs.PCT_LO <= p <= _rs.PCT_HI] or [100], dev)
+        plan_pct = plan_pct.to(device=dev, dtype=torch.int32).contiguous()
+        _SegmentBuffer(B, C, T, dev).mix(corpus, banks, plan_utt, plan_start, plan_pct, gain, mixture, sources, peak, ws,
+                                         GATHER_MODE if mode is None else int(mode), torch.cuda.current_stream(dev).cuda_stream)
+        return mixture, sources, peak
     lib.call("ctn_dynmix_gather", _ptr(corpus.corpus), _ptr(corpus.offsets), _ptr(corpus.lens), corpus.num_utterances,
              _ptr(plan_utt), _ptr(plan_start), _ptr(gain), B, C, T, _ptr(mixture), _ptr(sources), _ptr(peak), _ptr(ws),
              ws.numel(), GATHER_MODE if mode is None else int(mode), torch.cuda.current_stream(dev).cuda_stream)

@@ -96,22 +96,39 @@ def build_parser():
                     "from this second manifest (the same minibatches every epoch); default: --data-dir's cv/")
     ap.add_argument("--cv-steps", type=int, default=100, help="minibatches of the --dynamic-mix-cv validation set")
     ap.add_argument("--seed", type=int, default=0, help="seed of the dynamic-mixing draw")
+    ap.add_argument("--segment-len", type=int, default=32000, help="samples per segment of the dynamic-mixing loaders")
+    ap.add_argument("--tiny", action="store_true", help="a tiny model (N=64 L=20 B=32 H=64 P=3 X=2 R=2) instead of the paper's: a "
+                    "quick end-to-end check of a data path")
+    ap.add_argument("--speed-perturb", default=None, metavar="LO:HI", help="--dynamic-mix only: replay every source at a drawn "
+                    "integer percent of its speed in [LO, HI], e.g. 95:105 (resampled on the device); validation never perturbs")
+    ap.add_argument("--corpus-rate", default="8000", choices=["8000", "auto"], help="rate of the --dynamic-mix files: 8000 (any "
+                    "other rate is an error), or auto: files at other rates are resampled to 8 kHz on the device")
     return ap
 
 
-def main():
+TINY = dict(N=64, L=20, B=32, H=64, P=3, X=2, R=2, C=2)
+
+
+def main(argv=None):
     import os
-    a = build_parser().parse_args()
+    a = build_parser().parse_args(argv)
+    if a.speed_perturb and not a.dynamic_mix:
+        raise SystemExit("--speed-perturb applies to --dynamic-mix only")
     world, rank, device = parallel.init_distributed()
     tr = cv = None
     if a.dynamic_mix or a.dynamic_mix_cv:
         from .dynmix import DeviceCorpus, DynamicMixLoader
+        auto = a.corpus_rate == "auto"
         if a.dynamic_mix:
-            tr = DynamicMixLoader(DeviceCorpus.from_manifest(a.dynamic_mix, 8000, device), a.batch_size, 32000,
-                                  steps_per_epoch=a.steps_per_epoch, seed=a.seed, rank=rank)
+            speeds = None
+            if a.speed_perturb:
+                from .resample import parse_speed_range
+                speeds = parse_speed_range(a.speed_perturb)
+            tr = DynamicMixLoader(DeviceCorpus.from_manifest(a.dynamic_mix, 8000, device, resample=auto), a.batch_size, a.segment_len,
+                                  steps_per_epoch=a.steps_per_epoch, seed=a.seed, rank=rank, speeds=speeds)
         if a.dynamic_mix_cv:
-            cv = DynamicMixLoader(DeviceCorpus.from_manifest(a.dynamic_mix_cv, 8000, device), a.batch_size, 32000,
-                                  steps_per_epoch=a.cv_steps, seed=a.seed + 1, rank=rank, reshuffle=False)
+            cv = DynamicMixLoader(DeviceCorpus.from_manifest(a.dynamic_mix_cv, 8000, device, resample=auto), a.batch_size,
+                                  a.segment_len, steps_per_epoch=a.cv_steps, seed=a.seed + 1, rank=rank, reshuffle=False)
     if a.data_dir:
         from .data import AudioDataLoader, AudioDataset
         if tr is None:
@@ -124,8 +141,8 @@ def main():
         tr = SyntheticLoader(a.batches, a.batch_size, rank=rank, world=world)
     if cv is None:
         cv = SyntheticLoader(1, a.batch_size, first_utt=10 ** 6, rank=rank, world=world)
-    train({'tr_loader': tr, 'cv_loader': cv}, a.epochs, a.model_path, save_folder=a.save_folder, lr=a.lr,
-          optimizer_type=a.optimizer, momentum=a.momentum, l2=a.l2)
+    return train({'tr_loader': tr, 'cv_loader': cv}, a.epochs, a.model_path, save_folder=a.save_folder, lr=a.lr,
+                 optimizer_type=a.optimizer, momentum=a.momentum, l2=a.l2, config=TINY if a.tiny else None)
 
 
 if __name__ == "__main__":

@@ -589,6 +589,59 @@ int ctn_dynmix_gather(const float* corpus, const long long* offsets, const long 
                       const long long* plan_start, const float* gain, int B, int C, int T, float* mixture, float* sources,
                       float* peak, void* workspace, size_t workspace_bytes, int mode, void* stream);
 
+/* ---- on-device sinc resampling: corpora at any rate, speed perturbation (csrc/ctn_resample.hip, csrc/ctn_dynmix.hip) ------
+ * what librosa.load(path, sr=sample_rate) does for the reference's loaders, for ragged rows in device memory.
+ * Filter (designed on the host in fp64, rounded once to fp32: resample.design_filter): up / down in lowest terms,
+ *     fc = rolloff * min(1, up / down),  W = ceil(zeros / fc)                 (zeros = 32, rolloff = 0.95, beta = 14.77)
+ *     h [up][2W]: for phase p in [0, up) and tap j in [0, 2W), tau = (j - W + 1) - p / up,
+ *     h[p][j] = fc * sinc(fc * tau) * I0(beta * sqrt(1 - (tau / W)^2)) / I0(beta), 0 where |tau| >= W   (sinc(v) = sin(pi v) / (pi v));
+ *     every phase is then divided by its own sum, so a constant stays constant.
+ * Output sample t of a row sits at input position t * down / up: i = floor(t * down / up), p = (t * down) mod up,
+ *     y[t] = sum_{j = 0}^{2W - 1} h[p][j] * x[i + j - W + 1]            n_out = ceil(n_in * up / down)
+ *     acc = +0; for j ascending: acc = acc + h[p][j] * x[..]: every product and every add is one fp32 rounding (no fused
+ *     multiply-add).  x outside [0, n_in) of its OWN row reads as zero.  The output is a bitwise function of the table and the
+ *     input, whatever the launch geometry.
+ *   ctn_resample_ragged: U rows of one flat buffer x (x_samples floats; in_offsets, in_lens [U] int64 in device memory)
+ *     into rows of the flat buffer y (y_samples floats; out_offsets, out_lens [U]), out_lens[r] = ceil(in_lens[r] * up / down).
+ *     host_tables [4][U] int64 in HOST memory holds the same four tables (in_offsets, in_lens, out_offsets, out_lens): sizes and
+ *     every row are checked against the two buffers before the launch (CTN_ERR_ARG, nothing launched), and the grid is sized
+ *     from them.  The kernel checks the device tables again: a row outside its buffer is neither read nor written and
+ *     status[r] = -1 (0 otherwise; status [U] int32 may be null).  1 <= up, down <= 2^20, gcd(up, down) = 1, rows of 1 .. 2^40
+ *     samples.  One workgroup of 256 threads per 1024 consecutive outputs of a row (fewer where down / up is large) stages
+ *     their input span, and the bank when it fits, in LDS.  ctn_resample_span(up, down, W, chunk) = that span in floats,
+ *     floor((up - 1 + (chunk - 1) * down) / up) + 2W (0 for arguments out of range, chunk <= 1024).
+ *   ctn_dynmix_plan_speed: ctn_dynmix_plan plus a table pct [n] int32 of speed percents in device memory (1 <= n <= 151, every
+ *     entry in [50, 200]).  For source c of mixture b ONE MORE Philox block under the same key,
+ *         counter = (c + 256, b, step, epoch)        word 0: plan_pct[b,c] = pct[(uint64(word 0) * n) >> 32]
+ *     The block (c, b, step, epoch) draws speaker, utterance and level exactly as ctn_dynmix_plan does; its word 2 draws the start
+ *     uniform in [0, lens[u] - need] with need = ceil(seg_len * pct / 100), the input samples the segment spans.  Eligible
+ *     utterances (spk_ptr / utt_ids): lens[u] >= ceil(seg_len * max(pct) / 100) and meansq[u] > 0.  *step += 1 on the device.
+ *   ctn_dynmix_speed_segments: seg [B,C,T] fp32 = the unit-gain segments of a plan with speeds.  Source (b,c) is utterance u
+ *     replayed at pct % of its speed: resampled by up / down = 100 / pct in lowest terms, output sample 0 at input sample
+ *     plan_start,  seg[b,c,t] = sum_j h[p][j] * x_u[plan_start + i + j - W + 1]  with the sum above; x_u outside [0, lens[u]) reads
+ *     as zero, inside it (before plan_start, or past plan_start + need) it reads the utterance.  pct = 100 is a plain copy,
+ *     seg[b,c,t] = x_u[plan_start + t], whatever the tables say.  banks: the fp32 tables of all configured percents in one flat
+ *     buffer of bank_floats floats; bank_tab [151][4] int32, row pct - 50 = (up, down, W, offset of h in banks), W = 0 for a
+ *     percent that is not configured.  span_cap, bank_cap: LDS floats for the input span of 1024 outputs (>= the largest
+ *     ctn_resample_span(up, down, W, 1024) configured) and for a staged bank (a bank of more than bank_cap / (2W + 1) phases is
+ *     read through the cache); 4 * (span_cap + bank_cap) <= 61440.  An entry that is never read -- u outside [0, U), start < 0,
+ *     start + need > lens[u], pct outside [50, 200] or not configured, a table row outside banks -- gives a segment of zeros
+ *     and seg_utt[b,c] = -1; every other entry gives seg_utt[b,c] = b * C + c.
+ *   The mix: ctn_dynmix_gather over seg as a corpus of B * C utterances of T samples (offsets = arange * T, lens = T), with
+ *     plan_utt = seg_utt and plan_start = 0: gains, sum order, peak and the 0.9 rescale are the contract above, both modes, and
+ *     a flagged entry gives peak[b] = -1 as there. */
+size_t ctn_resample_span(int up, int down, int W, int chunk);
+int ctn_resample_ragged(const float* x, long long x_samples, const long long* in_offsets, const long long* in_lens, long long U, int up,
+                        int down, const float* h, int W, float* y, long long y_samples, const long long* out_offsets,
+                        const long long* out_lens, const long long* host_tables, int* status, void* stream);
+int ctn_dynmix_plan_speed(const int* spk_ptr, const int* utt_ids, int S, const long long* lens, const float* inv_rms, const float* w,
+                          const int* pct, int n, long long seed, int epoch, int rank, unsigned* step, int B, int C, int seg_len,
+                          int* plan_utt, long long* plan_start, int* plan_q, float* gain, int* plan_pct, void* stream);
+int ctn_dynmix_speed_segments(const float* corpus, const long long* offsets, const long long* lens, long long U, const int* plan_utt,
+                              const long long* plan_start, const int* plan_pct, int B, int C, int T, const float* banks,
+                              long long bank_floats, const int* bank_tab, int span_cap, int bank_cap, float* seg, int* seg_utt,
+                              void* stream);
+
 #ifdef __cplusplus
 }
 #endif
