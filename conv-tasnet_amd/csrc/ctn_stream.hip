@@ -22,6 +22,9 @@ constexpr int ST_GRP = ST_NT / ST_TC;   // channel groups of the cLN partial sum
 constexpr int ST_MAXP = 8;        // depthwise taps
 constexpr int ST_MAXC = 8;        // speakers (softmax mask)
 constexpr int ST_HDR = 64;        // floats in front of the rings: word 0 = frame position
+constexpr int ST_TAB = 8;         // ints per slot of a ragged step table (CTN_STREAM_TAB): nf, nh, src, dst, out hop offsets, 3 spare
+constexpr int ST_RST_SLOTS = 32;  // slots / rings per launch of the per-slot reset
+constexpr int ST_RST_RINGS = 64;
 constexpr size_t ST_MAX_LDS = 64 * 1024;
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -33,6 +36,13 @@ inline long long ring_len(int P, int d, int max_frames) { return pow2ceil((long 
 inline size_t block_floats(int B, int H, int P) { return (size_t)2 * H * B + 4 + (size_t)4 * H + (size_t)H * P; }
 
 enum { EPI_STORE = 0, EPI_ADD = 1, EPI_RELU = 2 };
+
+// Frames slot m computes in this step: the call's `frames` (F), or with RAGGED its own count from the step table, clamped to 0 .. F
+// (F is the leading dimension of every activation of the step: a bad table cannot index past a row).
+template <bool RAGGED>
+__device__ __forceinline__ int slot_frames(const int* __restrict__ tab, int m, int F) {
+    return RAGGED ? min(max(tab[m * ST_TAB], 0), F) : F;
+}
 
 // ---- weights -> MFMA fragment order --------------------------------------------------------------------------------
 // W [R, Cn] row-major -> float4 [ceil(R/16)][ceil(Cn/16)][64 lanes]: element i of lane l in (row tile rt, k group g) is
@@ -278,19 +288,25 @@ struct StageArgs {
     float* y;               // [M,B,F], in place
     const float* ring_prev; // [M,H,Rp]   (j >= 1)
     float* ring_cur;        // [M,H,Rc]   (j < nblocks)
-    const unsigned* pos;    // device word: index of this chunk's first frame
+    const unsigned* pos;    // device word: index of this chunk's first frame (RAGGED: one word per slot)
+    const int* tab;         // RAGGED: step table [M][ST_TAB]
     int Rp, dp, Rc;
     int B, H, P, F, tiles;
 };
 
+// RAGGED (every kernel of a step): slot m computes nf[m] <= F frames from its own ring position; a workgroup whose tile starts at or
+// beyond nf[m] returns before its first load and barrier (blockIdx and the table only: uniform over the workgroup).
+template <bool RAGGED>
 __global__ __launch_bounds__(ST_NT) void stream_stage_kernel(StageArgs a) {
     extern __shared__ float lds[];
     float* ybuf = lds;                              // [B][16]
     float* hbuf = ybuf + (size_t)a.B * ST_TC;       // [H][16]
     float* part = hbuf + (size_t)a.H * ST_TC;       // [ST_GRP][16]
     const int m = blockIdx.x / a.tiles, k0 = (blockIdx.x % a.tiles) * ST_TC;
-    const int nvalid = min(ST_TC, a.F - k0);
-    const unsigned pos = a.pos[0] + (unsigned)k0;
+    const int nf = slot_frames<RAGGED>(a.tab, m, a.F);
+    if (RAGGED && k0 >= nf) return;
+    const int nvalid = min(ST_TC, nf - k0);
+    const unsigned pos = a.pos[RAGGED ? m : 0] + (unsigned)k0;
     const int B = a.B, H = a.H, P = a.P;
     float* yg = a.y + (size_t)m * B * a.F;
     tile_load(ybuf, yg, B, a.F, k0, nvalid);
@@ -324,23 +340,28 @@ struct RowsArgs {
     float* hraw;            // [M,H,F]
     float* ring;            // [M,H,R]
     const unsigned* pos;
+    const int* tab;         // RAGGED: step table
     int R, d;
     int B, H, P, F, nsplit;
 };
 
+template <bool RAGGED>
 __global__ __launch_bounds__(ST_NT) void stream_rows_a_kernel(RowsArgs a) {
     extern __shared__ float lds[];
     float* ybuf = lds;
     float* hbuf = ybuf + (size_t)a.B * ST_TC;
     const int m = blockIdx.x / a.nsplit, sp = blockIdx.x % a.nsplit, wave = threadIdx.x >> 6;
     const int Rt = a.H / 16, per = (Rt + a.nsplit - 1) / a.nsplit, rt0 = min(sp * per, Rt), rt1 = min(rt0 + per, Rt);
-    tile_load(ybuf, a.y + (size_t)m * a.B * a.F, a.B, a.F, 0, a.F);
+    const int nf = slot_frames<RAGGED>(a.tab, m, a.F);     // a.F: leading dimension; nf: valid columns
+    if (RAGGED && nf == 0) return;
+    tile_load(ybuf, a.y + (size_t)m * a.B * a.F, a.B, a.F, 0, nf);
     __syncthreads();
     for (int rt = rt0 + wave; rt < rt1; rt += ST_NW) gemm_rows<EPI_STORE, 1>(reinterpret_cast<const float4*>(a.blk), rt, a.B / 16, ybuf, hbuf);
     __syncthreads();
-    tile_store(hbuf + (size_t)rt0 * 16 * ST_TC, a.hraw + ((size_t)m * a.H + rt0 * 16) * a.F, (rt1 - rt0) * 16, a.F, 0, a.F);
+    tile_store(hbuf + (size_t)rt0 * 16 * ST_TC, a.hraw + ((size_t)m * a.H + rt0 * 16) * a.F, (rt1 - rt0) * 16, a.F, 0, nf);
 }
 
+template <bool RAGGED>
 __global__ __launch_bounds__(ST_NT) void stream_rows_b_kernel(RowsArgs a) {
     extern __shared__ float lds[];
     float* ybuf = lds;
@@ -349,24 +370,31 @@ __global__ __launch_bounds__(ST_NT) void stream_rows_b_kernel(RowsArgs a) {
     const int m = blockIdx.x / a.nsplit, sp = blockIdx.x % a.nsplit, wave = threadIdx.x >> 6;
     const int B = a.B, H = a.H;
     const int Rt = B / 16, per = (Rt + a.nsplit - 1) / a.nsplit, rt0 = min(sp * per, Rt), rt1 = min(rt0 + per, Rt);
-    const unsigned pos = a.pos[0];
+    const int nf = slot_frames<RAGGED>(a.tab, m, a.F);
+    if (RAGGED && nf == 0) return;
+    const unsigned pos = a.pos[RAGGED ? m : 0];
     const float* vec = a.blk + (size_t)2 * H * B;
     float* yg = a.y + ((size_t)m * B + rt0 * 16) * a.F;
     float* ring = a.ring + (size_t)m * H * a.R;
-    tile_load(hbuf, a.hraw + (size_t)m * H * a.F, H, a.F, 0, a.F);
-    tile_load(ybuf + (size_t)rt0 * 16 * ST_TC, yg, (rt1 - rt0) * 16, a.F, 0, a.F);
+    tile_load(hbuf, a.hraw + (size_t)m * H * a.F, H, a.F, 0, nf);
+    tile_load(ybuf + (size_t)rt0 * 16 * ST_TC, yg, (rt1 - rt0) * 16, a.F, 0, nf);
     tile_cln(hbuf, H, vec, vec + 4, vec + 4 + H, part);
-    if (sp == 0) ring_store(ring, a.R, pos, hbuf, H, a.F);
+    if (sp == 0) ring_store(ring, a.R, pos, hbuf, H, nf);
     tile_dw_any<true>(hbuf, ring, a.R, pos, a.d, H, a.P, vec + 4 + 4 * H, hbuf);
     tile_cln(hbuf, H, vec + 1, vec + 4 + 2 * H, vec + 4 + 3 * H, part);
     for (int rt = rt0 + wave; rt < rt1; rt += ST_NW)
         gemm_rows<EPI_ADD, 1>(reinterpret_cast<const float4*>(a.blk + (size_t)H * B), rt, H / 16, hbuf, ybuf);
     __syncthreads();
-    tile_store(ybuf + (size_t)rt0 * 16 * ST_TC, yg, (rt1 - rt0) * 16, a.F, 0, a.F);
+    tile_store(ybuf + (size_t)rt0 * 16 * ST_TC, yg, (rt1 - rt0) * 16, a.F, 0, nf);
 }
 
 __global__ void stream_advance_kernel(unsigned* pos, int frames) {
     if (threadIdx.x == 0 && blockIdx.x == 0) pos[0] += (unsigned)frames;
+}
+
+__global__ __launch_bounds__(256) void stream_advance_ragged_kernel(unsigned* __restrict__ pos, const int* __restrict__ tab, int M, int F) {
+    const int m = blockIdx.x * 256 + threadIdx.x;
+    if (m < M) pos[m] += (unsigned)slot_frames<true>(tab, m, F);
 }
 
 // ---- front end: frames of the sample buffer -> relu(U x) = w -> cLN -> bottleneck 1x1 = y ---------------------------
@@ -374,9 +402,11 @@ struct FrontArgs {
     const float* x; int xld;        // [M][xld] samples; frame k = x[k*S .. k*S+L)
     const float* Up; const float* g0; const float* b0; const float* Wbp;
     float* w; float* y;             // [M,N,F], [M,B,F]
+    const int* tab;                 // RAGGED: step table
     int N, L, B, F, tiles;
 };
 
+template <bool RAGGED>
 __global__ __launch_bounds__(ST_NT) void stream_front_kernel(FrontArgs a) {
     extern __shared__ float lds[];
     const int Lp = (a.L + 15) / 16 * 16, S = a.L / 2;
@@ -385,7 +415,9 @@ __global__ __launch_bounds__(ST_NT) void stream_front_kernel(FrontArgs a) {
     float* ybuf = wbuf + (size_t)a.N * ST_TC;       // [B][16]
     float* part = ybuf + (size_t)a.B * ST_TC;
     const int m = blockIdx.x / a.tiles, k0 = (blockIdx.x % a.tiles) * ST_TC;
-    const int nvalid = min(ST_TC, a.F - k0);
+    const int nf = slot_frames<RAGGED>(a.tab, m, a.F);
+    if (RAGGED && k0 >= nf) return;
+    const int nvalid = min(ST_TC, nf - k0);
     const float* xg = a.x + (size_t)m * a.xld;
     for (int e = threadIdx.x; e < Lp * ST_TC; e += ST_NT) {
         const int i = e / ST_TC, c = e & (ST_TC - 1);
@@ -406,9 +438,11 @@ __global__ __launch_bounds__(ST_NT) void stream_front_kernel(FrontArgs a) {
 struct BackArgs {
     const float* y; const float* w; const float* Wmp; const float* Vp;
     float* fr;                      // [M,C,L,F]
+    const int* tab;                 // RAGGED: step table
     int N, L, B, C, F, tiles, softmax;
 };
 
+template <bool RAGGED>
 __global__ __launch_bounds__(ST_NT) void stream_back_kernel(BackArgs a) {
     extern __shared__ float lds[];
     const int Lp = (a.L + 15) / 16 * 16, N = a.N, C = a.C;
@@ -416,7 +450,9 @@ __global__ __launch_bounds__(ST_NT) void stream_back_kernel(BackArgs a) {
     float* sbuf = ybuf + (size_t)a.B * ST_TC;           // [C*N][16]
     float* fbuf = sbuf + (size_t)C * N * ST_TC;         // [C][Lp][16]
     const int m = blockIdx.x / a.tiles, k0 = (blockIdx.x % a.tiles) * ST_TC;
-    const int nvalid = min(ST_TC, a.F - k0);
+    const int nf = slot_frames<RAGGED>(a.tab, m, a.F);
+    if (RAGGED && k0 >= nf) return;
+    const int nvalid = min(ST_TC, nf - k0);
     tile_load(ybuf, a.y + (size_t)m * a.B * a.F, a.B, a.F, k0, nvalid);
     __syncthreads();
     tile_gemm<EPI_STORE>(a.Wmp, C * N / 16, a.B / 16, ybuf, sbuf);
@@ -448,24 +484,80 @@ __global__ __launch_bounds__(ST_NT) void stream_back_kernel(BackArgs a) {
 
 // Overlap-add with the carried half frame (L = 2S: at most two frames meet in a sample, and a two-term sum commutes), then the carries:
 // tail = second half of the last frame; the first S samples of the sample buffer = its last S consumed ones.  One thread per (row, r).
+// RAGGED: nf[m] frames per row of slot m (F stays the leading dimension of fr and out); a slot with nf = 0 keeps both of its carries.
+template <bool RAGGED>
 __global__ __launch_bounds__(256) void stream_ola_kernel(const float* __restrict__ fr, float* __restrict__ out, float* __restrict__ tail,
-                                                         float* __restrict__ x, int xld, int M, int MC, int L, int F) {
+                                                         float* __restrict__ x, int xld, int M, int MC, int L, int F,
+                                                         const int* __restrict__ tab) {
     const int S = L / 2;
     const int e = blockIdx.x * 256 + threadIdx.x;
     if (e < MC * S) {
         const int mc = e / S, r = e % S;
-        const float* f = fr + (size_t)mc * L * F;
-        float prev = tail[e];
-        float* o = out + (size_t)mc * F * S + r;
-        for (int k = 0; k < F; ++k) {
-            o[(size_t)k * S] = f[(size_t)r * F + k] + prev;
-            prev = f[(size_t)(r + S) * F + k];
+        const int nf = slot_frames<RAGGED>(tab, mc / (MC / M), F);
+        if (!RAGGED || nf > 0) {
+            const float* f = fr + (size_t)mc * L * F;
+            float prev = tail[e];
+            float* o = out + (size_t)mc * F * S + r;
+            for (int k = 0; k < nf; ++k) {
+                o[(size_t)k * S] = f[(size_t)r * F + k] + prev;
+                prev = f[(size_t)(r + S) * F + k];
+            }
+            tail[e] = prev;
         }
-        tail[e] = prev;
     }
     if (e < M * S) {
         const int m = e / S, i = e % S;
-        x[(size_t)m * xld + i] = x[(size_t)m * xld + (size_t)F * S + i];
+        const int nf = slot_frames<RAGGED>(tab, m, F);
+        if (!RAGGED || nf > 0) x[(size_t)m * xld + i] = x[(size_t)m * xld + (size_t)nf * S + i];
+    }
+}
+
+// ---- ragged steps: the caller's rows <-> the fixed buffers of a step, by the step table (all offsets in hops of S samples) ------------
+// x[m][(dst + h) * S ..] = chunk[m][(src + h) * S ..] for h < nh[m]; nh is clamped to what fits in either row.
+__global__ __launch_bounds__(256) void stream_load_ragged_kernel(const float* __restrict__ chunk, long long cld, int chunk_hops,
+                                                                 float* __restrict__ x, int xld, const int* __restrict__ tab, int S) {
+    const int m = blockIdx.y;
+    const int* t = tab + m * ST_TAB;
+    const int src = max(t[2], 0), dst = max(t[3], 0);
+    const int room = min(xld / S - dst, chunk_hops - src);
+    const long long n = (long long)min(max(t[1], 0), max(room, 0)) * S;
+    const float* c = chunk + (size_t)m * cld + (size_t)src * S;
+    float* o = x + (size_t)m * xld + (size_t)dst * S;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) o[i] = c[i];
+}
+
+// dst[m][c][(out + k) * S ..] = step output [M,C,F*S] frames k < nf[m]; clamped to the destination row.
+__global__ __launch_bounds__(256) void stream_store_ragged_kernel(const float* __restrict__ out, float* __restrict__ dst, long long dld,
+                                                                  const int* __restrict__ tab, int C, int S, int F) {
+    const int mc = blockIdx.y, m = mc / C;
+    const int off = max(tab[m * ST_TAB + 4], 0);
+    const long long n = min((long long)slot_frames<true>(tab, m, F), max(dld / S - off, 0LL)) * S;
+    const float* s = out + (size_t)mc * F * S;
+    float* o = dst + (size_t)mc * dld + (size_t)off * S;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) o[i] = s[i];
+}
+
+// ---- per-slot reset: the listed slots' part of every ring, their carried hop, overlap-add carry and position word ----------------------
+struct ResetArgs {
+    float* ring0;                       // first ring of this launch
+    float* x; float* tail; unsigned* pos;
+    long long off[ST_RST_RINGS];        // ring j of this launch starts at ring0 + off[j]
+    int R[ST_RST_RINGS];
+    int slot[ST_RST_SLOTS];
+    int nrings, H, xld, S, CS;          // CS = C * S; blockIdx.y == nrings: the small carries (only in the launch that has x != null)
+};
+
+__global__ __launch_bounds__(256) void stream_reset_slots_kernel(ResetArgs a) {
+    const int j = blockIdx.y, m = a.slot[blockIdx.z];
+    const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x, step = (size_t)gridDim.x * 256;
+    if (j < a.nrings) {
+        const size_t n4 = (size_t)a.H * a.R[j] / 4;         // H % 16 == 0 and the rings start 16-byte aligned
+        float4* p = reinterpret_cast<float4*>(a.ring0 + a.off[j] + (size_t)m * a.H * a.R[j]);
+        for (size_t i = t; i < n4; i += step) p[i] = float4{0.f, 0.f, 0.f, 0.f};
+    } else if (a.x) {
+        for (size_t i = t; i < (size_t)a.S; i += step) a.x[(size_t)m * a.xld + i] = 0.f;
+        for (size_t i = t; i < (size_t)a.CS; i += step) a.tail[(size_t)m * a.CS + i] = 0.f;
+        if (t == 0) a.pos[m] = 0u;
     }
 }
 
@@ -537,6 +629,68 @@ int ctn_stream_reset(void* state, size_t bytes, void* stream) {
     return CTN_OK;
 }
 
+}  // extern "C"
+
+namespace {
+
+// tab == null: one frame count and the state's own position word; else the ragged step (table + one position word per slot)
+int tcn_cln_launch(const void* packed, const int* dilation, int nblocks, float* y, void* state, const int* tab, unsigned* pos_m,
+                   int M, int B, int H, int P, int frames, int max_frames, void* stream) {
+    const size_t lds = ((size_t)(B + H) * ST_TC + ST_GRP * ST_TC) * sizeof(float);
+    const int tiles = ctn_cdiv(frames, ST_TC);
+    const size_t bf = block_floats(B, H, P);
+    float* ring = (float*)state + ST_HDR;
+    const unsigned* pos = tab ? pos_m : (const unsigned*)state;
+    // at most one tile per stream and room for >= 2 workgroups per stream in one round of the CUs: two row-split launches per block
+    const int cap = 256 / M;
+    if (frames <= ST_TC && cap >= 2) {
+        float* hraw = ring;
+        for (int j = 0; j < nblocks; ++j) hraw += (size_t)M * H * (size_t)ring_len(P, dilation[j], max_frames);
+        for (int j = 0; j < nblocks; ++j) {
+            RowsArgs a;
+            a.blk = (const float*)packed + (size_t)j * bf;
+            a.y = y; a.hraw = hraw; a.ring = ring; a.pos = pos; a.tab = tab;
+            a.R = (int)ring_len(P, dilation[j], max_frames); a.d = dilation[j];
+            a.B = B; a.H = H; a.P = P; a.F = frames;
+            a.nsplit = std::max(1, std::min(std::min(H / 16, 16), cap));
+            if (tab) hipLaunchKernelGGL(stream_rows_a_kernel<true>, dim3((unsigned)(M * a.nsplit)), dim3(ST_NT), lds, (hipStream_t)stream, a);
+            else hipLaunchKernelGGL(stream_rows_a_kernel<false>, dim3((unsigned)(M * a.nsplit)), dim3(ST_NT), lds, (hipStream_t)stream, a);
+            a.nsplit = std::max(1, std::min(std::min(B / 16, 16), cap));
+            if (tab) hipLaunchKernelGGL(stream_rows_b_kernel<true>, dim3((unsigned)(M * a.nsplit)), dim3(ST_NT), lds, (hipStream_t)stream, a);
+            else hipLaunchKernelGGL(stream_rows_b_kernel<false>, dim3((unsigned)(M * a.nsplit)), dim3(ST_NT), lds, (hipStream_t)stream, a);
+            ring += (size_t)M * H * a.R;
+        }
+    } else {
+        float* ring_prev = nullptr;
+        int Rp = 0;
+        for (int j = 0; j <= nblocks; ++j) {
+            StageArgs a;
+            a.prev = j >= 1 ? (const float*)packed + (size_t)(j - 1) * bf : nullptr;
+            a.cur = j < nblocks ? (const float*)packed + (size_t)j * bf : nullptr;
+            a.y = y;
+            a.ring_prev = ring_prev;
+            a.Rp = Rp;
+            a.dp = j >= 1 ? dilation[j - 1] : 0;
+            a.ring_cur = j < nblocks ? ring : nullptr;
+            a.Rc = j < nblocks ? (int)ring_len(P, dilation[j], max_frames) : 0;
+            a.pos = pos; a.tab = tab;
+            a.B = B; a.H = H; a.P = P; a.F = frames; a.tiles = tiles;
+            if (tab) hipLaunchKernelGGL(stream_stage_kernel<true>, dim3((unsigned)(M * tiles)), dim3(ST_NT), lds, (hipStream_t)stream, a);
+            else hipLaunchKernelGGL(stream_stage_kernel<false>, dim3((unsigned)(M * tiles)), dim3(ST_NT), lds, (hipStream_t)stream, a);
+            ring_prev = ring;
+            Rp = a.Rc;
+            ring += (size_t)M * H * a.Rc;
+        }
+    }
+    if (tab) hipLaunchKernelGGL(stream_advance_ragged_kernel, dim3((unsigned)ctn_cdiv(M, 256)), dim3(256), 0, (hipStream_t)stream, pos_m, tab, M, frames);
+    else hipLaunchKernelGGL(stream_advance_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (unsigned*)state, frames);
+    return CTN_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
 int ctn_stream_tcn_cln(const void* packed, const int* dilation, int nblocks, float* y, void* state, int M, int B, int H, int P,
                        int frames, int max_frames, void* stream) {
     CTN_REQUIRE(packed && dilation && y && state, "ctn_stream_tcn_cln: null pointer");
@@ -550,50 +704,7 @@ int ctn_stream_tcn_cln(const void* packed, const int* dilation, int nblocks, flo
         CTN_REQUIRE(dilation[j] >= 1 && dilation[j] <= (1 << 20), "ctn_stream_tcn_cln: bad dilation %d of block %d", dilation[j], j);
     const size_t lds = ((size_t)(B + H) * ST_TC + ST_GRP * ST_TC) * sizeof(float);
     CTN_REQUIRE(lds <= ST_MAX_LDS, "ctn_stream_tcn_cln: B + H = %d needs %zu bytes of LDS per tile (limit %zu)", B + H, lds, ST_MAX_LDS);
-    const int tiles = ctn_cdiv(frames, ST_TC);
-    const size_t bf = block_floats(B, H, P);
-    float* ring = (float*)state + ST_HDR;
-    // at most one tile per stream and room for >= 2 workgroups per stream in one round of the CUs: two row-split launches per block
-    const int cap = 256 / M;
-    if (frames <= ST_TC && cap >= 2) {
-        float* hraw = ring;
-        for (int j = 0; j < nblocks; ++j) hraw += (size_t)M * H * (size_t)ring_len(P, dilation[j], max_frames);
-        for (int j = 0; j < nblocks; ++j) {
-            RowsArgs a;
-            a.blk = (const float*)packed + (size_t)j * bf;
-            a.y = y; a.hraw = hraw; a.ring = ring; a.pos = (const unsigned*)state;
-            a.R = (int)ring_len(P, dilation[j], max_frames); a.d = dilation[j];
-            a.B = B; a.H = H; a.P = P; a.F = frames;
-            a.nsplit = std::max(1, std::min(std::min(H / 16, 16), cap));
-            hipLaunchKernelGGL(stream_rows_a_kernel, dim3((unsigned)(M * a.nsplit)), dim3(ST_NT), lds, (hipStream_t)stream, a);
-            a.nsplit = std::max(1, std::min(std::min(B / 16, 16), cap));
-            hipLaunchKernelGGL(stream_rows_b_kernel, dim3((unsigned)(M * a.nsplit)), dim3(ST_NT), lds, (hipStream_t)stream, a);
-            ring += (size_t)M * H * a.R;
-        }
-        hipLaunchKernelGGL(stream_advance_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (unsigned*)state, frames);
-        CTN_CHECK_LAUNCH("ctn_stream_tcn_cln");
-        return CTN_OK;
-    }
-    float* ring_prev = nullptr;
-    int Rp = 0;
-    for (int j = 0; j <= nblocks; ++j) {
-        StageArgs a;
-        a.prev = j >= 1 ? (const float*)packed + (size_t)(j - 1) * bf : nullptr;
-        a.cur = j < nblocks ? (const float*)packed + (size_t)j * bf : nullptr;
-        a.y = y;
-        a.ring_prev = ring_prev;
-        a.Rp = Rp;
-        a.dp = j >= 1 ? dilation[j - 1] : 0;
-        a.ring_cur = j < nblocks ? ring : nullptr;
-        a.Rc = j < nblocks ? (int)ring_len(P, dilation[j], max_frames) : 0;
-        a.pos = (const unsigned*)state;
-        a.B = B; a.H = H; a.P = P; a.F = frames; a.tiles = tiles;
-        hipLaunchKernelGGL(stream_stage_kernel, dim3((unsigned)(M * tiles)), dim3(ST_NT), lds, (hipStream_t)stream, a);
-        ring_prev = ring;
-        Rp = a.Rc;
-        ring += (size_t)M * H * a.Rc;
-    }
-    hipLaunchKernelGGL(stream_advance_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (unsigned*)state, frames);
+    tcn_cln_launch(packed, dilation, nblocks, y, state, nullptr, nullptr, M, B, H, P, frames, max_frames, stream);
     CTN_CHECK_LAUNCH("ctn_stream_tcn_cln");
     return CTN_OK;
 }
@@ -609,9 +720,9 @@ int ctn_stream_front(const float* x, int xld, const void* Up, const float* g0, c
     const size_t lds = ((size_t)(c16(L) * 16 + N + B) * ST_TC + ST_GRP * ST_TC) * sizeof(float);
     CTN_REQUIRE(lds <= ST_MAX_LDS, "ctn_stream_front: N + B = %d needs %zu bytes of LDS per tile (limit %zu)", N + B, lds, ST_MAX_LDS);
     FrontArgs a;
-    a.x = x; a.xld = xld; a.Up = (const float*)Up; a.g0 = g0; a.b0 = b0; a.Wbp = (const float*)Wbp; a.w = w; a.y = y;
+    a.x = x; a.xld = xld; a.Up = (const float*)Up; a.g0 = g0; a.b0 = b0; a.Wbp = (const float*)Wbp; a.w = w; a.y = y; a.tab = nullptr;
     a.N = N; a.L = L; a.B = B; a.F = frames; a.tiles = ctn_cdiv(frames, ST_TC);
-    hipLaunchKernelGGL(stream_front_kernel, dim3((unsigned)(M * a.tiles)), dim3(ST_NT), lds, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(stream_front_kernel<false>, dim3((unsigned)(M * a.tiles)), dim3(ST_NT), lds, (hipStream_t)stream, a);
     CTN_CHECK_LAUNCH("ctn_stream_front");
     return CTN_OK;
 }
@@ -629,12 +740,145 @@ int ctn_stream_back(const float* y, const float* w, const void* Wmp, const void*
     const size_t lds = ((size_t)B + (size_t)C * N + (size_t)C * c16(L) * 16) * ST_TC * sizeof(float);
     CTN_REQUIRE(lds <= ST_MAX_LDS, "ctn_stream_back: B + C*N = %d needs %zu bytes of LDS per tile (limit %zu)", B + C * N, lds, ST_MAX_LDS);
     BackArgs a;
-    a.y = y; a.w = w; a.Wmp = (const float*)Wmp; a.Vp = (const float*)Vp; a.fr = fr;
+    a.y = y; a.w = w; a.Wmp = (const float*)Wmp; a.Vp = (const float*)Vp; a.fr = fr; a.tab = nullptr;
     a.N = N; a.L = L; a.B = B; a.C = C; a.F = frames; a.tiles = ctn_cdiv(frames, ST_TC); a.softmax = softmax;
-    hipLaunchKernelGGL(stream_back_kernel, dim3((unsigned)(M * a.tiles)), dim3(ST_NT), lds, (hipStream_t)stream, a);
-    hipLaunchKernelGGL(stream_ola_kernel, dim3((unsigned)ctn_cdiv(M * C * (L / 2), 256)), dim3(256), 0, (hipStream_t)stream,
-                       (const float*)fr, out, ola_tail, x, xld, M, M * C, L, frames);
+    hipLaunchKernelGGL(stream_back_kernel<false>, dim3((unsigned)(M * a.tiles)), dim3(ST_NT), lds, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(stream_ola_kernel<false>, dim3((unsigned)ctn_cdiv(M * C * (L / 2), 256)), dim3(256), 0, (hipStream_t)stream,
+                       (const float*)fr, out, ola_tail, x, xld, M, M * C, L, frames, (const int*)nullptr);
     CTN_CHECK_LAUNCH("ctn_stream_back");
+    return CTN_OK;
+}
+
+// ---- ragged steps (a slot pool): the same launches driven by a per-slot step table ------------------------------------------------------
+int ctn_stream_load_ragged(const float* chunk, long long cld, int chunk_hops, float* x, int xld, const int* tab, int M, int S, int max_hops,
+                           void* stream) {
+    CTN_REQUIRE(chunk && x, "ctn_stream_load_ragged: null pointer");
+    CTN_REQUIRE(tab, "ctn_stream_load_ragged: null step table (tab)");
+    CTN_REQUIRE(M > 0 && M <= 65535, "ctn_stream_load_ragged: M must be 1..65535 (got %d)", M);
+    CTN_REQUIRE(S > 0, "ctn_stream_load_ragged: S must be positive (got %d)", S);
+    CTN_REQUIRE(xld >= S && xld % S == 0, "ctn_stream_load_ragged: xld must be a positive multiple of S (got %d)", xld);
+    CTN_REQUIRE(chunk_hops >= 1 && cld >= (long long)chunk_hops * S, "ctn_stream_load_ragged: chunk row stride (cld) shorter than chunk_hops hops");
+    CTN_REQUIRE(max_hops >= 1 && max_hops <= xld / S, "ctn_stream_load_ragged: max_hops must be 1..xld/S (got %d)", max_hops);
+    const unsigned gx = (unsigned)std::min(ctn_cdivll((long long)max_hops * S, 256), 64LL);
+    hipLaunchKernelGGL(stream_load_ragged_kernel, dim3(gx, (unsigned)M), dim3(256), 0, (hipStream_t)stream, chunk, cld, chunk_hops, x, xld, tab, S);
+    CTN_CHECK_LAUNCH("ctn_stream_load_ragged");
+    return CTN_OK;
+}
+
+int ctn_stream_store_ragged(const float* out, float* dst, long long dld, const int* tab, int M, int C, int S, int frames, void* stream) {
+    CTN_REQUIRE(out && dst, "ctn_stream_store_ragged: null pointer");
+    CTN_REQUIRE(tab, "ctn_stream_store_ragged: null step table (tab)");
+    CTN_REQUIRE(M > 0 && C > 0 && (long long)M * C <= 65535, "ctn_stream_store_ragged: M * C must be 1..65535");
+    CTN_REQUIRE(S > 0 && frames > 0, "ctn_stream_store_ragged: S and frames must be positive");
+    CTN_REQUIRE(dld >= S, "ctn_stream_store_ragged: destination row (dld) shorter than one hop");
+    const unsigned gx = (unsigned)std::min(ctn_cdivll((long long)frames * S, 256), 64LL);
+    hipLaunchKernelGGL(stream_store_ragged_kernel, dim3(gx, (unsigned)(M * C)), dim3(256), 0, (hipStream_t)stream, out, dst, dld, tab, C, S, frames);
+    CTN_CHECK_LAUNCH("ctn_stream_store_ragged");
+    return CTN_OK;
+}
+
+int ctn_stream_front_ragged(const float* x, int xld, const void* Up, const float* g0, const float* b0, const void* Wbp, float* w, float* y,
+                            const int* tab, int M, int N, int L, int B, int frames, void* stream) {
+    CTN_REQUIRE(x && Up && g0 && b0 && Wbp && w && y, "ctn_stream_front_ragged: null pointer");
+    CTN_REQUIRE(tab, "ctn_stream_front_ragged: null step table (tab)");
+    CTN_REQUIRE(M > 0 && frames > 0, "ctn_stream_front_ragged: M and frames must be positive (got %d, %d)", M, frames);
+    CTN_REQUIRE(N > 0 && B > 0 && N % 16 == 0 && B % 16 == 0, "ctn_stream_front_ragged: N and B must be positive multiples of 16 (got %d, %d)", N, B);
+    CTN_REQUIRE(L >= 4 && L % 4 == 0, "ctn_stream_front_ragged: L must be a multiple of 4 (got %d)", L);
+    CTN_REQUIRE((long long)xld >= (long long)(frames + 1) * (L / 2), "ctn_stream_front_ragged: sample buffer row shorter than frames + 1 hops");
+    CTN_REQUIRE(aligned16(Up) && aligned16(Wbp), "ctn_stream_front_ragged: packed weights must be 16-byte aligned");
+    const size_t lds = ((size_t)(c16(L) * 16 + N + B) * ST_TC + ST_GRP * ST_TC) * sizeof(float);
+    CTN_REQUIRE(lds <= ST_MAX_LDS, "ctn_stream_front_ragged: N + B = %d needs %zu bytes of LDS per tile (limit %zu)", N + B, lds, ST_MAX_LDS);
+    FrontArgs a;
+    a.x = x; a.xld = xld; a.Up = (const float*)Up; a.g0 = g0; a.b0 = b0; a.Wbp = (const float*)Wbp; a.w = w; a.y = y; a.tab = tab;
+    a.N = N; a.L = L; a.B = B; a.F = frames; a.tiles = ctn_cdiv(frames, ST_TC);
+    hipLaunchKernelGGL(stream_front_kernel<true>, dim3((unsigned)(M * a.tiles)), dim3(ST_NT), lds, (hipStream_t)stream, a);
+    CTN_CHECK_LAUNCH("ctn_stream_front_ragged");
+    return CTN_OK;
+}
+
+int ctn_stream_tcn_cln_ragged(const void* packed, const int* dilation, int nblocks, float* y, void* state, const int* tab, void* pos,
+                              int M, int B, int H, int P, int frames, int max_frames, void* stream) {
+    CTN_REQUIRE(packed && dilation && y && state, "ctn_stream_tcn_cln_ragged: null pointer");
+    CTN_REQUIRE(tab, "ctn_stream_tcn_cln_ragged: null step table (tab)");
+    CTN_REQUIRE(pos, "ctn_stream_tcn_cln_ragged: null position array (pos)");
+    CTN_REQUIRE(nblocks > 0 && M > 0, "ctn_stream_tcn_cln_ragged: bad sizes");
+    CTN_REQUIRE(B > 0 && H > 0 && B % 16 == 0 && H % 16 == 0, "ctn_stream_tcn_cln_ragged: B and H must be positive multiples of 16 (got %d, %d)", B, H);
+    CTN_REQUIRE(P >= 1 && P <= ST_MAXP, "ctn_stream_tcn_cln_ragged: kernel size must be 1..%d (got %d)", ST_MAXP, P);
+    CTN_REQUIRE(max_frames >= 1 && max_frames <= (1 << 20), "ctn_stream_tcn_cln_ragged: bad max_frames");
+    CTN_REQUIRE(frames >= 1 && frames <= max_frames, "ctn_stream_tcn_cln_ragged: frames must be 1..max_frames (got %d, max_frames %d)", frames, max_frames);
+    CTN_REQUIRE(aligned16(packed) && aligned16(state), "ctn_stream_tcn_cln_ragged: packed and state must be 16-byte aligned");
+    for (int j = 0; j < nblocks; ++j)
+        CTN_REQUIRE(dilation[j] >= 1 && dilation[j] <= (1 << 20), "ctn_stream_tcn_cln_ragged: bad dilation %d of block %d", dilation[j], j);
+    const size_t lds = ((size_t)(B + H) * ST_TC + ST_GRP * ST_TC) * sizeof(float);
+    CTN_REQUIRE(lds <= ST_MAX_LDS, "ctn_stream_tcn_cln_ragged: B + H = %d needs %zu bytes of LDS per tile (limit %zu)", B + H, lds, ST_MAX_LDS);
+    tcn_cln_launch(packed, dilation, nblocks, y, state, tab, (unsigned*)pos, M, B, H, P, frames, max_frames, stream);
+    CTN_CHECK_LAUNCH("ctn_stream_tcn_cln_ragged");
+    return CTN_OK;
+}
+
+int ctn_stream_back_ragged(const float* y, const float* w, const void* Wmp, const void* Vp, float* fr, float* out, float* ola_tail,
+                           float* x, int xld, const int* tab, int M, int N, int L, int B, int C, int frames, int softmax, void* stream) {
+    CTN_REQUIRE(y && w && Wmp && Vp && fr && out && ola_tail && x, "ctn_stream_back_ragged: null pointer");
+    CTN_REQUIRE(tab, "ctn_stream_back_ragged: null step table (tab)");
+    CTN_REQUIRE(M > 0 && frames > 0 && C > 0, "ctn_stream_back_ragged: M, C and frames must be positive (got %d, %d, %d)", M, C, frames);
+    CTN_REQUIRE(N > 0 && B > 0 && N % 16 == 0 && B % 16 == 0, "ctn_stream_back_ragged: N and B must be positive multiples of 16 (got %d, %d)", N, B);
+    CTN_REQUIRE(L >= 4 && L % 4 == 0, "ctn_stream_back_ragged: L must be a multiple of 4 (got %d)", L);
+    CTN_REQUIRE(softmax == 0 || softmax == 1, "ctn_stream_back_ragged: mask must be 0 (relu) or 1 (softmax)");
+    CTN_REQUIRE(C <= ST_MAXC, "ctn_stream_back_ragged: at most %d speakers", ST_MAXC);
+    CTN_REQUIRE((long long)xld >= (long long)(frames + 1) * (L / 2), "ctn_stream_back_ragged: sample buffer row shorter than frames + 1 hops");
+    CTN_REQUIRE(aligned16(Wmp) && aligned16(Vp), "ctn_stream_back_ragged: packed weights must be 16-byte aligned");
+    const size_t lds = ((size_t)B + (size_t)C * N + (size_t)C * c16(L) * 16) * ST_TC * sizeof(float);
+    CTN_REQUIRE(lds <= ST_MAX_LDS, "ctn_stream_back_ragged: B + C*N = %d needs %zu bytes of LDS per tile (limit %zu)", B + C * N, lds, ST_MAX_LDS);
+    BackArgs a;
+    a.y = y; a.w = w; a.Wmp = (const float*)Wmp; a.Vp = (const float*)Vp; a.fr = fr; a.tab = tab;
+    a.N = N; a.L = L; a.B = B; a.C = C; a.F = frames; a.tiles = ctn_cdiv(frames, ST_TC); a.softmax = softmax;
+    hipLaunchKernelGGL(stream_back_kernel<true>, dim3((unsigned)(M * a.tiles)), dim3(ST_NT), lds, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(stream_ola_kernel<true>, dim3((unsigned)ctn_cdiv(M * C * (L / 2), 256)), dim3(256), 0, (hipStream_t)stream,
+                       (const float*)fr, out, ola_tail, x, xld, M, M * C, L, frames, tab);
+    CTN_CHECK_LAUNCH("ctn_stream_back_ragged");
+    return CTN_OK;
+}
+
+int ctn_stream_reset_slots(void* state, float* x, int xld, float* ola_tail, void* pos, const int* slots, int nslots, int M, int H, int P,
+                           const int* dilation, int nblocks, int max_frames, int C, int L, void* stream) {
+    CTN_REQUIRE(state && x && ola_tail && pos && slots && dilation, "ctn_stream_reset_slots: null pointer");
+    CTN_REQUIRE(M > 0 && nblocks > 0 && C > 0, "ctn_stream_reset_slots: bad sizes");
+    CTN_REQUIRE(nslots >= 1 && nslots <= M, "ctn_stream_reset_slots: nslots must be 1..M (got %d, M %d)", nslots, M);
+    CTN_REQUIRE(H > 0 && H % 16 == 0, "ctn_stream_reset_slots: H must be a positive multiple of 16 (got %d)", H);
+    CTN_REQUIRE(P >= 1 && P <= ST_MAXP, "ctn_stream_reset_slots: kernel size must be 1..%d (got %d)", ST_MAXP, P);
+    CTN_REQUIRE(max_frames >= 1 && max_frames <= (1 << 20), "ctn_stream_reset_slots: bad max_frames");
+    CTN_REQUIRE(L >= 4 && L % 4 == 0 && xld >= L / 2, "ctn_stream_reset_slots: L must be a multiple of 4 and xld at least one hop");
+    CTN_REQUIRE(aligned16(state), "ctn_stream_reset_slots: state must be 16-byte aligned");
+    for (int j = 0; j < nblocks; ++j)
+        CTN_REQUIRE(dilation[j] >= 1 && dilation[j] <= (1 << 20), "ctn_stream_reset_slots: bad dilation %d of block %d", dilation[j], j);
+    for (int i = 0; i < nslots; ++i)
+        CTN_REQUIRE(slots[i] >= 0 && slots[i] < M, "ctn_stream_reset_slots: slot %d (entry %d of the list) is outside 0..%d", slots[i], i, M - 1);
+    ResetArgs a;
+    a.x = nullptr; a.tail = ola_tail; a.pos = (unsigned*)pos;
+    a.H = H; a.xld = xld; a.S = L / 2; a.CS = C * (L / 2);
+    float* ring = (float*)state + ST_HDR;
+    for (int j0 = 0; j0 < nblocks; j0 += ST_RST_RINGS) {
+        a.ring0 = ring;
+        a.nrings = std::min(ST_RST_RINGS, nblocks - j0);
+        long long off = 0, rmax = 0;
+        for (int j = 0; j < a.nrings; ++j) {
+            a.off[j] = off;
+            a.R[j] = (int)ring_len(P, dilation[j0 + j], max_frames);
+            rmax = std::max(rmax, (long long)a.R[j]);
+            off += (long long)M * H * a.R[j];
+        }
+        ring += off;
+        const bool last = j0 + ST_RST_RINGS >= nblocks;     // the small carries ride on the last group of rings
+        a.x = last ? x : nullptr;
+        const unsigned gx = (unsigned)std::min(ctn_cdivll((long long)H * rmax / 4, 256 * 4), 64LL);
+        for (int s0 = 0; s0 < nslots; s0 += ST_RST_SLOTS) {
+            const int ns = std::min(ST_RST_SLOTS, nslots - s0);
+            for (int i = 0; i < ns; ++i) a.slot[i] = slots[s0 + i];
+            hipLaunchKernelGGL(stream_reset_slots_kernel, dim3(std::max(gx, 1u), (unsigned)(a.nrings + (last ? 1 : 0)), (unsigned)ns), dim3(256),
+                               0, (hipStream_t)stream, a);
+        }
+    }
+    CTN_CHECK_LAUNCH("ctn_stream_reset_slots");
     return CTN_OK;
 }
 

@@ -145,29 +145,10 @@ class StreamingSeparator:
         return out
 
 
-class FusedStreamingSeparator:
-    """Low-latency, many-stream form of `StreamingSeparator`: same contract, one fused launch per block boundary.
+class _FusedBase:
+    """What FusedStreamingSeparator and FusedStreamPool share: the checks, the packed weights and the fixed buffers of a chunk step."""
 
-        s = FusedStreamingSeparator(model, batch=32, max_chunk_frames=16)
-        out = s.push(chunk)             # chunk [M, n*S] -> [M, C, n*S] (the very first push: [M, C, (n-1)*S], and needs n*S >= L)
-        tail = s.flush()                # [M, C, L-S]
-    Concatenating every `out` and `tail` reproduces ``model(full_mixture)``.
-
-    A chunk costs nblocks + 5 launches (csrc/ctn_stream.hip) on unpadded [M, Ch, frames] activations: front end, one stage per
-    block boundary with the depthwise history in per-block ring buffers, back end with the overlap-add carry; chunks of at most 16
-    frames run each block as two launches spread over up to 16 workgroups per stream (2 * nblocks + 4 launches).  The arithmetic is
-    frame-local and in a fixed order (exact fp32 MFMA chains; it does not follow `set_gemm_arith`), so the output samples are
-    BITWISE independent of how the signal was cut into chunks and of the other streams of the batch.  Every push after the first
-    accepts any n >= 1; a chunk of more than `max_chunk_frames` frames is split inside `push`.
-
-    The weights are packed into the kernels' fragment order at construction: call `refresh()` after the model's parameters changed.
-    ``graph=True`` replays the chunk step of a given length as one HIP graph from its second occurrence on (same kernels: same bits).
-
-    Out of scope: per-stream reset and streams joining mid-flight (the first chunk has one frame fewer, for every stream of the batch
-    at once), gLN / non-causal models (ValueError), training (no autograd).
-    """
-
-    def __init__(self, model, batch=1, max_chunk_frames=64, graph=False):
+    def _setup(self, model, batch, max_chunk_frames, graph):
         import ctypes
         if not model.causal or model.norm_type != "cLN":
             raise ValueError("streaming needs the causal cLN variant (gLN statistics span the whole utterance)")
@@ -203,7 +184,6 @@ class FusedStreamingSeparator:
         self.ola_tail = torch.zeros((M, m.C, self.L - S), device=dev)
         self._graphs = {}            # frames -> graph
         self._seen = set()           # frames of the steady-state steps run eagerly so far
-        self.first = True
         self.refresh()
 
     @torch.no_grad()
@@ -228,6 +208,53 @@ class FusedStreamingSeparator:
         lib.call("ctn_stream_pack_gemm", Wb.data_ptr(), m.B, m.N, self.Wbp.data_ptr(), st)
         lib.call("ctn_stream_pack_gemm", Wm.data_ptr(), m.C * m.N, m.B, self.Wmp.data_ptr(), st)
         lib.call("ctn_stream_pack_gemm", V.data_ptr(), m.L, m.N, self.Vp.data_ptr(), st)
+
+    def _run(self, frames):
+        if not self.use_graph:
+            return self._step(frames).clone()
+        if frames not in self._graphs:
+            if frames not in self._seen:                 # one eager step of this length first (module load, allocator)
+                self._seen.add(frames)
+                return self._step(frames).clone()
+            torch.cuda.synchronize(self.dev)
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g):                    # records, does not run: the state is untouched until the replay
+                self._step(frames)
+            self._graphs[frames] = g
+        self._graphs[frames].replay()
+        return self._out_view(frames).clone()
+
+    def _out_view(self, frames):
+        m = self.m
+        return self.out[: self.M * m.C * frames * self.S].view(self.M, m.C, frames * self.S)
+
+
+class FusedStreamingSeparator(_FusedBase):
+    """Low-latency, many-stream form of `StreamingSeparator`: same contract, one fused launch per block boundary.
+
+        s = FusedStreamingSeparator(model, batch=32, max_chunk_frames=16)
+        out = s.push(chunk)             # chunk [M, n*S] -> [M, C, n*S] (the very first push: [M, C, (n-1)*S], and needs n*S >= L)
+        tail = s.flush()                # [M, C, L-S]
+    Concatenating every `out` and `tail` reproduces ``model(full_mixture)``.
+
+    A chunk costs nblocks + 5 launches (csrc/ctn_stream.hip) on unpadded [M, Ch, frames] activations: front end, one stage per
+    block boundary with the depthwise history in per-block ring buffers, back end with the overlap-add carry; chunks of at most 16
+    frames run each block as two launches spread over up to 16 workgroups per stream (2 * nblocks + 4 launches).  The arithmetic is
+    frame-local and in a fixed order (exact fp32 MFMA chains; it does not follow `set_gemm_arith`), so the output samples are
+    BITWISE independent of how the signal was cut into chunks and of the other streams of the batch.  Every push after the first
+    accepts any n >= 1; a chunk of more than `max_chunk_frames` frames is split inside `push`.
+
+    The weights are packed into the kernels' fragment order at construction: call `refresh()` after the model's parameters changed.
+    ``graph=True`` replays the chunk step of a given length as one HIP graph from its second occurrence on (same kernels: same bits).
+
+    Every stream of the batch starts on the same push and delivers the same number of hops; streams that join, leave, reset or
+    deliver different amounts per push are served by `FusedStreamPool` (below; same kernels, same bits).  Out of scope: gLN /
+    non-causal models (ValueError), training (no autograd).
+    """
+
+    def __init__(self, model, batch=1, max_chunk_frames=64, graph=False):
+        self._setup(model, batch, max_chunk_frames, graph)
+        self.first = True
 
     def reset(self):
         """Back to the start of a stream (every stream of the batch); packed weights and captured graphs stay valid."""
@@ -257,25 +284,6 @@ class FusedStreamingSeparator:
                 outs.append(self._run(frames))
         return outs[0] if len(outs) == 1 else torch.cat(outs, dim=2)
 
-    def _run(self, frames):
-        if not self.use_graph:
-            return self._step(frames).clone()
-        if frames not in self._graphs:
-            if frames not in self._seen:                 # one eager step of this length first (module load, allocator)
-                self._seen.add(frames)
-                return self._step(frames).clone()
-            torch.cuda.synchronize(self.dev)
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):                    # records, does not run: the state is untouched until the replay
-                self._step(frames)
-            self._graphs[frames] = g
-        self._graphs[frames].replay()
-        return self._out_view(frames).clone()
-
-    def _out_view(self, frames):
-        m = self.m
-        return self.out[: self.M * m.C * frames * self.S].view(self.M, m.C, frames * self.S)
-
     def _step(self, frames):
         """`frames` frames of the sample buffer through the network; every carry updated in place.  Returns a view of the output buffer."""
         m, M, st = self.m, self.M, ops._stream()
@@ -294,3 +302,175 @@ class FusedStreamingSeparator:
         out = self.ola_tail.clone()
         self.ola_tail.zero_()
         return out
+
+
+TAB = 8      # ints per slot of a step table (CTN_STREAM_TAB in include/ctn_hip.h): nf, nh, src, dst, out, 3 unused
+
+
+def plan_steps(hops, fresh, F):
+    """Cut one ragged push into steps of at most `F` frames per slot (pure host code, no GPU).
+
+    hops[m]: hops slot m delivers with this push; fresh[m]: its stream starts with this push (its first hop only primes the carry:
+    h hops hold h - 1 frames, and they land at offset 0 of the sample buffer instead of behind the carried hop).
+    -> list of (frames, max_hops, rows): rows[m] = [nf, nh, src, dst, out, 0, 0, 0] in hops (the table of include/ctn_hip.h),
+    frames = max nf, max_hops = max nh.  Step i holds every slot's i-th piece; slots that ran out have nf = nh = 0.
+    """
+    M = len(hops)
+    left, new = [int(h) for h in hops], [bool(f) for f in fresh]
+    src, out = [0] * M, [0] * M
+    steps = []
+    while any(left):
+        rows = []
+        for m in range(M):
+            if new[m] and left[m]:
+                nh = min(left[m], F + 1)
+                nf, dst = nh - 1, 0
+                new[m] = False
+            else:
+                nh = nf = min(left[m], F)
+                dst = 1
+            rows.append([nf, nh, src[m], dst, out[m], 0, 0, 0])
+            left[m] -= nh
+            src[m] += nh
+            out[m] += nf
+        steps.append((max(r[0] for r in rows), max(r[1] for r in rows), rows))
+    return steps
+
+
+class FusedStreamPool(_FusedBase):
+    """`slots` independent streams on the kernels of `FusedStreamingSeparator`, each with a life of its own.
+
+        pool = FusedStreamPool(model, slots=32, max_chunk_frames=16)
+        s = pool.open()                         # a free slot (or pool.open(slot)), reset on the device
+        out, lengths = pool.push(chunk, hops)   # chunk [slots, n*S]; slot m delivers hops[m] hops = the first hops[m]*S samples of its row
+        tail = pool.close(s)                    # [C, L-S]: the slot's last overlap-add samples; the slot is free again
+    `hops` may be any mix of values: 0 (nothing this time), 1 on a slot's very first push (its first hop only primes the carry),
+    more than `max_chunk_frames` (split inside `push`).  out is [slots, C, max(lengths)] with zeros beyond lengths[m] = hops[m]*S
+    (minus S on the push that carries the slot's first hop).  out[m, :, :lengths[m]] of every push of a slot and its `close()` tail,
+    concatenated, are BITWISE what `FusedStreamingSeparator(model, batch=1)` gives for that stream alone, whatever the other slots do.
+
+    A step is a per-slot table (`plan_steps`) uploaded to a fixed device tensor, then the ragged forms of the same launches
+    (include/ctn_hip.h, "ragged steps"): one copy of the chunk rows into the sample buffer, front, stack, back, one copy into the
+    padded output rows: two launches and one small upload more than the class, none of them per slot.  ``graph=True`` replays
+    front + stack + back as one HIP graph per maximum frame count from its second occurrence on; the per-slot counts live in the
+    table, never in a graph; `open` / `close` and both copies stay outside the graphs.
+    """
+
+    def __init__(self, model, slots=1, max_chunk_frames=16, graph=False):
+        self._setup(model, slots, max_chunk_frames, graph)
+        dev, M = self.dev, self.M
+        self.pos = torch.zeros(M, dtype=torch.int32, device=dev)
+        self.tab = torch.zeros((M, TAB), dtype=torch.int32, device=dev)
+        self.is_open, self.fresh = [False] * M, [False] * M
+        # pinned staging for the table upload: a ring, each entry with the event of its last copy (never rewritten before that completed)
+        self._stage, self._stage_i = [], 0
+        if dev.type == "cuda":
+            self._stage = [[torch.zeros((M, TAB), dtype=torch.int32).pin_memory(), None] for _ in range(4)]
+
+    def open(self, slot=None):
+        """Take a free slot (the lowest, or `slot`) and reset it on the device; returns its index."""
+        import ctypes
+        if slot is None:
+            free = [i for i, o in enumerate(self.is_open) if not o]
+            if not free:
+                raise ValueError("no free slot (all %d are open)" % self.M)
+            slot = free[0]
+        slot = int(slot)
+        if not 0 <= slot < self.M:
+            raise ValueError("slot %d is outside 0..%d" % (slot, self.M - 1))
+        if self.is_open[slot]:
+            raise ValueError("slot %d is already open" % slot)
+        m = self.m
+        lib.call("ctn_stream_reset_slots", self.state.data_ptr(), self.x.data_ptr(), self.xld, self.ola_tail.data_ptr(), self.pos.data_ptr(),
+                 (ctypes.c_int * 1)(slot), 1, self.M, m.H, m.P, self.dil, self.nb, self.F, m.C, m.L, ops._stream())
+        self.is_open[slot], self.fresh[slot] = True, True
+        return slot
+
+    @torch.no_grad()
+    def close(self, slot):
+        """The slot's last L-S output samples [C, L-S] (their second overlap-add tap never arrives); the slot is free again."""
+        slot = int(slot)
+        if not 0 <= slot < self.M or not self.is_open[slot]:
+            raise ValueError("slot %r is not open" % (slot,))
+        tail = self.ola_tail[slot].clone()
+        self.is_open[slot] = self.fresh[slot] = False
+        return tail
+
+    def _upload(self, rows):
+        """The step table -> the fixed device tensor, through pinned staging on the current stream."""
+        if not self._stage:
+            self.tab.copy_(torch.tensor(rows, dtype=torch.int32))
+            return
+        buf = self._stage[self._stage_i]
+        self._stage_i = (self._stage_i + 1) % len(self._stage)
+        if buf[1] is not None:
+            buf[1].synchronize()                 # its previous copy has completed (long ago, as a rule)
+        else:
+            buf[1] = torch.cuda.Event()
+        buf[0].copy_(torch.tensor(rows, dtype=torch.int32))
+        self.tab.copy_(buf[0], non_blocking=True)
+        buf[1].record()
+
+    @torch.no_grad()
+    def push(self, chunk, hops):
+        S, M, m = self.S, self.M, self.m
+        hops = [int(h) for h in hops]
+        if len(hops) != M:
+            raise ValueError("hops must have one entry per slot (%d), got %d" % (M, len(hops)))
+        if chunk.dim() != 2 or chunk.shape[0] != M:
+            raise ValueError("chunk must be [%d, n*%d]" % (M, S))
+        for i, h in enumerate(hops):
+            if h < 0:
+                raise ValueError("hops[%d] is negative" % i)
+            if h and not self.is_open[i]:
+                raise ValueError("slot %d is not open but hops[%d] = %d" % (i, i, h))
+            if h * S > chunk.shape[1]:
+                raise ValueError("chunk rows hold %d samples, slot %d needs hops[%d]*%d = %d" % (chunk.shape[1], i, i, S, h * S))
+        steps = plan_steps(hops, self.fresh, self.F)
+        lengths = [(h - (1 if f and h else 0)) * S for h, f in zip(hops, self.fresh)]
+        for i, h in enumerate(hops):
+            if h:
+                self.fresh[i] = False
+        out = torch.zeros((M, m.C, max(lengths)), device=self.dev)
+        if not steps:
+            return out, lengths
+        chunk = chunk.to(self.dev, torch.float32)
+        if chunk.stride(1) != 1 or (M > 1 and chunk.stride(0) < chunk.shape[1]):
+            chunk = chunk.contiguous()
+        cld = chunk.stride(0) if M > 1 else chunk.shape[1]       # rows of a wider tensor are read in place
+        for frames, max_hops, rows in steps:
+            st = ops._stream()
+            self._upload(rows)
+            lib.call("ctn_stream_load_ragged", chunk.data_ptr(), cld, chunk.shape[1] // S, self.x.data_ptr(), self.xld,
+                     self.tab.data_ptr(), M, S, max_hops, st)
+            if frames:                           # 0: only first hops that prime their carries
+                self._run_step(frames)
+                lib.call("ctn_stream_store_ragged", self.out.data_ptr(), out.data_ptr(), out.shape[2], self.tab.data_ptr(),
+                         M, m.C, S, frames, st)
+        return out, lengths
+
+    def _run_step(self, frames):
+        if not self.use_graph:
+            return self._step(frames)
+        if frames not in self._graphs:
+            if frames not in self._seen:                 # one eager step of this maximum first (module load, allocator)
+                self._seen.add(frames)
+                return self._step(frames)
+            torch.cuda.synchronize(self.dev)
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g):                    # records, does not run; the table is read at replay, not baked in
+                self._step(frames)
+            self._graphs[frames] = g
+        self._graphs[frames].replay()
+
+    def _step(self, frames):
+        """One ragged step of at most `frames` frames per slot, by the table in `self.tab`; every carry updated in place."""
+        m, M, st = self.m, self.M, ops._stream()
+        g0, b0, tab = self._small[4], self._small[5], self.tab.data_ptr()
+        lib.call("ctn_stream_front_ragged", self.x.data_ptr(), self.xld, self.Up.data_ptr(), g0.data_ptr(), b0.data_ptr(),
+                 self.Wbp.data_ptr(), self.w.data_ptr(), self.y.data_ptr(), tab, M, m.N, m.L, m.B, frames, st)
+        lib.call("ctn_stream_tcn_cln_ragged", self.packed.data_ptr(), self.dil, self.nb, self.y.data_ptr(), self.state.data_ptr(),
+                 tab, self.pos.data_ptr(), M, m.B, m.H, m.P, frames, self.F, st)
+        lib.call("ctn_stream_back_ragged", self.y.data_ptr(), self.w.data_ptr(), self.Wmp.data_ptr(), self.Vp.data_ptr(),
+                 self.fr.data_ptr(), self.out.data_ptr(), self.ola_tail.data_ptr(), self.x.data_ptr(), self.xld, tab,
+                 M, m.N, m.L, m.B, m.C, frames, self.soft, st)

@@ -540,6 +540,40 @@ int ctn_stream_front(const float* x, int xld, const void* Up, const float* g0, c
 int ctn_stream_back(const float* y, const float* w, const void* Wmp, const void* Vp, float* fr, float* out, float* ola_tail,
                     float* x, int xld, int M, int N, int L, int B, int C, int frames, int softmax, void* stream);
 
+/* ---- ragged steps of the same kernels: a slot pool whose streams join, leave and deliver different amounts (csrc/ctn_stream.hip) ----
+ * One step serves M slots; slot m computes nf[m] frames, 0 <= nf[m] <= frames.  `frames` (the maximum over the slots) sizes the grid
+ * and is the leading dimension of w, y, fr and the step output, exactly as in the calls above; a workgroup whose tile starts at or
+ * beyond nf[m] returns before its first load.  The same device functions run the same per-element FMA chains and cLN sums: a frame's
+ * values are bitwise those of the calls above.  Two caller-owned device arrays replace the scalar count and the state's position word:
+ *   tab  int [M][CTN_STREAM_TAB], rewritten by the caller before every step; offsets in hops of S = L/2 samples:
+ *        [0] nf   frames to compute                      [1] nh   hops to load (nf, or nf + 1 for a stream that starts with this step)
+ *        [2] src  first hop in the caller's chunk row    [3] dst  where they land in the sample buffer row: 0 for a stream that
+ *        [4] out  first hop in the caller's output row        starts with this step (its first frame begins at its sample 0), else 1
+ *        [5..7] unused.  The kernels clamp nf to 0..frames and the copies to their rows: a bad table cannot write out of bounds.
+ *   pos  unsigned [M]: ring position per slot (the position word in `state`'s header is unused by these calls).
+ * `state` is laid out and sized as above (ctn_stream_state_bytes).  A step is  load -> front -> tcn_cln -> back -> store  on `stream`:
+ * 2 more launches than the calls above, none of them per slot.
+ *   ctn_stream_load_ragged: x[m][(dst+h)*S ..] = chunk[m][(src+h)*S ..], h < nh[m]; chunk: M rows of chunk_hops hops, row stride cld
+ *     samples; max_hops >= every nh (grid size).
+ *   ctn_stream_front_ragged / _tcn_cln_ragged / _back_ragged: as ctn_stream_front / _tcn_cln / _back with nf[m] valid frames for
+ *     slot m; tcn_cln advances pos[m] by nf[m]; back writes the step output out [M,C,frames*S] (nf[m]*S samples valid per row), and a
+ *     slot with nf[m] = 0 keeps its ola_tail and its carried hop.
+ *   ctn_stream_store_ragged: dst[m][c][(out+k)*S ..] = step output frames k < nf[m]; dst [M,C,dld] (the caller's padded rows).
+ *   ctn_stream_reset_slots: the `nslots` slots listed in `slots` (HOST array) back to the start of a stream: their part of every
+ *     ring, their carried hop x[m][0..S), ola_tail [M,C,S] row and pos[m] are zeroed, in one launch per 64 blocks x 32 slots. */
+#define CTN_STREAM_TAB 8
+int ctn_stream_load_ragged(const float* chunk, long long cld, int chunk_hops, float* x, int xld, const int* tab, int M, int S, int max_hops,
+                           void* stream);
+int ctn_stream_front_ragged(const float* x, int xld, const void* Up, const float* g0, const float* b0, const void* Wbp, float* w, float* y,
+                            const int* tab, int M, int N, int L, int B, int frames, void* stream);
+int ctn_stream_tcn_cln_ragged(const void* packed, const int* dilation, int nblocks, float* y, void* state, const int* tab, void* pos,
+                              int M, int B, int H, int P, int frames, int max_frames, void* stream);
+int ctn_stream_back_ragged(const float* y, const float* w, const void* Wmp, const void* Vp, float* fr, float* out, float* ola_tail,
+                           float* x, int xld, const int* tab, int M, int N, int L, int B, int C, int frames, int softmax, void* stream);
+int ctn_stream_store_ragged(const float* out, float* dst, long long dld, const int* tab, int M, int C, int S, int frames, void* stream);
+int ctn_stream_reset_slots(void* state, float* x, int xld, float* ola_tail, void* pos, const int* slots, int nslots, int M, int H, int P,
+                           const int* dilation, int nblocks, int max_frames, int C, int L, void* stream);
+
 /* ---- on-device dynamic mixing: a resident single-speaker corpus and the minibatch sampler (csrc/ctn_dynmix.hip) ---------
  * replaces the offline mixture set of the reference's recipe: the list tools/create_txt_file_like_wsj0.py draws (two
  * speakers, snr_1 = randrange(1, 250) / 100 dB, snr_2 = -snr_1) and tools/matlab-code/create_wav_2speakers.m builds
