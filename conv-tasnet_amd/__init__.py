@@ -11,5 +11,7 @@ from .ops import gemm_arith, gemm_arithmetic, set_gemm_arith  # noqa: F401
 from .streaming import StreamingSeparator, FusedStreamingSeparator, FusedStreamPool  # noqa: F401
 from .dynmix import DeviceCorpus, DynamicMixLoader  # noqa: F401
 from . import resample  # noqa: F401
+from . import rir  # noqa: F401
+from .rir import RirBank  # noqa: F401
 
 __version__ = "0.1.0"

@@ -2,14 +2,12 @@
 // Contract: include/ctn_hip.h ("on-device dynamic mixing"); executable restatement: tests/dynmix_oracle.py.
 // Every float32 operation of the gather is ONE rounding in a stated order (no contraction into fused multiply-adds, IEEE
 // division), so the minibatch is a bitwise function of the plan and the corpus.
-#include "ctn_common.h"
+#include "ctn_dynmix_common.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
-constexpr int DM_NT = 256;          // threads per workgroup of every kernel here
-constexpr int DM_CHUNK = 4 * DM_NT; // samples per workgroup of the chunked gather (4 consecutive samples per thread)
 constexpr int DM_WIDE_NT = 1024;    // threads of the one-workgroup-per-mixture gather
 
 // ---- levels ------------------------------------------------------------------------------------------------------------
@@ -36,26 +34,6 @@ __global__ __launch_bounds__(DM_NT) void dynmix_levels_kernel(const float* __res
 }
 
 // ---- plan --------------------------------------------------------------------------------------------------------------
-struct Philox4 { unsigned w[4]; };
-
-__device__ __forceinline__ Philox4 philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const unsigned long long p0 = (unsigned long long)0xD2511F53u * c0;
-        const unsigned long long p1 = (unsigned long long)0xCD9E8D57u * c2;
-        const unsigned n0 = (unsigned)(p1 >> 32) ^ c1 ^ k0;
-        const unsigned n1 = (unsigned)p1;
-        const unsigned n2 = (unsigned)(p0 >> 32) ^ c3 ^ k1;
-        const unsigned n3 = (unsigned)p0;
-        c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-    return Philox4{{c0, c1, c2, c3}};
-}
-
-__device__ __forceinline__ unsigned below(unsigned r, unsigned long long n) { return (unsigned)(((unsigned long long)r * n) >> 32); }
-
 // One workgroup; thread b draws mixture b (and b + NT, ...).  Every thread reads the step word before the barrier, thread 0
 // advances it behind the barrier.
 __global__ __launch_bounds__(DM_NT) void dynmix_plan_kernel(const int* __restrict__ spk_ptr, const int* __restrict__ utt_ids, int S,
@@ -246,20 +224,6 @@ __device__ __forceinline__ void range_write(const Rows<C>& r, float scale, int t
         }
     }
 }
-
-template <int NT>
-__device__ __forceinline__ float block_max(float v, float* scratch) {
-    v = wave_max(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) scratch[threadIdx.x >> 6] = v;
-    __syncthreads();
-    float r = scratch[0];
-#pragma unroll
-    for (int w = 1; w < NT / 64; ++w) r = fmaxf(r, scratch[w]);
-    return r;
-}
-
-__device__ __forceinline__ float peak_scale(float a) { return a > 0.0f ? __fdiv_rn(0.9f, a) : 1.0f; }
 
 #define DM_GATHER_ARGS                                                                                                          \
     const float *__restrict__ corpus, const long long *__restrict__ offsets, const long long *__restrict__ lens, int U,         \

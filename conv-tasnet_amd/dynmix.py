@@ -14,6 +14,9 @@ rescaled to a peak of 0.9 (tools/matlab-code/create_wav_2speakers.m:111-112).  A
 Files at another rate: `from_manifest(..., resample=True)` / `from_arrays(..., sample_rates=, target_rate=)` resample them on
 the device (resample.py, csrc/ctn_resample.hip) before the levels are taken.  Speed perturbation: `speeds=range(95, 106)`
 replays every source at a drawn integer percent of its speed, resampled on the device by 100 / pct each step.
+Noise and reverberation (csrc/ctn_dynmix_aug.hip): `noise=` a second DeviceCorpus of noise recordings, one segment of it under
+every mixture at an SNR drawn from `snr_db`; `rirs=` a rir.RirBank, every source convolved with a drawn room impulse response,
+the training targets being its direct path and early reflections.  Both compose with `speeds`.
 
 Differences from the MATLAB tool, on purpose: the level is the plain RMS of the whole utterance (not ITU-T P.56 active
 level) and the peak rescale is per drawn segment (not per whole utterance).
@@ -42,6 +45,39 @@ def inverse_rms(meansq):
     live = meansq > 0
     out[live] = 1.0 / np.sqrt(meansq[live])
     return out.astype(np.float32)
+
+
+def snr_range(snr_db):
+    """(lo, hi) in dB -> the integer tenths of a dB (lo10, hi10): at most 1024 values, lo10 <= hi10."""
+    try:
+        lo, hi = snr_db
+        lo10, hi10 = int(round(float(lo) * 10.0)), int(round(float(hi) * 10.0))
+    except (TypeError, ValueError, OverflowError):
+        raise ValueError("snr_db must be (lo, hi) in dB, got %r" % (snr_db,))
+    if lo10 > hi10:
+        raise ValueError("empty SNR range %r" % (snr_db,))
+    if hi10 - lo10 + 1 > 1024:
+        raise ValueError("the SNR range %r holds %d tenths of a dB, at most 1024 are supported" % (snr_db, hi10 - lo10 + 1))
+    return lo10, hi10
+
+
+def snr_table(lo10, hi10):
+    """wn[i] = 10^(-(lo10 + i) / 200), i = 0 .. hi10 - lo10: the noise gain at unit RMS for an SNR of (lo10 + i) / 10 dB relative
+    to the sources' 0-dB reference level; float32 rounded from float64 on the host."""
+    return np.array([10.0 ** (-(lo10 + i) / 200.0) for i in range(hi10 - lo10 + 1)], dtype=np.float64).astype(np.float32)
+
+
+def noise_table(lens, meansq, segment_len):
+    """noise_ids int32: the noise utterances of at least segment_len samples that are not silent; none is a ValueError."""
+    lens, meansq = np.asarray(lens, dtype=np.int64), np.asarray(meansq, dtype=np.float64)
+    if int(segment_len) <= 0:
+        raise ValueError("segment_len must be positive, got %d" % segment_len)
+    ids = np.nonzero((lens >= int(segment_len)) & (meansq > 0))[0].astype(np.int32)
+    if len(ids) == 0:
+        raise ValueError("no noise utterance of at least %d samples that is not silent" % segment_len)
+    if int(lens[ids].max()) - int(segment_len) + 1 >= 1 << 32:
+        raise ValueError("a noise utterance of %d samples is too long for a 32-bit start draw" % int(lens[ids].max()))
+    return ids
 
 
 def build_tables(lens, meansq, speakers, segment_len, num_speakers=2):
@@ -195,10 +231,18 @@ class DynamicMixLoader:
     gather_mode: the form of ctn_dynmix_gather (None: GATHER_MODE); both give the same bits.
     speeds: None, or integer percents in [50, 200]: every source is replayed at a drawn percent of its speed (one more Philox
     block per source; speaker, utterance and level draws are those of speeds=None), resampled on the device into a segment
-    buffer the gather then mixes.  Eligible utterances hold ceil(segment_len * max(speeds) / 100) samples."""
+    buffer the gather then mixes.  Eligible utterances hold ceil(segment_len * max(speeds) / 100) samples.
+    rirs: None, or a rir.RirBank: every source is convolved with a drawn response (one more Philox block per source); `mixture`
+    sums the reverberant sources, `sources` holds their early-taps targets (the bank's early_ms), time-aligned with the dry
+    source.  The reverberation sees the drawn segment only, not the utterance before it.
+    noise: None, or a DeviceCorpus of noise recordings (labels ignored): one segment under every mixture (one more Philox block
+    per mixture) at an SNR drawn uniformly from the tenths of a dB in snr_db = (lo, hi), relative to the sources' 0-dB reference
+    level (unit RMS, before the plan's +-q).  The peak rescale to 0.9 covers the noisy mixture and the targets.
+    With either option the mix is ctn_dynmix_gather_aug, which has the chunked form only (gather_mode plays no part).
+    With rirs=None and noise=None the launches and the bits are those of a loader without these arguments."""
 
     def __init__(self, corpus, batch_size, segment_len, num_speakers=2, steps_per_epoch=1000, seed=0, rank=None,
-                 reshuffle=True, gather_mode=None, speeds=None):
+                 reshuffle=True, gather_mode=None, speeds=None, rirs=None, noise=None, snr_db=(-6, 3)):
         if rank is None:
             from . import parallel
             rank = torch.distributed.get_rank() if parallel.world_size() > 1 else parallel.env_world()[1]
@@ -236,6 +280,9 @@ class DynamicMixLoader:
             self._pct = torch.tensor(self.speeds, dtype=torch.int32, device=dev)
             self._plan_pct = torch.zeros(self.B, self.C, dtype=torch.int32, device=dev)
             self._seg = _SegmentBuffer(self.B, self.C, self.T, dev)
+        self._aug = None
+        if rirs is not None or noise is not None:
+            self._aug = _Augment(self.B, self.C, self.T, dev, rirs, noise, snr_db)
 
     # Solver: loader.dataset.set_epoch(epoch).  A property, not an attribute: `self.dataset = self` is a reference cycle, and a
     # dropped loader's device buffers would then stay allocated until the cyclic collector happens to run
@@ -256,26 +303,44 @@ class DynamicMixLoader:
         for t, shape, name in ((mixture, (B, T), "mixture"), (sources, (B, C, T), "sources")):
             if tuple(t.shape) != shape or t.dtype != torch.float32 or not t.is_contiguous() or t.device != self.device:
                 raise ValueError("%s must be a contiguous float32 %s tensor on %s" % (name, shape, self.device))
-        c = self.corpus
+        c, aug = self.corpus, self._aug
         stream = torch.cuda.current_stream(self.device).cuda_stream
+        if aug is not None:
+            aug.plan(self.seed, self.epoch, self.rank, self._step, stream)          # reads the step word, leaves it alone
         if self.speeds is not None:
             lib.call("ctn_dynmix_plan_speed", _ptr(self._spk_ptr), _ptr(self._utt_ids), len(self.tables["spk_ptr"]) - 1,
                      _ptr(c.lens), _ptr(c.inv_rms), _ptr(c.w), _ptr(self._pct), len(self.speeds), self.seed, self.epoch, self.rank,
                      _ptr(self._step), B, C, T, _ptr(self._plan_utt), _ptr(self._plan_start), _ptr(self._plan_q), _ptr(self._gain),
                      _ptr(self._plan_pct), stream)
+        else:
+            lib.call("ctn_dynmix_plan", _ptr(self._spk_ptr), _ptr(self._utt_ids), len(self.tables["spk_ptr"]) - 1, _ptr(c.lens),
+                     _ptr(c.inv_rms), _ptr(c.w), self.seed, self.epoch, self.rank, _ptr(self._step), B, C, T,
+                     _ptr(self._plan_utt), _ptr(self._plan_start), _ptr(self._plan_q), _ptr(self._gain), stream)
+        if aug is not None:                  # speed_segments -> reverb -> gather_aug (include/ctn_hip.h: the pipeline of one step)
+            if self.speeds is not None:
+                self._seg.segments(c, self._banks, self._plan_utt, self._plan_start, self._plan_pct, stream)
+                rows = self._seg.rows()
+            else:
+                rows = _Rows(c.corpus, c.offsets, c.lens, c.num_utterances, self._plan_utt, self._plan_start)
+            aug.mix(rows, self._gain, mixture, sources, self._peak, self._ws, stream)
+        elif self.speeds is not None:
             self._seg.mix(c, self._banks, self._plan_utt, self._plan_start, self._plan_pct, self._gain, mixture, sources,
                           self._peak, self._ws, self.gather_mode, stream)
-            if lengths is not None:
-                lengths.copy_(self._lengths)
-            return
-        lib.call("ctn_dynmix_plan", _ptr(self._spk_ptr), _ptr(self._utt_ids), len(self.tables["spk_ptr"]) - 1, _ptr(c.lens),
-                 _ptr(c.inv_rms), _ptr(c.w), self.seed, self.epoch, self.rank, _ptr(self._step), B, C, T,
-                 _ptr(self._plan_utt), _ptr(self._plan_start), _ptr(self._plan_q), _ptr(self._gain), stream)
-        lib.call("ctn_dynmix_gather", _ptr(c.corpus), _ptr(c.offsets), _ptr(c.lens), c.num_utterances, _ptr(self._plan_utt),
-                 _ptr(self._plan_start), _ptr(self._gain), B, C, T, _ptr(mixture), _ptr(sources), _ptr(self._peak),
-                 _ptr(self._ws), self._ws.numel(), self.gather_mode, stream)
+        else:
+            lib.call("ctn_dynmix_gather", _ptr(c.corpus), _ptr(c.offsets), _ptr(c.lens), c.num_utterances, _ptr(self._plan_utt),
+                     _ptr(self._plan_start), _ptr(self._gain), B, C, T, _ptr(mixture), _ptr(sources), _ptr(self._peak),
+                     _ptr(self._ws), self._ws.numel(), self.gather_mode, stream)
         if lengths is not None:
             lengths.copy_(self._lengths)
+
+    def last_aug_plan(self):
+        """Copies of the last minibatch's extra draws: (plan_rir [B,C] i32, noise_utt [B] i32, noise_start [B] i64, snr10 [B] i32
+        in tenths of a dB, ngain [B] f32); the RIR element is None without rirs, the four noise elements without noise."""
+        a = self._aug
+        rir = a.plan_rir.clone() if a is not None and a.rirs is not None else None
+        if a is None or a.noise is None:
+            return rir, None, None, None, None
+        return rir, a.noise_utt.clone(), a.noise_start.clone(), a.snr10.clone(), a.ngain.clone()
 
     def last_plan(self):
         """Copies of the last minibatch's plan: (plan_utt [B,C] i32, plan_start [B,C] i64, plan_q [B,C] i32, gain [B,C] f32),
@@ -308,13 +373,128 @@ class _SegmentBuffer:
         self.lens = torch.full((B * C,), T, dtype=torch.int64, device=device)
         self.start = torch.zeros(B, C, dtype=torch.int64, device=device)
 
-    def mix(self, corpus, banks, plan_utt, plan_start, plan_pct, gain, mixture, sources, peak, ws, mode, stream):
+    def rows(self):
+        return _Rows(self.seg, self.offsets, self.lens, self.B * self.C, self.seg_utt, self.start)
+
+    def segments(self, corpus, banks, plan_utt, plan_start, plan_pct, stream):
         B, C, T = self.B, self.C, self.T
         lib.call("ctn_dynmix_speed_segments", _ptr(corpus.corpus), _ptr(corpus.offsets), _ptr(corpus.lens), corpus.num_utterances,
                  _ptr(plan_utt), _ptr(plan_start), _ptr(plan_pct), B, C, T, _ptr(banks.banks), banks.banks.numel(), _ptr(banks.table),
                  banks.span_cap, banks.bank_cap, _ptr(self.seg), _ptr(self.seg_utt), stream)
+
+    def mix(self, corpus, banks, plan_utt, plan_start, plan_pct, gain, mixture, sources, peak, ws, mode, stream):
+        B, C, T = self.B, self.C, self.T
+        self.segments(corpus, banks, plan_utt, plan_start, plan_pct, stream)
         lib.call("ctn_dynmix_gather", _ptr(self.seg), _ptr(self.offsets), _ptr(self.lens), B * C, _ptr(self.seg_utt),
                  _ptr(self.start), _ptr(gain), B, C, T, _ptr(mixture), _ptr(sources), _ptr(peak), _ptr(ws), ws.numel(), mode, stream)
+
+
+class _Rows:
+    """B * C rows in the "corpus + plan" form the gather and the reverberation read: row i is T samples of `data` from
+    offsets[utt[i]] + start[i] on."""
+
+    def __init__(self, data, offsets, lens, num_utterances, utt, start):
+        self.data, self.offsets, self.lens, self.U, self.utt, self.start = data, offsets, lens, int(num_utterances), utt, start
+
+
+class _Augment:
+    """The buffers and launches of the noise and reverberation stages of one loader (all allocated here, none per step)."""
+
+    def __init__(self, B, C, T, device, rirs, noise, snr_db):
+        self.B, self.C, self.T, self.rirs, self.noise = B, C, T, rirs, noise
+        if rirs is not None:
+            if rirs.device != device:
+                raise ValueError("the RIR bank is on %s, the corpus on %s" % (rirs.device, device))
+            self.plan_rir = torch.zeros(B, C, dtype=torch.int32, device=device)
+            self.wet = _SegmentBuffer(B, C, T, device)                       # seg = wet rows, seg_utt = out_utt
+            self.tgt = None if rirs.full_targets else torch.zeros(B * C * T, dtype=torch.float32, device=device)
+        if noise is not None:
+            if noise.device != device:
+                raise ValueError("the noise corpus is on %s, the corpus on %s" % (noise.device, device))
+            self.lo10, self.hi10 = snr_range(snr_db)
+            self.noise_ids_host = noise_table(noise.lens_host, noise.meansq, T)
+            self.noise_ids = torch.from_numpy(self.noise_ids_host).to(device)
+            self.wn = torch.from_numpy(snr_table(self.lo10, self.hi10)).to(device)
+            self.noise_utt = torch.zeros(B, dtype=torch.int32, device=device)
+            self.noise_start = torch.zeros(B, dtype=torch.int64, device=device)
+            self.snr10 = torch.zeros(B, dtype=torch.int32, device=device)
+            self.ngain = torch.zeros(B, dtype=torch.float32, device=device)
+
+    @classmethod
+    def of_plan(cls, B, C, T, device, rirs, plan_rir, noise, noise_utt, noise_start, ngain):
+        """The stages over a caller-written plan: nothing is drawn, so no tables."""
+        self = cls.__new__(cls)
+        self.B, self.C, self.T, self.rirs, self.noise = B, C, T, rirs, noise
+        if rirs is not None:
+            self.plan_rir = plan_rir.to(device=device, dtype=torch.int32).contiguous()
+            self.wet = _SegmentBuffer(B, C, T, device)
+            self.tgt = None if rirs.full_targets else torch.zeros(B * C * T, dtype=torch.float32, device=device)
+        if noise is not None:
+            self.noise_utt = noise_utt.to(device=device, dtype=torch.int32).contiguous()
+            self.noise_start = noise_start.to(device=device, dtype=torch.int64).contiguous()
+            self.ngain = ngain.to(device=device, dtype=torch.float32).contiguous()
+        return self
+
+    def plan(self, seed, epoch, rank, step, stream):
+        r, n = self.rirs, self.noise
+        if n is None:
+            lib.call("ctn_dynmix_plan_aug", seed, epoch, rank, _ptr(step), self.B, self.C, self.T, r.num_responses, _ptr(self.plan_rir),
+                     0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, stream)
+            return
+        lib.call("ctn_dynmix_plan_aug", seed, epoch, rank, _ptr(step), self.B, self.C, self.T, r.num_responses if r is not None else 0,
+                 _ptr(self.plan_rir) if r is not None else 0, _ptr(self.noise_ids), len(self.noise_ids_host), _ptr(n.lens),
+                 n.num_utterances, _ptr(n.inv_rms), _ptr(self.wn), self.hi10 - self.lo10 + 1, self.lo10, _ptr(self.noise_utt),
+                 _ptr(self.noise_start), _ptr(self.snr10), _ptr(self.ngain), stream)
+
+    def mix(self, rows, gain, mixture, sources, peak, ws, stream):
+        B, C, T, r, n = self.B, self.C, self.T, self.rirs, self.noise
+        tgt = None
+        if r is not None:
+            tgt = self.tgt
+            lib.call("ctn_dynmix_reverb", _ptr(rows.data), _ptr(rows.offsets), _ptr(rows.lens), rows.U, _ptr(rows.utt), _ptr(rows.start),
+                     B * C, T, _ptr(r.bank), r.bank.numel(), _ptr(r.offsets), _ptr(r.lens), _ptr(r.direct), _ptr(r.early),
+                     r.num_responses, _ptr(self.plan_rir), _ptr(self.wet.seg), _ptr(tgt), _ptr(self.wet.seg_utt), stream)
+            rows = self.wet.rows()
+        if n is None:
+            noise_args = (0, 0, 0, 0, 0, 0, 0)
+        else:
+            noise_args = (_ptr(n.corpus), _ptr(n.offsets), _ptr(n.lens), n.num_utterances, _ptr(self.noise_utt), _ptr(self.noise_start),
+                          _ptr(self.ngain))
+        lib.call("ctn_dynmix_gather_aug", _ptr(rows.data), _ptr(rows.offsets), _ptr(rows.lens), rows.U, _ptr(rows.utt), _ptr(rows.start),
+                 _ptr(gain), B, C, T, _ptr(tgt), *noise_args, _ptr(mixture), _ptr(sources), _ptr(peak), _ptr(ws), ws.numel(), stream)
+
+
+def gather_aug(corpus, plan_utt, plan_start, gain, segment_len, rirs=None, plan_rir=None, noise=None, noise_utt=None,
+               noise_start=None, ngain=None, plan_pct=None):
+    """The minibatch of a caller-written plan with reverberation and noise: gather()'s arguments, plus rirs (a rir.RirBank) with
+    plan_rir [B,C] int32, and noise (a DeviceCorpus) with noise_utt [B] int32, noise_start [B] int64, ngain [B] float32 (the noise
+    gain itself, nothing is drawn or looked up) -> (mixture [B,T], sources [B,C,T], peak [B]).  Either half may be left out."""
+    dev = corpus.device
+    B, C = plan_utt.shape
+    T = int(segment_len)
+    if (rirs is None) != (plan_rir is None):
+        raise ValueError("rirs and plan_rir go together")
+    if (noise is None) != (noise_utt is None) or (noise is None) != (noise_start is None) or (noise is None) != (ngain is None):
+        raise ValueError("noise, noise_utt, noise_start and ngain go together")
+    plan_utt = plan_utt.to(device=dev, dtype=torch.int32).contiguous()
+    plan_start = plan_start.to(device=dev, dtype=torch.int64).contiguous()
+    gain = gain.to(device=dev, dtype=torch.float32).contiguous()
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    aug = _Augment.of_plan(B, C, T, dev, rirs, plan_rir, noise, noise_utt, noise_start, ngain)
+    rows = _Rows(corpus.corpus, corpus.offsets, corpus.lens, corpus.num_utterances, plan_utt, plan_start)
+    if plan_pct is not None:
+        from . import resample as _rs
+        pcts = sorted(set(int(p) for p in plan_pct.reshape(-1).tolist()))
+        banks = _rs.speed_banks([p for p in pcts if _rs.PCT_LO <= p <= _rs.PCT_HI] or [100], dev)
+        seg = _SegmentBuffer(B, C, T, dev)
+        seg.segments(corpus, banks, plan_utt, plan_start, plan_pct.to(device=dev, dtype=torch.int32).contiguous(), stream)
+        rows = seg.rows()
+    mixture = torch.empty(B, T, dtype=torch.float32, device=dev)
+    sources = torch.empty(B, C, T, dtype=torch.float32, device=dev)
+    peak = torch.empty(B, dtype=torch.float32, device=dev)
+    ws = torch.empty(max(1, lib.ctn_dynmix_gather_workspace(B, T)), dtype=torch.uint8, device=dev)
+    aug.mix(rows, gain, mixture, sources, peak, ws, stream)
+    return mixture, sources, peak
 
 
 def gather(corpus, plan_utt, plan_start, gain, segment_len, mode=None, plan_pct=None):

@@ -103,7 +103,44 @@ def build_parser():
                     "integer percent of its speed in [LO, HI], e.g. 95:105 (resampled on the device); validation never perturbs")
     ap.add_argument("--corpus-rate", default="8000", choices=["8000", "auto"], help="rate of the --dynamic-mix files: 8000 (any "
                     "other rate is an error), or auto: files at other rates are resampled to 8 kHz on the device")
+    ap.add_argument("--checkpoint", action="store_true", help="save checkpoint_models/epochN.pth.tar under --save-folder every epoch")
+    ap.add_argument("--continue-from", default="", metavar="CHECKPOINT", help="resume from this checkpoint and run --epochs + 1 "
+                    "more epochs (the Solver's arithmetic); a dynamic-mixing run sees the minibatches of the uninterrupted one")
+    ap.add_argument("--noise", default=None, metavar="NOISE_JSON", help="--dynamic-mix only: add a segment of a noise recording "
+                    "from this manifest (the --dynamic-mix layout; labels ignored) under every mixture, at a drawn SNR")
+    ap.add_argument("--snr", default="-6:3", metavar="LO:HI", help="range of the drawn SNR in dB (tenths of a dB are drawn "
+                    "uniformly), relative to a source at its 0-dB reference level; with --noise")
+    ap.add_argument("--rirs", default=None, metavar="RIR_JSON | synthetic:N", help="--dynamic-mix only: convolve every source with "
+                    "a room impulse response drawn from this manifest of [wav_path, n_samples] at 8 kHz, or from N synthetic ones")
+    ap.add_argument("--rir-early-ms", default="50", metavar="MS | full", help="the training targets keep the direct path and the "
+                    "reflections of this many milliseconds behind it; full: the reverberant sources.  --noise, --snr, --rirs and "
+                    "--rir-early-ms also reach the --dynamic-mix-cv loader (the same banks, reshuffle=False: a fixed validation set)")
     return ap
+
+
+def parse_snr(text):
+    """'LO:HI' in dB -> (lo, hi) floats (train.py --snr; '=' joins a negative LO to the flag: --snr=-3:6)."""
+    try:
+        lo, hi = (float(v) for v in str(text).split(":"))
+    except ValueError:
+        raise ValueError("SNR range must be LO:HI in dB, got %r" % (text,))
+    return lo, hi
+
+
+def _augmentations(a, device):
+    """(rirs, noise, snr_db) of --rirs / --noise / --snr / --rir-early-ms for the dynamic-mixing loaders."""
+    from .dynmix import DeviceCorpus
+    from . import rir as _rir
+    rirs = noise = None
+    if a.rirs:
+        early = None if a.rir_early_ms == "full" else float(a.rir_early_ms)
+        if a.rirs.startswith("synthetic:"):
+            rirs = _rir.RirBank.from_arrays(_rir.synthetic_bank(int(a.rirs.split(":", 1)[1]), 8000, seed=a.seed), device, 8000, early)
+        else:
+            rirs = _rir.RirBank.from_manifest(a.rirs, 8000, device, early_ms=early)
+    if a.noise:
+        noise = DeviceCorpus.from_manifest(a.noise, 8000, device, resample=a.corpus_rate == "auto")
+    return rirs, noise, parse_snr(a.snr)
 
 
 TINY = dict(N=64, L=20, B=32, H=64, P=3, X=2, R=2, C=2)
@@ -114,21 +151,26 @@ def main(argv=None):
     a = build_parser().parse_args(argv)
     if a.speed_perturb and not a.dynamic_mix:
         raise SystemExit("--speed-perturb applies to --dynamic-mix only")
+    if (a.noise or a.rirs) and not a.dynamic_mix:
+        raise SystemExit("--noise and --rirs apply to --dynamic-mix only")
     world, rank, device = parallel.init_distributed()
     tr = cv = None
     if a.dynamic_mix or a.dynamic_mix_cv:
         from .dynmix import DeviceCorpus, DynamicMixLoader
         auto = a.corpus_rate == "auto"
+        rirs, noise, snr_db = _augmentations(a, device) if a.dynamic_mix else (None, None, (-6, 3))
         if a.dynamic_mix:
             speeds = None
             if a.speed_perturb:
                 from .resample import parse_speed_range
                 speeds = parse_speed_range(a.speed_perturb)
             tr = DynamicMixLoader(DeviceCorpus.from_manifest(a.dynamic_mix, 8000, device, resample=auto), a.batch_size, a.segment_len,
-                                  steps_per_epoch=a.steps_per_epoch, seed=a.seed, rank=rank, speeds=speeds)
+                                  steps_per_epoch=a.steps_per_epoch, seed=a.seed, rank=rank, speeds=speeds, rirs=rirs, noise=noise,
+                                  snr_db=snr_db)
         if a.dynamic_mix_cv:
             cv = DynamicMixLoader(DeviceCorpus.from_manifest(a.dynamic_mix_cv, 8000, device, resample=auto), a.batch_size,
-                                  a.segment_len, steps_per_epoch=a.cv_steps, seed=a.seed + 1, rank=rank, reshuffle=False)
+                                  a.segment_len, steps_per_epoch=a.cv_steps, seed=a.seed + 1, rank=rank, reshuffle=False, rirs=rirs,
+                                  noise=noise, snr_db=snr_db)
     if a.data_dir:
         from .data import AudioDataLoader, AudioDataset
         if tr is None:
@@ -142,7 +184,8 @@ def main(argv=None):
     if cv is None:
         cv = SyntheticLoader(1, a.batch_size, first_utt=10 ** 6, rank=rank, world=world)
     return train({'tr_loader': tr, 'cv_loader': cv}, a.epochs, a.model_path, save_folder=a.save_folder, lr=a.lr,
-                 optimizer_type=a.optimizer, momentum=a.momentum, l2=a.l2, config=TINY if a.tiny else None)
+                 optimizer_type=a.optimizer, momentum=a.momentum, l2=a.l2, config=TINY if a.tiny else None,
+                 enable_checkpoint=int(a.checkpoint), continue_from=a.continue_from)
 
 
 if __name__ == "__main__":

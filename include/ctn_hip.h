@@ -676,6 +676,78 @@ int ctn_dynmix_speed_segments(const float* corpus, const long long* offsets, con
                               long long bank_floats, const int* bank_tab, int span_cap, int bank_cap, float* seg, int* seg_utt,
                               void* stream);
 
+/* ---- noisy and reverberant dynamic mixing (csrc/ctn_dynmix_aug.hip) ------------------------------------------------------
+ * what WHAM!, WHAMR! and noisy LibriMix add to wsj0-2mix, drawn on the device: a noise recording at a drawn SNR under every
+ * mixture, every source convolved with a drawn room impulse response (RIR).  The conventions are those of the two sections
+ * above: draws are pure functions of (seed, rank, epoch, step, b) through Philox4x32-10 under the same key, no pow or sqrt on the
+ * device, every fp32 operation is one rounding in a stated order, outputs are a bitwise function of plan and data whatever the
+ * launch geometry, and an entry that breaks its tables is never read and is flagged.
+ * RIR bank: R responses back to back in one flat fp32 buffer of bank_floats floats; rir_offsets [R] int64, rir_lens [R],
+ *   rir_direct [R], rir_early [R] int32.  Response r has n_r = rir_lens[r] taps, 1 <= n_r <= 8192; d_r = rir_direct[r] in
+ *   [0, n_r) is its direct path (the host takes the first index of max |h|); rir_early[r] in [0, n_r] is the number of leading
+ *   taps that make the training target (direct path and early reflections; n_r: the fully reverberant source).  The host may
+ *   divide every response by sqrt(sum h^2) in fp64 before the one rounding to fp32 (rir.RirBank(normalize=True)): the
+ *   reverberant source then keeps ROUGHLY the level the plan gave it -- a deliberate approximation, in the spirit of "plain RMS,
+ *   not P.56": exact for white sources only, and the early-taps target is below it by the energy of the late taps.
+ * Noise: an ordinary corpus (noise, noise_offsets, noise_lens [Un], noise_inv_rms [Un]; speaker labels play no part).
+ *   noise_ids [Nn] int32: the eligible noise utterances, lens[v] >= seg_len and meansq[v] > 0.  SNR in integer tenths of a dB,
+ *   lo10 .. lo10 + nsnr - 1 (1 <= nsnr <= 1024), table wn [nsnr] fp32, wn[i] = 10^(-(lo10 + i) / 200) rounded from fp64 on the
+ *   host.  The SNR is relative to the sources' 0-dB REFERENCE level -- unit RMS, before the +-q hundredths of a dB the plan gives
+ *   each source -- not to the level of the louder source or of their sum.
+ *   ctn_dynmix_plan_aug: the extra draws of one minibatch; launched BEFORE ctn_dynmix_plan / ctn_dynmix_plan_speed on the same
+ *     stream, it reads *step and leaves it alone (the kernel behind it advances it).  Same key; the blocks at counters
+ *     (c, ..) and (c + 256, ..) are not touched, so speaker, utterance, start, level and speed draws of a seed are what they are
+ *     without this call.  New blocks:
+ *         RIR of source c of mixture b     counter = (c + 512, b, step, epoch)   plan_rir[b,c] = (uint64(word 0) * R) >> 32
+ *         noise of mixture b               counter = (768, b, step, epoch)
+ *             word 0  noise_utt[b] = v = noise_ids[(uint64(word 0) * Nn) >> 32]
+ *             word 1  noise_start[b]: uniform in [0, noise_lens[v] - seg_len]
+ *             word 2  k = (uint64(word 2) * nsnr) >> 32,  snr10[b] = lo10 + k
+ *         ngain[b] = wn[k] * noise_inv_rms[v]: one fp32 multiply.
+ *     plan_rir [B,C] int32; noise_utt, snr10 [B] int32, noise_start [B] int64, ngain [B] fp32.  Either half is skipped when its
+ *     pointers are null (plan_rir; the eight noise arrays together); both null is an error.  A noise_ids entry outside [0, Un)
+ *     or shorter than seg_len gives noise_utt[b] = -1, ngain[b] = 0: an entry the mix flags.
+ *   ctn_dynmix_reverb: rows i in [0, N), N = B * C, of the "corpus + plan" form ctn_dynmix_gather reads.  The dry segment of row
+ *     i is x_i[t] = corpus[offsets[u] + plan_start[i] + t] for t in [0, T), u = plan_utt[i], and reads as ZERO outside [0, T):
+ *     the reverberation sees the drawn segment only, not the utterance before it -- the same thing as convolving a cut segment,
+ *     and what lets the stage run over the speed-perturbed segment buffer as a corpus (seg, offsets = arange * T, lens = T,
+ *     plan_utt = seg_utt, plan_start = 0).  With r = plan_rir[i], n = rir_lens[r], d = rir_direct[r], h = bank + rir_offsets[r]:
+ *         wet[i,t] = sum_{j=0}^{n-1} h[j] * x_i[t + d - j]
+ *         acc = +0; for j ascending: acc = acc + h[j] * x: the product and the add are one fp32 rounding each
+ *         tgt[i,t] = acc after the taps j < rir_early[r]                    (so tgt == wet where rir_early[r] == n)
+ *     wet, tgt [N,T] fp32 at unit gain (16-byte aligned); tgt may be null (then only wet is computed).  The shift by d keeps the
+ *     target time-aligned with the dry source.  Taps whose sample lies outside [0, T) may be skipped or added as zeros: acc
+ *     starts at +0 and can never become -0, so both give the same bits.  A row is written as zeros with out_utt[i] = -1 when its
+ *     plan entry is outside its utterance (u outside [0, U) -- a segment the speed stage flagged has u = -1 --, start < 0,
+ *     start + T > lens[u]), plan_rir[i] is outside [0, R), or the response's table entry is outside the bank buffer or breaks
+ *     1 <= n <= 8192, 0 <= d < n, 0 <= early <= n; every other row gives out_utt[i] = i.  One workgroup of 256 threads per 1024
+ *     consecutive outputs of a row, 4 per thread in registers; taps are staged in LDS 1024 at a time beside their input span.
+ *   ctn_dynmix_gather_aug: ctn_dynmix_gather (chunked form, two launches, ctn_dynmix_gather_workspace() bytes) with targets that
+ *     differ from the mixture components and a noise row.  tgt_corpus: same layout and plan as corpus (null: the targets are the
+ *     mixture components); noise null: no noise, and no noise term in the sum.
+ *         r_c[t] = gain[b,c] * corpus[..]        g_c[t] = gain[b,c] * tgt_corpus[..]        (g_c = r_c when tgt_corpus is null)
+ *         n[t]   = ngain[b] * noise[noise_offsets[v] + noise_start[b] + t]                  v = noise_utt[b]
+ *         mix[t] = (((r_0[t] + r_1[t]) + r_2[t] ...) + n[t])
+ *         a      = max_t max(|mix[t]|, |g_0[t]|, ..., |g_{C-1}[t]|)          scale = a > 0 ? 0.9f / a : 1.0f
+ *         mixture[b,t] = scale * mix[t];  sources[b,c,t] = scale * g_c[t];  peak[b] = a
+ *     A source entry outside its utterance (as ctn_dynmix_gather defines it; both r_c and g_c) or a noise entry outside its
+ *     utterance (v outside [0, Un), start < 0, start + T > noise_lens[v]) is never read, counts as silence and gives peak[b] = -1.
+ *   The pipeline of one step: plan_aug -> plan | plan_speed -> speed_segments (with speeds) -> reverb over the corpus or over seg
+ *     (with RIRs) -> gather_aug over (wet, tgt) as corpora of B * C utterances of T samples, plan_utt = out_utt, plan_start = 0. */
+int ctn_dynmix_plan_aug(long long seed, int epoch, int rank, const unsigned* step, int B, int C, int seg_len, int R, int* plan_rir,
+                        const int* noise_ids, int Nn, const long long* noise_lens, long long Un, const float* noise_inv_rms,
+                        const float* wn, int nsnr, int lo10, int* noise_utt, long long* noise_start, int* snr10, float* ngain,
+                        void* stream);
+int ctn_dynmix_reverb(const float* corpus, const long long* offsets, const long long* lens, long long U, const int* plan_utt,
+                      const long long* plan_start, int N, int T, const float* bank, long long bank_floats, const long long* rir_offsets,
+                      const int* rir_lens, const int* rir_direct, const int* rir_early, int R, const int* plan_rir, float* wet, float* tgt,
+                      int* out_utt, void* stream);
+int ctn_dynmix_gather_aug(const float* corpus, const long long* offsets, const long long* lens, long long U, const int* plan_utt,
+                          const long long* plan_start, const float* gain, int B, int C, int T, const float* tgt_corpus,
+                          const float* noise, const long long* noise_offsets, const long long* noise_lens, long long Un,
+                          const int* noise_utt, const long long* noise_start, const float* ngain, float* mixture, float* sources,
+                          float* peak, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
