@@ -8,9 +8,10 @@ from .conv_tasnet import ConvTasNet  # noqa: F401
 from .pit_criterion import cal_loss, cal_si_snr_with_pit  # noqa: F401
 from .utils import overlap_and_add, remove_pad  # noqa: F401
 from .ops import gemm_arith, gemm_arithmetic, set_gemm_arith  # noqa: F401
-from .streaming import StreamingSeparator, FusedStreamingSeparator, FusedStreamPool  # noqa: F401
+from .streaming import StreamingSeparator, FusedStreamingSeparator, FusedStreamPool, ResamplingStreamPool  # noqa: F401
 from .dynmix import DeviceCorpus, DynamicMixLoader  # noqa: F401
 from . import resample  # noqa: F401
+from .resample import StreamResampler  # noqa: F401
 from . import rir  # noqa: F401
 from .rir import RirBank  # noqa: F401
 

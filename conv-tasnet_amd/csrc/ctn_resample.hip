@@ -151,6 +151,103 @@ __global__ __launch_bounds__(RS_NT) void dynmix_speed_segments_kernel(const floa
     rs_chunk(xrow, lens[u], st, up, down, banks + boff, W, bank_lds, span, rs_lds, yrow, t0, n);
 }
 
+// ---- streaming rows: the same sum over a signal that arrives push by push -------------------------------------------------
+// tab row (int64 [RS_STAB]): n_old, n_new, t0, n_out, src, dst, parity, spare (include/ctn_hip.h, "streaming sinc resampling").
+// Global sample g of a row: zero for g < 0 and g >= n_old + n_new, the chunk for g >= n_old, else the row's history of the last
+// 2W - 1 samples.  hist [2][rows][2W - 1]: a push reads the half `parity` and writes the other one, so the workgroup that moves
+// the history on never races with those that still read it.
+constexpr int RS_STAB = 8;
+
+// a row's table entry against the two buffers and the contract; a row with n_new = n_out = 0 has nothing to check
+__host__ __device__ inline bool rs_stream_row_ok(const long long* e, int up, int down, int W, long long chunk_samples, long long y_samples) {
+    const long long n_old = e[0], n_new = e[1], t0 = e[2], n_out = e[3], src = e[4], dst = e[5], par = e[6];
+    if (n_new == 0 && n_out == 0) return true;
+    if (n_old < 0 || n_new < 0 || t0 < 0 || n_out < 0 || src < 0 || dst < 0 || (par != 0 && par != 1)) return false;
+    if (n_old > RS_MAX_LEN || n_new > RS_MAX_LEN || n_old + n_new > RS_MAX_LEN) return false;
+    if (n_new > chunk_samples || src > chunk_samples - n_new || n_out > y_samples || dst > y_samples - n_out) return false;
+    if (t0 > RS_MAX_LEN || n_out > RS_MAX_LEN || t0 + n_out > ((n_old + n_new) * up + down - 1) / down) return false;
+    // the first tap of the first output lies inside the history
+    return n_out == 0 || (t0 * down) / up - W + 1 >= n_old - (2LL * W - 1);
+}
+
+__device__ __forceinline__ float rs_stream_fetch(const float* __restrict__ hrow, const float* __restrict__ crow, long long g, long long n_old,
+                                                 long long n_tot, int H) {
+    if (g < 0 || g >= n_tot) return 0.0f;
+    if (g >= n_old) return crow[g - n_old];
+    const long long k = g - (n_old - H);
+    return k >= 0 ? hrow[k] : 0.0f;
+}
+
+// workgroup id = row * (nchunk + 1) + ch: ch < nchunk computes outputs [t0 + ch * chunk, ..) of the row, ch == nchunk moves the
+// row's history on.  A row whose table breaks the contract is flagged and neither read nor written.
+__global__ __launch_bounds__(RS_NT) void stream_resample_kernel(const float* __restrict__ chunkbuf, long long chunk_samples, float* hist,
+                                                                long long rows, int up, int down, const float* __restrict__ h, int W,
+                                                                float* __restrict__ y, long long y_samples, const long long* __restrict__ tab,
+                                                                int nchunk, int chunk, int span, int bank_lds, int* __restrict__ status) {
+    extern __shared__ float rs_lds[];
+    const unsigned per = (unsigned)nchunk + 1u;
+    const long long row = blockIdx.x / per;
+    const int ch = (int)(blockIdx.x - (unsigned)row * per);
+    const long long* const e = tab + row * RS_STAB;
+    const long long n_old = e[0], n_new = e[1], t0 = e[2], n_out = e[3];
+    const bool ok = rs_stream_row_ok(e, up, down, W, chunk_samples, y_samples);
+    if (ch == 0 && threadIdx.x == 0 && status != nullptr) status[row] = ok ? 0 : -1;
+    if (!ok || (n_new == 0 && n_out == 0)) return;
+    const int H = 2 * W - 1;
+    const long long par = e[6], n_tot = n_old + n_new;
+    const float* const hrow = hist + (par * rows + row) * H;
+    const float* const crow = chunkbuf + e[4];
+    if (ch == nchunk) {
+        if (n_new == 0) return;                                           // a flush: the history stays
+        float* const hnew = hist + ((1 - par) * rows + row) * H;
+        for (int k = threadIdx.x; k < H; k += RS_NT) hnew[k] = rs_stream_fetch(hrow, crow, n_tot - H + k, n_old, n_tot, H);
+        return;
+    }
+    const long long l0 = (long long)ch * chunk;
+    if (l0 >= n_out) return;
+    const int n = (int)(n_out - l0 < (long long)chunk ? n_out - l0 : (long long)chunk);
+    const long long p = (t0 + l0) * down, q0 = p / up;
+    const unsigned r0 = (unsigned)(p - q0 * up);
+    float* const xs = rs_lds;
+    float* const hs = rs_lds + span;
+    const long long g0 = q0 - W + 1;
+    const int need = (int)rs_span(up, down, W, n);                        // <= span: the staged part of n <= chunk outputs
+    for (int k = threadIdx.x; k < need; k += RS_NT) xs[k] = rs_stream_fetch(hrow, crow, g0 + k, n_old, n_tot, H);
+    if (bank_lds) {
+        const int taps = 2 * W, total = up * taps;
+        for (int idx = threadIdx.x; idx < total; idx += RS_NT) {
+            const int ph = idx / taps;
+            hs[ph * (taps + 1) + (idx - ph * taps)] = h[idx];
+        }
+    }
+    __syncthreads();
+    float* const yrow = y + e[5] + l0;
+    if (bank_lds)
+        rs_taps(xs, hs, 2 * W + 1, (unsigned)up, (unsigned)down, W, r0, n, yrow);
+    else
+        rs_taps(xs, h, 2 * W, (unsigned)up, (unsigned)down, W, r0, n, yrow);
+}
+
+// buf[r][k] = buf[r][off + k], k < n <= 4 * RS_NT, off = the spare entry of row r's table: one workgroup per row reads everything
+// before it writes anything (the two spans may overlap).  off <= 0 or off + n > ld: the row is left alone.
+__global__ __launch_bounds__(RS_NT) void stream_carry_kernel(float* __restrict__ buf, long long ld, const long long* __restrict__ tab, int n) {
+    const long long off = tab[(long long)blockIdx.x * RS_STAB + 7];
+    if (off <= 0 || off > ld - n) return;                                 // uniform over the workgroup
+    float* const row = buf + (long long)blockIdx.x * ld;
+    float v[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int i = (int)threadIdx.x + k * RS_NT;
+        v[k] = i < n ? row[off + i] : 0.0f;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int i = (int)threadIdx.x + k * RS_NT;
+        if (i < n) row[i] = v[k];
+    }
+}
+
 int rs_gcd(int a, int b) {
     while (b) { const int t = a % b; a = b; b = t; }
     return a;
@@ -202,6 +299,49 @@ int ctn_resample_ragged(const float* x, long long x_samples, const long long* in
     resample_ragged_kernel<<<dim3((unsigned)(nchunk * U)), dim3(RS_NT), lds, (hipStream_t)stream>>>(
         x, x_samples, in_offsets, in_lens, up, down, h, W, y, y_samples, out_offsets, out_lens, (int)nchunk, chunk, (int)span, bank_lds, status);
     CTN_CHECK_LAUNCH("ctn_resample_ragged");
+    return CTN_OK;
+}
+
+int ctn_stream_resample(const float* chunk, long long chunk_samples, float* hist, long long rows, int up, int down, const float* h, int W,
+                        float* y, long long y_samples, const long long* tab, const long long* host_tab, int* status, void* stream) {
+    CTN_REQUIRE(chunk && hist && h && y && tab && host_tab, "ctn_stream_resample: null pointer");
+    CTN_REQUIRE(rows >= 1 && rows <= 0x7fffffffLL, "ctn_stream_resample: %lld rows (1 .. 2^31 - 1)", rows);
+    CTN_REQUIRE(up >= 1 && down >= 1 && up <= RS_MAX_TERM && down <= RS_MAX_TERM, "ctn_stream_resample: ratio %d / %d (terms in 1 .. 2^20)",
+                up, down);
+    CTN_REQUIRE(rs_gcd(up, down) == 1, "ctn_stream_resample: ratio %d / %d is not in lowest terms", up, down);
+    CTN_REQUIRE(W >= 1 && W <= (1 << 16), "ctn_stream_resample: W = %d taps to either side (1 .. 2^16)", W);
+    CTN_REQUIRE(chunk_samples >= 1 && y_samples >= 1, "ctn_stream_resample: buffers of %lld and %lld samples", chunk_samples, y_samples);
+    long long longest = 0;
+    for (long long r = 0; r < rows; ++r) {
+        const long long* e = host_tab + r * RS_STAB;
+        CTN_REQUIRE(rs_stream_row_ok(e, up, down, W, chunk_samples, y_samples),
+                    "ctn_stream_resample: row %lld (n_old %lld, n_new %lld, t0 %lld, n_out %lld, src %lld, dst %lld, parity %lld) breaks its "
+                    "contract or lies outside the buffers of %lld and %lld samples", r, e[0], e[1], e[2], e[3], e[4], e[5], e[6], chunk_samples,
+                    y_samples);
+        if (e[3] > longest) longest = e[3];
+    }
+    // the largest chunk (a multiple of 256 outputs, 1024 at most) whose input span fits the LDS, as in ctn_resample_ragged
+    int chunkn = RS_CHUNK;
+    while (chunkn > 0 && 4 * rs_span(up, down, W, chunkn) > RS_LDS_BYTES) chunkn -= RS_NT;
+    CTN_REQUIRE(chunkn > 0, "ctn_stream_resample: the input span of 256 outputs at %d / %d with W = %d does not fit %d bytes of LDS", up, down, W,
+                RS_LDS_BYTES);
+    const long long span = rs_span(up, down, W, chunkn), padded = (long long)up * (2 * W + 1);
+    const int bank_lds = 4 * (span + padded) <= RS_LDS_BYTES;
+    const long long nchunk = ctn_cdivll(longest, chunkn);
+    CTN_REQUIRE((nchunk + 1) * rows <= 0x7fffffffLL, "ctn_stream_resample: %lld rows of up to %lld chunks exceed one launch", rows, nchunk);
+    const size_t lds = 4 * (size_t)(span + (bank_lds ? padded : 0));
+    stream_resample_kernel<<<dim3((unsigned)((nchunk + 1) * rows)), dim3(RS_NT), lds, (hipStream_t)stream>>>(
+        chunk, chunk_samples, hist, rows, up, down, h, W, y, y_samples, tab, (int)nchunk, chunkn, (int)span, bank_lds, status);
+    CTN_CHECK_LAUNCH("ctn_stream_resample");
+    return CTN_OK;
+}
+
+int ctn_stream_carry(float* buf, long long ld, long long rows, const long long* tab, int n, void* stream) {
+    CTN_REQUIRE(buf && tab, "ctn_stream_carry: null pointer");
+    CTN_REQUIRE(rows >= 1 && rows <= 0x7fffffffLL, "ctn_stream_carry: %lld rows (1 .. 2^31 - 1)", rows);
+    CTN_REQUIRE(n >= 1 && n <= RS_CHUNK && ld >= n, "ctn_stream_carry: n = %d samples (1 .. %d) in rows of %lld", n, RS_CHUNK, ld);
+    stream_carry_kernel<<<dim3((unsigned)rows), dim3(RS_NT), 0, (hipStream_t)stream>>>(buf, ld, tab, n);
+    CTN_CHECK_LAUNCH("ctn_stream_carry");
     return CTN_OK;
 }
 

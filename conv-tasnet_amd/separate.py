@@ -3,6 +3,10 @@
 Writes <base>.wav (the mixture) and <base>_s{c}.wav per speaker into out_dir.  The forward pass is the HIP path.
 wav IO uses scipy (librosa is not a dependency here; the reference's librosa.output.write_wav no longer exists
 upstream).  File-name quirk kept: ``basename.strip('.wav')`` strips CHARACTERS from both ends (:52-53).
+
+``file_rate=R`` (not in the reference): the files are at R Hz instead of `sample_rate`.  Every mixture is resampled on the device to
+`sample_rate` (resample.resample), separated, and its estimates are resampled back; the mixture and the _s{c} files are written at R
+with the file's own length.  A file at any other rate raises ValueError.
 """
 import os
 
@@ -10,7 +14,7 @@ import numpy as np
 import torch
 
 from .conv_tasnet import ConvTasNet
-from .data import EvalDataLoader, EvalDataset
+from .data import EvalDataLoader, EvalDataset, read_wav_native
 from .utils import remove_pad
 
 
@@ -19,7 +23,16 @@ def _write_wav(path, x, sample_rate):
     wavfile.write(path, sample_rate, np.asarray(x, dtype=np.float32))
 
 
-def separate(model_path, mix_dir, mix_json, out_dir, use_cuda, sample_rate, batch_size):
+def _reader_at(file_rate):
+    def read(path, _sample_rate):
+        x, sr = read_wav_native(path)
+        if sr != file_rate:
+            raise ValueError("%s is at %d Hz, expected file_rate = %d" % (path, sr, file_rate))
+        return x
+    return read
+
+
+def separate(model_path, mix_dir, mix_json, out_dir, use_cuda, sample_rate, batch_size, file_rate=None):
     if mix_dir is None and mix_json is None:
         print("Must provide mix_dir or mix_json! When providing mix_dir, mix_json is ignored.")
     model = ConvTasNet.load_model(model_path)
@@ -27,16 +40,57 @@ def separate(model_path, mix_dir, mix_json, out_dir, use_cuda, sample_rate, batc
     if use_cuda:
         model.cuda()
     dev = next(model.parameters()).device
-    eval_loader = EvalDataLoader(EvalDataset(mix_dir, mix_json, batch_size=batch_size, sample_rate=sample_rate))
+    if file_rate is None or int(file_rate) == int(sample_rate):
+        dataset = EvalDataset(mix_dir, mix_json, batch_size=batch_size, sample_rate=sample_rate)
+        file_rate = None
+    else:
+        from . import resample as rs
+        file_rate = int(file_rate)
+        rs.ratio(file_rate, sample_rate)
+        dataset = EvalDataset(mix_dir, mix_json, batch_size=batch_size, sample_rate=sample_rate, reader=_reader_at(file_rate))
+    eval_loader = EvalDataLoader(dataset)
     os.makedirs(out_dir, exist_ok=True)
     with torch.no_grad():
         for mixture, lens, filenames in eval_loader:
             mixture, lens = mixture.to(dev), lens.to(dev)
-            estimate_source = model(mixture)                     # [B, C, T]
-            flat_estimate = remove_pad(estimate_source, lens)
-            mixture_np = remove_pad(mixture, lens)
+            if file_rate is None:
+                estimate_source = model(mixture)                 # [B, C, T]
+                flat_estimate = remove_pad(estimate_source, lens)
+                mixture_np = remove_pad(mixture, lens)
+                out_rate = sample_rate
+            else:                                                # every file on its own through the device resampler, both ways
+                n_file = [int(n) for n in lens]
+                low = [rs.resample(mixture[i, :n].contiguous(), file_rate, sample_rate) for i, n in enumerate(n_file)]
+                batch = torch.zeros((len(low), max(x.shape[0] for x in low)), device=dev)
+                for i, x in enumerate(low):
+                    batch[i, :x.shape[0]] = x
+                estimate_source = model(batch)
+                flat_estimate = [rs.resample(estimate_source[i, :, :x.shape[0]].contiguous(), sample_rate, file_rate)[:, :n_file[i]]
+                                 .cpu().numpy() for i, x in enumerate(low)]
+                mixture_np = remove_pad(mixture, lens)
+                out_rate = file_rate
             for i, path in enumerate(filenames):
                 filename = os.path.join(out_dir, os.path.basename(path).strip('.wav'))
-                _write_wav(filename + '.wav', mixture_np[i], sample_rate)
+                _write_wav(filename + '.wav', mixture_np[i], out_rate)
                 for c in range(flat_estimate[i].shape[0]):
-                    _write_wav(filename + '_s{}.wav'.format(c + 1), flat_estimate[i][c], sample_rate)
+                    _write_wav(filename + '_s{}.wav'.format(c + 1), flat_estimate[i][c], out_rate)
+
+
+def main(argv=None):
+    import argparse
+    ap = argparse.ArgumentParser(description="separate the wav files of a directory (or of a json list) with a trained Conv-TasNet")
+    ap.add_argument("--model-path", required=True)
+    ap.add_argument("--mix-dir", default=None)
+    ap.add_argument("--mix-json", default=None)
+    ap.add_argument("--out-dir", required=True)
+    ap.add_argument("--use-cuda", type=int, default=1)
+    ap.add_argument("--sample-rate", type=int, default=8000, help="the model's rate")
+    ap.add_argument("--batch-size", type=int, default=1)
+    ap.add_argument("--file-rate", type=int, default=None,
+                    help="the files' rate when it is not --sample-rate: resampled on the device both ways, outputs written at this rate")
+    a = ap.parse_args(argv)
+    separate(a.model_path, a.mix_dir, a.mix_json, a.out_dir, a.use_cuda, a.sample_rate, a.batch_size, file_rate=a.file_rate)
+
+
+if __name__ == "__main__":
+    main()

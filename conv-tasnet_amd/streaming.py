@@ -13,6 +13,7 @@ import torch
 
 from . import ops
 from ._lib import lib
+from .resample import ZEROS
 
 
 def _padded(t, K):
@@ -474,3 +475,147 @@ class FusedStreamPool(_FusedBase):
         lib.call("ctn_stream_back_ragged", self.y.data_ptr(), self.w.data_ptr(), self.Wmp.data_ptr(), self.Vp.data_ptr(),
                  self.fr.data_ptr(), self.out.data_ptr(), self.ola_tail.data_ptr(), self.x.data_ptr(), self.xld, tab,
                  M, m.N, m.L, m.B, m.C, frames, self.soft, st)
+
+
+def plan_rate_push(rem, new, S):
+    """(hops, rem'): a slot that carries `rem` < S model-rate samples and receives `new` more feeds (rem + new) // S whole hops to
+    the pool and carries the rest (pure host code, no GPU)."""
+    rem, new, S = int(rem), int(new), int(S)
+    if not 0 <= rem < S or new < 0:
+        raise ValueError("a remainder in 0..%d and a count >= 0 expected, got %d and %d" % (S - 1, rem, new))
+    return (rem + new) // S, (rem + new) % S
+
+
+def plan_rate_close(fed_hops, rem, S, L):
+    """(hops, pad): the last push of a stream of n = fed_hops * S + rem model-rate samples (rem may be S or more here: it holds the
+    resampler's flush): `pad` zeros take it to max(L, the next multiple of S), fed as `hops` hops.  (0, 0) for an empty stream."""
+    fed_hops, rem, S, L = int(fed_hops), int(rem), int(S), int(L)
+    n = fed_hops * S + rem
+    if n == 0:
+        return 0, 0
+    total = max(L, -(-n // S) * S)
+    return (total - fed_hops * S) // S, total - n
+
+
+class ResamplingStreamPool:
+    """`FusedStreamPool` for clients at another sample rate: samples in at `input_rate`, separated audio out at `output_rate`
+    (None: at the model's rate, no output stage), resampled on the device by two `resample.StreamResampler`s.
+
+        pool = ResamplingStreamPool(model, slots=32, max_chunk_frames=16, input_rate=16000, output_rate=16000)
+        s = pool.open()
+        out, lengths = pool.push(chunk, counts)     # chunk [slots, n]: slot m delivers counts[m] SAMPLES at input_rate, any values
+        tail = pool.close(s)                        # [C, n]: everything not yet delivered; the slot is free again
+    out is [slots, C, max(lengths)] with zeros beyond lengths[m].
+
+    A push, in order: the input resampler writes every slot's new model-rate samples behind the slot's remainder (fewer than S
+    samples) in a device staging buffer; (remainder + new) // S whole hops per slot go to the pool; the leftover moves to the front of
+    the staging rows; the pool's [slots, C, .] output goes through the output resampler (slots * C rows, groups = C).  No launch or
+    copy is per slot, nothing is read back and nothing synchronises: all counting is host arithmetic (`plan_rate_push`,
+    `resample.plan_stream_resample`, `plan_steps`).  `close` flushes the input resampler, zero-pads what is left to a whole hop (and
+    the stream to L samples if it was shorter), pushes it, takes the pool's tail, cuts the model-rate result to
+    n8 = ceil(N * model_rate / input_rate) samples, feeds and flushes the output resampler.  A stream of 0 samples gives [C, 0].
+
+    For every slot, all `push` outputs plus the `close` tail are BITWISE what this offline pipeline gives for the slot's signal x:
+        x8 = resample(x, input_rate, model_rate)
+        x8 zero-padded to max(L, the next multiple of S), through FusedStreamingSeparator(model, batch=1) as one push plus flush()
+        the result cut to len(x8), then resample(., model_rate, output_rate)
+    whatever the cuts and whatever the other slots do (for zeros != 32 read `resample` as the same sum with that filter).
+    `zeros` sets the resamplers' look-ahead (see StreamResampler); ``graph`` is the pool's: the resample launches stay outside its graphs.
+    """
+
+    def __init__(self, model, slots=1, max_chunk_frames=16, model_rate=8000, input_rate=8000, output_rate=None, zeros=ZEROS, graph=False):
+        from . import resample as rs
+        rs.ratio(input_rate, model_rate)                       # ValueError on a bad rate before anything is built
+        if output_rate is not None:
+            rs.ratio(model_rate, output_rate)
+        self.pool = pool = FusedStreamPool(model, slots, max_chunk_frames, graph)
+        self.M, self.S, self.L, self.C, self.dev = pool.M, pool.S, pool.L, model.C, pool.dev
+        piece = pool.F * pool.S                                  # model-rate samples of one pool step
+        self.in_rs = rs.StreamResampler(self.M, input_rate, model_rate, max(1, piece * int(input_rate) // int(model_rate)), zeros=zeros,
+                                        device=self.dev)
+        self.out_rs = None
+        if output_rate is not None:
+            self.out_rs = rs.StreamResampler(self.M * self.C, model_rate, output_rate, piece, zeros=zeros, groups=self.C, device=self.dev)
+        self.rem, self.fed = [0] * self.M, [0] * self.M          # carried model-rate samples; hops fed to the pool so far
+        self.stage = torch.zeros((self.M, 4 * piece + 2 * self.S), device=self.dev)
+
+    @property
+    def is_open(self):
+        return self.pool.is_open
+
+    def _room(self, width):
+        """Staging rows of at least `width` samples; the carried remainders move along."""
+        if width > self.stage.shape[1]:
+            grown = torch.zeros((self.M, 2 * width), device=self.dev)
+            grown[:, :self.S] = self.stage[:, :self.S]
+            self.stage = grown
+
+    def open(self, slot=None):
+        slot = self.pool.open(slot)
+        self.in_rs.open(slot)
+        if self.out_rs is not None:
+            self.out_rs.open(slot)
+        self.rem[slot] = self.fed[slot] = 0
+        return slot
+
+    @torch.no_grad()
+    def push(self, chunk, counts):
+        M, S, C = self.M, self.S, self.C
+        counts = self.in_rs._check_counts(counts)
+        if not any(counts):
+            return torch.zeros((M, C, 0), device=self.dev), [0] * M
+        new = self.in_rs.plan(counts)
+        plan = [plan_rate_push(r, n, S) for r, n in zip(self.rem, new)]
+        hops = [h for h, _ in plan]
+        self._room(max(r + n for r, n in zip(self.rem, new)) + S)
+        self.in_rs.run(chunk, counts, self.stage, self.stage.shape[1], self.rem, spare=[h * S for h in hops])
+        if any(hops):
+            out, lengths = self.pool.push(self.stage[:, :max(hops) * S], hops)
+            # the leftover of every row to its front: row m from hops[m] * S on (the table's spare entry), one launch for all
+            lib.call("ctn_stream_carry", self.stage.data_ptr(), self.stage.shape[1], M, self.in_rs.tab.data_ptr(), S - 1, ops._stream())
+        else:
+            out, lengths = torch.zeros((M, C, 0), device=self.dev), [0] * M
+        for m, (h, r) in enumerate(plan):
+            self.fed[m] += h
+            self.rem[m] = r
+        if self.out_rs is None:
+            return out, lengths
+        y, lengths = self.out_rs.push(out.view(M * C, out.shape[2]), lengths)
+        return y.view(M, C, y.shape[1]), lengths
+
+    @torch.no_grad()
+    def close(self, slot):
+        """Everything of the slot's stream not yet delivered, [C, n] at the output rate; the slot is free again."""
+        slot = int(slot)
+        if not 0 <= slot < self.M or not self.pool.is_open[slot]:
+            raise ValueError("slot %r is not open" % (slot,))
+        M, S, C = self.M, self.S, self.C
+        none = [0] * M
+        flush = self.in_rs.plan(none, (slot,))[slot]
+        self._room(self.rem[slot] + flush + self.L + S)
+        total_in = self.in_rs.n[slot]
+        self.in_rs.run(None, none, self.stage, self.stage.shape[1], self.rem, final=(slot,))
+        rem = self.rem[slot] + flush
+        n8, fed = self.fed[slot] * S + rem, self.fed[slot]
+        assert n8 == self.in_rs.out_total(total_in)
+        hops, pad = plan_rate_close(fed, rem, S, self.L)
+        self.rem[slot] = self.fed[slot] = 0
+        if n8 == 0:
+            self.pool.close(slot)
+            if self.out_rs is not None:
+                self.out_rs.close(slot)
+            return torch.zeros((C, 0), device=self.dev)
+        if pad:
+            self.stage[slot, rem:rem + pad] = 0
+        feed = list(none)
+        feed[slot] = hops
+        out, lengths = self.pool.push(self.stage[:, :hops * S], feed)
+        rest = torch.cat([out[slot, :, :lengths[slot]], self.pool.close(slot)], dim=1)
+        rest = rest[:, :n8 - max(fed - 1, 0) * S]                # the model-rate result cut to n8 samples in all
+        if self.out_rs is None:
+            return rest.contiguous()
+        buf = torch.zeros((M * C, rest.shape[1]), device=self.dev)
+        buf[slot * C:(slot + 1) * C] = rest
+        feed[slot] = rest.shape[1]
+        y, lengths = self.out_rs.push(buf, feed)
+        return torch.cat([y[slot * C:(slot + 1) * C, :lengths[slot]], self.out_rs.close(slot)], dim=1)

@@ -676,6 +676,43 @@ int ctn_dynmix_speed_segments(const float* corpus, const long long* offsets, con
                               long long bank_floats, const int* bank_tab, int span_cap, int bank_cap, float* seg, int* seg_utt,
                               void* stream);
 
+/* ---- streaming sinc resampling: the sum above over signals that arrive push by push (csrc/ctn_resample.hip) -----------------
+ * `rows` independent streams.  The filter, (i, p) and the tap sum are those of the section above, taken over the WHOLE stream of a
+ * row: x before sample 0 and beyond the end of the stream reads as zero, so every output is bitwise what ctn_resample_ragged gives
+ * for the whole signal, however it was cut into pushes and whatever the other rows do.  The arithmetic the caller keeps on the host:
+ *     after N input samples exactly E(N) = ceil((N - W) * up / down) outputs are computable for N > W, 0 otherwise (output t reads
+ *     up to input i_t + W); a push that takes a row from N to N + k samples emits outputs [E(N), E(N + k)); the first tap of output
+ *     E(N) is at index >= N - 2W + 1; closing a row emits [E(N), ceil(N * up / down)) with zeros for the missing future.
+ * State: hist [2][rows][2W - 1] fp32, the last 2W - 1 samples of every row, twice: a push reads half `parity` and writes the other
+ * half, so no workgroup reads what another one of the same launch writes; the caller flips a row's parity after every push with
+ * n_new > 0.  A stream starts with n_old = 0 (history entries before sample 0 are never read; zeroing them is the caller's choice).
+ *   tab  int64 [rows][CTN_STREAM_RS_TAB] in device memory, rewritten by the caller before every call:
+ *        [0] n_old   samples of the row received before this call      [1] n_new   new samples with this call (0: none, a flush)
+ *        [2] t0      first output to emit                              [3] n_out   outputs to emit
+ *        [4] src     offset of the row's new samples in `chunk`        [5] dst     offset of the row's first output in `y`
+ *        [6] parity  half of hist that holds the row's history (0, 1)  [7] spare
+ *   ctn_stream_resample: y[dst + k] = output t0 + k of the row for k < n_out, then hist[1 - parity][row] = the last 2W - 1 samples
+ *     of the n_old + n_new received (zeros before sample 0) when n_new > 0.  Sample g of the row reads as zero for g < 0 and
+ *     g >= n_old + n_new, chunk[src + g - n_old] for g >= n_old, hist[parity][row][g - n_old + 2W - 1] otherwise: the kernel never
+ *     touches chunk beyond a row's n_new.  A row with n_new = n_out = 0 is neither read nor written, whatever its other entries.
+ *     Every other row needs: all entries >= 0, parity 0 or 1, n_old + n_new <= 2^40, [src, src + n_new) inside chunk
+ *     (chunk_samples floats), [dst, dst + n_out) inside y (y_samples floats), t0 + n_out <= ceil((n_old + n_new) * up / down), and
+ *     for n_out > 0 the first tap of output t0 inside the history: floor(t0 * down / up) - W + 1 >= n_old - (2W - 1).
+ *     host_tab: the same table in HOST memory; every row is checked before the launch (CTN_ERR_ARG, nothing launched) and the grid
+ *     is sized from it.  The kernel checks the device table again: a row that breaks the contract is neither read nor written and
+ *     status[r] = -1 (0 otherwise; status [rows] int32 may be null).  One workgroup of 256 threads per 1024 consecutive outputs
+ *     of a row (fewer where down / up is large) stages the input span, and the bank when it fits, in LDS as ctn_resample_ragged
+ *     does, plus one workgroup per row for the history: a long push spreads over the device.  1 <= up, down <= 2^20 in lowest
+ *     terms, 1 <= W <= 2^16, 1 <= rows < 2^31.
+ *   ctn_stream_carry: buf [rows][ld] fp32; row r moves its samples [off, off + n) to its front, buf[r][k] = buf[r][off + k] for
+ *     k < n, off = tab[r][7] (the spare entry of the table above): what a caller that consumes whole hops from the front of
+ *     staging rows carries over to the next push.  One workgroup per row reads all n samples before it writes any (the spans may
+ *     overlap).  A row with off <= 0 or off + n > ld is left alone.  1 <= n <= 1024, ld >= n. */
+#define CTN_STREAM_RS_TAB 8
+int ctn_stream_resample(const float* chunk, long long chunk_samples, float* hist, long long rows, int up, int down, const float* h, int W,
+                        float* y, long long y_samples, const long long* tab, const long long* host_tab, int* status, void* stream);
+int ctn_stream_carry(float* buf, long long ld, long long rows, const long long* tab, int n, void* stream);
+
 /* ---- noisy and reverberant dynamic mixing (csrc/ctn_dynmix_aug.hip) ------------------------------------------------------
  * what WHAM!, WHAMR! and noisy LibriMix add to wsj0-2mix, drawn on the device: a noise recording at a drawn SNR under every
  * mixture, every source convolved with a drawn room impulse response (RIR).  The conventions are those of the two sections
