@@ -14,5 +14,7 @@ from . import resample  # noqa: F401
 from .resample import StreamResampler  # noqa: F401
 from . import rir  # noqa: F401
 from .rir import RirBank  # noqa: F401
+from . import longform  # noqa: F401
+from .longform import separate_long, frame_ragged, stitch_ragged, plan_segments, fade_tables  # noqa: F401
 
 __version__ = "0.1.0"

@@ -7,6 +7,11 @@ upstream).  File-name quirk kept: ``basename.strip('.wav')`` strips CHARACTERS f
 ``file_rate=R`` (not in the reference): the files are at R Hz instead of `sample_rate`.  Every mixture is resampled on the device to
 `sample_rate` (resample.resample), separated, and its estimates are resampled back; the mixture and the _s{c} files are written at R
 with the file's own length.  A file at any other rate raises ValueError.
+
+``segment=S`` (not in the reference; samples at `sample_rate`): every file goes through longform.separate_long -- cut into overlapping
+segments of S samples every `hop` (default S // 2), the segments of the files of one batch separated `segment_batch` at a time,
+their speaker orders chained and the overlaps cross-faded on the device.  It composes with file_rate (resample -> long-form ->
+resample back).  With segment=None the function is the path above, unchanged.
 """
 import os
 
@@ -32,7 +37,8 @@ def _reader_at(file_rate):
     return read
 
 
-def separate(model_path, mix_dir, mix_json, out_dir, use_cuda, sample_rate, batch_size, file_rate=None):
+def separate(model_path, mix_dir, mix_json, out_dir, use_cuda, sample_rate, batch_size, file_rate=None, segment=None, hop=None,
+             segment_batch=8):
     if mix_dir is None and mix_json is None:
         print("Must provide mix_dir or mix_json! When providing mix_dir, mix_json is ignored.")
     model = ConvTasNet.load_model(model_path)
@@ -40,6 +46,10 @@ def separate(model_path, mix_dir, mix_json, out_dir, use_cuda, sample_rate, batc
     if use_cuda:
         model.cuda()
     dev = next(model.parameters()).device
+    if segment is not None:
+        from . import longform
+        hop = int(segment) // 2 if hop is None else hop
+        longform.check_geometry(segment, hop)
     if file_rate is None or int(file_rate) == int(sample_rate):
         dataset = EvalDataset(mix_dir, mix_json, batch_size=batch_size, sample_rate=sample_rate)
         file_rate = None
@@ -53,7 +63,17 @@ def separate(model_path, mix_dir, mix_json, out_dir, use_cuda, sample_rate, batc
     with torch.no_grad():
         for mixture, lens, filenames in eval_loader:
             mixture, lens = mixture.to(dev), lens.to(dev)
-            if file_rate is None:
+            if segment is not None:                              # every file on its own through the long-form path
+                n_file = [int(n) for n in lens]
+                files = [mixture[i, :n].contiguous() for i, n in enumerate(n_file)]
+                low = files if file_rate is None else [rs.resample(x, file_rate, sample_rate) for x in files]
+                est = longform.separate_long(model, low, segment, hop, batch_size=segment_batch)
+                if file_rate is not None:
+                    est = [rs.resample(e.contiguous(), sample_rate, file_rate)[:, :n] for e, n in zip(est, n_file)]
+                flat_estimate = [e.cpu().numpy() for e in est]
+                mixture_np = remove_pad(mixture, lens)
+                out_rate = sample_rate if file_rate is None else file_rate
+            elif file_rate is None:
                 estimate_source = model(mixture)                 # [B, C, T]
                 flat_estimate = remove_pad(estimate_source, lens)
                 mixture_np = remove_pad(mixture, lens)
@@ -88,8 +108,18 @@ def main(argv=None):
     ap.add_argument("--batch-size", type=int, default=1)
     ap.add_argument("--file-rate", type=int, default=None,
                     help="the files' rate when it is not --sample-rate: resampled on the device both ways, outputs written at this rate")
+    ap.add_argument("--segment-s", type=float, default=None,
+                    help="long recordings: separate in overlapping segments of this many seconds (the training length) and stitch them "
+                         "on the device; default: every file in one pass")
+    ap.add_argument("--hop-s", type=float, default=None, help="seconds between segment starts (default: half of --segment-s)")
+    ap.add_argument("--segment-batch", type=int, default=8, help="segments per forward pass with --segment-s")
     a = ap.parse_args(argv)
-    separate(a.model_path, a.mix_dir, a.mix_json, a.out_dir, a.use_cuda, a.sample_rate, a.batch_size, file_rate=a.file_rate)
+    if a.hop_s is not None and a.segment_s is None:
+        ap.error("--hop-s needs --segment-s")
+    segment = None if a.segment_s is None else int(round(a.segment_s * a.sample_rate))
+    hop = None if a.hop_s is None else int(round(a.hop_s * a.sample_rate))
+    separate(a.model_path, a.mix_dir, a.mix_json, a.out_dir, a.use_cuda, a.sample_rate, a.batch_size, file_rate=a.file_rate,
+             segment=segment, hop=hop, segment_batch=a.segment_batch)
 
 
 if __name__ == "__main__":

@@ -785,6 +785,58 @@ int ctn_dynmix_gather_aug(const float* corpus, const long long* offsets, const l
                           const int* noise_utt, const long long* noise_start, const float* ngain, float* mixture, float* sources,
                           float* peak, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- long-recording separation: segments framed and stitched on the device (csrc/ctn_longform.hip) -------------------------
+ * what users of the non-causal gLN model do with a meeting or a podcast: cut it into overlapping segments of the training length,
+ * separate the segments as a batch, bring every segment's speakers into the order of its predecessor by comparing the overlaps
+ * (PIT leaves the order arbitrary per segment), and cross-fade.  R recordings at the model's rate; segment length seg, hop hop,
+ * overlap ov = seg - hop with 1 <= ov <= hop, so hop < seg <= 2 * hop: never more than two segments over one sample.
+ * Segments of a recording of T >= 1 samples: n = 1 if T <= seg, else n = 1 + ceil((T - seg) / hop) (ctn_longform_nseg; 0 for
+ *   arguments out of range).  Segment i covers samples [i * hop, i * hop + seg) and reads zero at and beyond T; only the last one
+ *   is ever padded: (n - 2) * hop + seg < T and (n - 1) * hop < T.  All recordings' segments form one list of Nseg rows;
+ *   seg_ptr [R + 1] int64 gives each recording's range (seg_ptr[0] = 0, seg_ptr[R] = Nseg).
+ * Framing (ctn_longform_frame): segs[s, u] = x[in_off[r] + i * hop + u] where i * hop + u < T[r], else +0, for s = seg_ptr[r] + i.
+ *   Bit copies.  segs [Nseg][seg] fp32.
+ * Costs (ctn_longform_costs): for every segment i >= 1 of a recording and speakers a, b < C,
+ *       cost[s, a, b] = sum_{t < ov} (est[s - 1, a, hop + t] - est[s, b, t])^2          est [Nseg][C][seg], cost [Nseg][C][C] fp32
+ *   in a fixed order that does not depend on the launch geometry: d = prev - cur, q = d * d, acc[j] = acc[j] + q, three separate
+ *   fp32 roundings (no fused multiply-add).  There are 1024 partial sums: acc[t mod 1024] takes the elements t in ascending order,
+ *   starting from +0; then for s = 512, 256, ..., 1: acc[j] += acc[j + s] for j < s; cost = acc[0].  Rows of first segments
+ *   are written as zeros.
+ * Order (ctn_longform_order): perms = the C! permutations in lexicographic (itertools) order, 2 <= C <= 4.  q_s = the first k
+ *   that minimises sum_a cost[s, a, perms[k][a]], the sum taken in fp32 from +0 with a ascending; a strict < keeps the earlier k
+ *   on a tie (and k = 0 when a sum is NaN).  g[first segment] = identity, g[s][a] = perms[q_s][ g[s - 1][a] ]: g[s][a] is the
+ *   local channel of segment s that carries output channel a.  g [Nseg][C] int32.  A recording's chain is a scan of permutations.
+ * Assembly (ctn_longform_assemble): for output channel a and sample t < T: i = min(t div hop, n - 1), u = t - i * hop.
+ *       i >= 1 and u < ov:   out = fo[u] * est[i - 1, g[i - 1][a], hop + u] + fi[u] * est[i, g[i][a], u]
+ *                            two products and one sum, each one fp32 rounding, in that order
+ *       otherwise            out = the bit copy of est[i, g[i][a], u]
+ *   fi, fo [ov] fp32 tables designed on the host in fp64 and rounded once (longform.fade_tables):
+ *       'linear'  fi[u] = (u + 0.5) / ov                     fo[u] = 1 - (u + 0.5) / ov
+ *       'hann'    fi[u] = sin^2(pi * (u + 0.5) / (2 * ov))   fo[u] = 1 - that
+ *   Channel a of recording r starts at out_off[r] + a * T[r] in the flat buffer out (out_samples floats).  Nothing outside those
+ *   ranges is written.  An entry of g outside [0, C) never forms an address: what would have read it -- that channel of the segment's
+ *   own samples, and of the chunk of its successor that holds the cross-fade -- is left unwritten.
+ * Conventions (those of ctn_resample_ragged): plain pointers and an explicit stream; seg_ptr, T, in_off / out_off as int64 in
+ *   device memory; host_tables in HOST memory = seg_ptr [R + 1], T [R], in_off or out_off [R] back to back (host_seg_ptr: the
+ *   first of the three), checked against the contract and the buffer sizes before anything is launched (CTN_ERR_ARG), the grid
+ *   sized from them.  The kernels check the device copy again: a recording whose range, length or offset breaks the contract is
+ *   neither read nor written and status[r] = -1 (0 otherwise; status [R] int32 may be null).  1 <= R <= Nseg < 2^31,
+ *   seg <= 2^30, T <= 2^40.  The C ABI takes any seg and hop within 1 <= ov <= hop; 16-byte loads and stores are used where the
+ *   addresses allow (seg and hop multiples of 4 on 16-byte aligned buffers), 4-byte ones elsewhere, with the same bits.
+ *   256-thread workgroups: one per 2048 samples of a segment (frame, assemble), one per segment pair (costs: the 2 * C overlap
+ *   rows are loaded once for all C * C costs, the tree runs through LDS), one per recording (order).  No atomics. */
+long long ctn_longform_nseg(long long T, int seg, int hop);
+int ctn_longform_frame(const float* x, long long x_samples, const long long* seg_ptr, const long long* T, const long long* in_off,
+                       long long R, long long Nseg, int seg, int hop, float* segs, const long long* host_tables, int* status,
+                       void* stream);
+int ctn_longform_costs(const float* est, const long long* seg_ptr, long long R, long long Nseg, int C, int seg, int hop, float* cost,
+                       const long long* host_seg_ptr, void* stream);
+int ctn_longform_order(const float* cost, const long long* seg_ptr, long long R, long long Nseg, int C, int* g,
+                       const long long* host_seg_ptr, int* status, void* stream);
+int ctn_longform_assemble(const float* est, const int* g, const long long* seg_ptr, const long long* T, const long long* out_off,
+                          long long R, long long Nseg, int C, int seg, int hop, const float* fi, const float* fo, float* out,
+                          long long out_samples, const long long* host_tables, int* status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
