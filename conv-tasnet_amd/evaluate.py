@@ -5,7 +5,8 @@
 utterances, scipy wav reader) and prints per-utterance and average SI-SNRi.  ``evaluate_loader(model, data_loader)`` is
 the same loop over any iterable of (padded_mixture, mixture_lengths, padded_source) batches.  SDRi (cal_SDRi, :76-91) is
 BSS Eval v3 on the GPU in fp64 (bss_eval.py): ``cal_SDRi`` for one utterance, ``evaluate_loader(..., calc_sdr=True)`` for
-a whole loader, one bss_eval_batch call per batch with the mixture as an extra estimate row.
+a whole loader, one bss_eval_batch call per batch with the mixture as an extra estimate row.  ``calc_stoi=True`` adds STOI and
+ESTOI (stoi.py, csrc/ctn_stoi.hip) the same way: one stoi_both call per batch, the mixture row giving the anchor.
 """
 import numpy as np
 import torch
@@ -13,6 +14,7 @@ import torch
 from .bss_eval import bss_eval_batch, sdr_improvement
 from .conv_tasnet import ConvTasNet
 from .pit_criterion import cal_loss
+from .stoi import stoi_both, stoi_improvement
 from .utils import remove_pad
 
 
@@ -48,8 +50,9 @@ def cal_SDRi(src_ref, src_est, mix):
     return float(sdr_improvement(sdr, sir)[0])
 
 
-def evaluate(model_path, data_dir, calc_sdr=0, use_cuda=1, sample_rate=8000, batch_size=1):
-    """The reference's signature (src/evaluate.py:21-73).  -> average SI-SNRi over data_dir's utterances."""
+def evaluate(model_path, data_dir, calc_sdr=0, use_cuda=1, sample_rate=8000, batch_size=1, calc_stoi=0):
+    """The reference's signature (src/evaluate.py:21-73).  -> average SI-SNRi over data_dir's utterances; with calc_stoi what
+    evaluate_loader(calc_stoi=True) returns."""
     if calc_sdr:
         raise NotImplementedError("evaluate(calc_sdr=1) is not switched on: SDRi is computed by "
                                   "evaluate_loader(..., calc_sdr=True) and cal_SDRi (GPU BSS Eval, bss_eval.py)")
@@ -58,13 +61,16 @@ def evaluate(model_path, data_dir, calc_sdr=0, use_cuda=1, sample_rate=8000, bat
     print(model)
     dataset = AudioDataset(data_dir, batch_size, sample_rate=sample_rate, segment=-1)
     data_loader = AudioDataLoader(dataset, batch_size=1, num_workers=2)
-    return evaluate_loader(model, data_loader, use_cuda=bool(use_cuda))
+    return evaluate_loader(model, data_loader, use_cuda=bool(use_cuda), calc_stoi=bool(calc_stoi), sample_rate=sample_rate)
 
 
-def evaluate_loader(model, data_loader, use_cuda=True, verbose=True, calc_sdr=False):
+def evaluate_loader(model, data_loader, use_cuda=True, verbose=True, calc_sdr=False, calc_stoi=False, sample_rate=8000):
     """-> average SI-SNRi over every utterance of the loader; with calc_sdr (src/evaluate.py:62-72) -> (average SI-SNRi,
     average SDRi), every batch scored by one bss_eval_batch call (the mixture is an extra estimate row, so its anchor
-    SDRs come out of the same call).  `model` is a ConvTasNet or a checkpoint path."""
+    SDRs come out of the same call).  With calc_stoi the return value is followed by (average STOI, average ESTOI, average
+    STOI improvement over the mixture): every batch scored by one stoi_both call at `sample_rate` on the reordered estimates
+    plus the mixture row, an utterance's STOI / ESTOI being the mean over its speakers.  `model` is a ConvTasNet or a checkpoint
+    path."""
     if isinstance(model, str):
         model = ConvTasNet.load_model(model)
     model.eval()
@@ -73,6 +79,7 @@ def evaluate_loader(model, data_loader, use_cuda=True, verbose=True, calc_sdr=Fa
     dev = next(model.parameters()).device
     total, count = 0.0, 0
     total_sdri = 0.0
+    total_stoi, total_estoi, total_stoii = 0.0, 0.0, 0.0
     with torch.no_grad():
         for padded_mixture, mixture_lengths, padded_source in data_loader:
             padded_mixture = padded_mixture.to(dev)
@@ -88,23 +95,42 @@ def evaluate_loader(model, data_loader, use_cuda=True, verbose=True, calc_sdr=Fa
                 rows = torch.cat([reorder, padded_mixture.unsqueeze(1)], 1)
                 sdr, sir, _, _ = bss_eval_batch(padded_source, rows, mixture_lengths)
                 sdri = sdr_improvement(sdr, sir).tolist()
+            scores = None
+            if calc_stoi:
+                rows = torch.cat([reorder, padded_mixture.unsqueeze(1)], 1)
+                d_stoi, d_estoi, _, _ = stoi_both(padded_source, rows, mixture_lengths, sample_rate)
+                C = padded_source.shape[1]
+                scores = (torch.diagonal(d_stoi[:, :C], dim1=1, dim2=2).mean(1).tolist(),
+                          torch.diagonal(d_estoi[:, :C], dim1=1, dim2=2).mean(1).tolist(), stoi_improvement(d_stoi).tolist())
             for u, (mix, ref, out) in enumerate(zip(mixture, source, est)):
                 if sdri is not None:
                     total_sdri += sdri[u]
                     if verbose:
                         print("\tSDRi=%.2f" % sdri[u])
+                if scores is not None:
+                    total_stoi += scores[0][u]
+                    total_estoi += scores[1][u]
+                    total_stoii += scores[2][u]
+                    if verbose:
+                        print("\tSTOI=%.3f ESTOI=%.3f" % (scores[0][u], scores[1][u]))
                 v = cal_SISNRi(ref.astype(np.float64), out.astype(np.float64), mix.astype(np.float64))
                 if verbose:
                     print("Utt %d\tSI-SNRi=%.2f" % (count + 1, v))
                 total += v
                 count += 1
     avg = total / max(count, 1)
+    if calc_stoi:
+        stoi_avgs = tuple(t / max(count, 1) for t in (total_stoi, total_estoi, total_stoii))
+        if verbose:
+            print("Average STOI: {0:.3f}".format(stoi_avgs[0]))
+            print("Average ESTOI: {0:.3f}".format(stoi_avgs[1]))
+            print("Average STOI improvement: {0:.3f}".format(stoi_avgs[2]))
     if calc_sdr:
         avg_sdri = total_sdri / max(count, 1)
         if verbose:
             print("Average SDR improvement: {0:.2f}".format(avg_sdri))
             print("Average SISNR improvement: {0:.2f}".format(avg))
-        return avg, avg_sdri
+        return (avg, avg_sdri) + stoi_avgs if calc_stoi else (avg, avg_sdri)
     if verbose:
         print("Average SISNR improvement: {0:.2f}".format(avg))
-    return avg
+    return (avg,) + stoi_avgs if calc_stoi else avg

@@ -837,6 +837,50 @@ int ctn_longform_assemble(const float* est, const int* g, const long long* seg_p
                           long long R, long long Nseg, int C, int seg, int hop, const float* fi, const float* fo, float* out,
                           long long out_samples, const long long* host_tables, int* status, void* stream);
 
+/* ---- STOI / ESTOI intelligibility scores in fp64 (csrc/ctn_stoi.hip) ---------------------------------------------------------
+ * C. H. Taal, R. C. Hendriks, R. Heusdens, J. Jensen, "An Algorithm for Intelligibility Prediction of Time-Frequency Weighted Noisy
+ * Speech", IEEE TASLP 19(7), 2011 (STOI) and J. Jensen, C. H. Taal, "An Algorithm for Predicting the Intelligibility of Speech
+ * Masked by Modulated Noise Maskers", IEEE/ACM TASLP 24(11), 2016 (ESTOI), with the conventions of the authors' MATLAB code and of
+ * pystoi.  Constants: 10 kHz input, frames of 256 at hop 128 starting at i < n - 256 (strict: the frame that ends on the last
+ * sample is dropped), window hanning(258)[1:-1], 512-point DFT, 15 third-octave bands from 150 Hz (bins 7 .. 218), segments of
+ * 30 frames, beta = -15 dB, 40 dB dynamic range, eps = DBL_EPSILON, 1e-5 for fewer than 30 frames.
+ * ref: [B,C,T] fp32 references, est: [B,E,T] fp32 estimate rows (the mixture can be one more row: the anchor in the same call),
+ * lengths: [B] int64, all ALREADY AT 10 kHz; samples at t >= lengths[b] are never read.  C >= 1, E >= 1, 1 <= T <= 2^30.  All
+ * arithmetic fp64 from the fp32 samples, every reduction in a fixed order that depends on the utterance alone (bitwise the same
+ * in any batch); no host read-back, no synchronisation, no atomics: graph-capturable.  NF = ctn_stoi_max_frames(T) =
+ * max(1, first-pass frames of T samples), MF = max(1, NF - 1).
+ *   ctn_stoi_eval: everything below in one call -> d_stoi, d_estoi [B,E,C] fp64 (estimate e against reference c), m_out, k_out
+ *     [B,E,C] int32 (nullable): the frames M after silent-frame removal and the kept first-pass frames K of that pair.
+ *     workspace: ctn_stoi_workspace() bytes.
+ * The stages, each on caller buffers:
+ *   ctn_stoi_frames: per reference row energy [B,C,NF] = 20 log10(||w * frame|| + eps) (0 beyond the row's frames), the keep
+ *     mask energy > max - 40 and its exclusive scan: keep_idx [B,C,NF] int32 = the kept frame indices in order (-1 beyond
+ *     them), kcount [B,C] int32 = K.  The mask belongs to the reference: an estimate paired with reference c uses c's table.
+ *   ctn_stoi_bands: env [B, C + E*C, 15, MF] fp64: set c < C = reference c, set C + e*C + c = estimate e compacted by the table of
+ *     reference c.  The compacted signal (overlap-add of the kept windowed frames at hop 128) is rebuilt on the fly, framed and
+ *     windowed again, its DFT taken as a DFT-matrix product on v_mfma_f64_16x16x4_f64; env = sqrt of the band sums of |X|^2.
+ *     Frame m < M = max(K - 1, 0) of a set is written, nothing beyond.
+ *   ctn_stoi_score: per pair and segment the 15 x 30 normalise / clip / correlate of STOI and the row / column normalisation
+ *     of ESTOI in one pass, then the sum over segments -> d; M < 30 gives 1e-5 for both.  workspace: ctn_stoi_score_workspace().
+ * Arguments are checked before any launch (CTN_ERR_ARG); the workspace functions return 0 for arguments out of range. */
+#define CTN_STOI_FS 10000
+#define CTN_STOI_FRAME 256
+#define CTN_STOI_HOP 128
+#define CTN_STOI_NFFT 512
+#define CTN_STOI_BANDS 15
+#define CTN_STOI_SEGMENT 30
+int ctn_stoi_max_frames(long long T);
+size_t ctn_stoi_workspace(long long B, int C, long long E, long long T);
+int ctn_stoi_eval(const float* ref, const float* est, const long long* lengths, long long B, int C, long long E, long long T,
+                  double* d_stoi, double* d_estoi, int* m_out, int* k_out, void* workspace, size_t workspace_bytes, void* stream);
+int ctn_stoi_frames(const float* ref, const long long* lengths, long long B, int C, long long T, double* energy, int* keep_idx,
+                    int* kcount, void* stream);
+int ctn_stoi_bands(const float* ref, const float* est, const long long* lengths, const int* keep_idx, const int* kcount,
+                   long long B, int C, long long E, long long T, double* env, void* stream);
+size_t ctn_stoi_score_workspace(long long B, int C, long long E, long long T);
+int ctn_stoi_score(const double* env, const int* kcount, long long B, int C, long long E, long long T, double* d_stoi,
+                   double* d_estoi, int* m_out, int* k_out, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
