@@ -1,6 +1,7 @@
 """Solver: epoch driver with the reference's constructor and observable behaviour (src/solver.py:13-221).
 
-``Solver(data, model, optimizer, arg_solver)`` takes the same positional 13-tuple.  Behaviour kept on purpose,
+``Solver(data, model, optimizer, arg_solver)`` takes the same positional 13-tuple; the optional ``criterion`` replaces the PIT
+loss (``criterion(sources, estimate, lengths)`` -> scalar loss; mixit.MixItCriterion trains without isolated sources).  Behaviour kept on purpose,
 quirks included:
   * reported epoch loss = sum / (n_batches + 1)                                   (src/solver.py:171,219-221)
   * LR halving compares with the PREVIOUS epoch; after three misses it halves on that and on every further
@@ -57,9 +58,12 @@ class _HalvingSchedule:
 
 
 class Solver(object):
-    def __init__(self, data, model, optimizer, arg_solver):
+    def __init__(self, data, model, optimizer, arg_solver, criterion=None):
         a = SolverArgs(*arg_solver)
         self.args = a
+        # None: the reference's cal_loss (PIT SI-SNR against [B,C,T] sources); otherwise criterion(sources, estimate, lengths)
+        # -> the scalar loss, e.g. mixit.MixItCriterion over the [B,2,T] references of a MixtureOfMixtures loader
+        self.criterion = criterion
         self.tr_loader, self.cv_loader = data['tr_loader'], data['cv_loader']
         self.model, self.optimizer = model, optimizer
         # attribute names the reference exposes
@@ -213,7 +217,10 @@ class Solver(object):
         for mixture, lengths, sources in loader:
             mixture, lengths, sources = mixture.to(dev), lengths.to(dev), sources.to(dev)
             with torch.set_grad_enabled(not cross_valid):
-                loss = cal_loss(sources, self.model(mixture), lengths)[0]
+                if self.criterion is None:
+                    loss = cal_loss(sources, self.model(mixture), lengths)[0]
+                else:
+                    loss = self.criterion(sources, self.model(mixture), lengths)
             if not cross_valid:
                 # training steps are collective (equal step counts per rank: data.AudioDataset equalises the plan)
                 loss, report = self._global_loss(loss, int(mixture.shape[0]))

@@ -50,14 +50,24 @@ class SyntheticLoader:
 
 def train(data, epochs, model_path, save_folder="exp/models", continue_from="", config=None, lr=1e-3,
           max_grad_norm=5, half_lr=1, early_stop=1, print_freq=10, enable_checkpoint=0, optimizer_type='adam',
-          momentum=0.0, l2=0.0):
+          momentum=0.0, l2=0.0, loss='pit', snr_max=30.0):
     """data = {'tr_loader': ..., 'cv_loader': ...}.  Returns the Solver after training.
+
+    loss 'pit': the reference's permutation-invariant SI-SNR against [B,C,T] sources.  loss 'mixit': mixture invariant
+    training (mixit.cal_mixit_loss, soft threshold snr_max dB or None): both loaders yield the two reference mixtures
+    [B,2,T] in place of the sources (mixit.MixtureOfMixtures) and config['C'] is the number of model outputs, 2 .. 8.
 
     optimizer_type 'sgd' -> FlatSGD(lr, momentum, weight_decay=l2), 'adam' -> FlatAdam(lr, weight_decay=l2)
     (src/train.py:87-98); any other value prints 'Not support optimizer' and returns None, as the reference does."""
     if optimizer_type not in ('sgd', 'adam'):
         print("Not support optimizer")
         return None
+    if loss not in ('pit', 'mixit'):
+        raise ValueError("loss must be 'pit' or 'mixit', got %r" % (loss,))
+    criterion = None
+    if loss == 'mixit':
+        from .mixit import MixItCriterion
+        criterion = MixItCriterion(snr_max)
     world, rank, device = parallel.init_distributed()
     cfg = dict(PAPER if config is None else config)
     torch.manual_seed(0)
@@ -71,7 +81,7 @@ def train(data, epochs, model_path, save_folder="exp/models", continue_from="", 
     parallel.broadcast_parameters(optimizer.flat_params)
     arg_solver = (1, epochs, half_lr, early_stop, max_grad_norm, save_folder, enable_checkpoint, continue_from,
                   model_path, print_freq, 0, 0, "Conv-TasNet Training")
-    solver = Solver(data, model, optimizer, arg_solver)
+    solver = Solver(data, model, optimizer, arg_solver, criterion=criterion)
     solver.train()
     return solver
 
@@ -115,6 +125,11 @@ def build_parser():
     ap.add_argument("--rir-early-ms", default="50", metavar="MS | full", help="the training targets keep the direct path and the "
                     "reflections of this many milliseconds behind it; full: the reverberant sources.  --noise, --snr, --rirs and "
                     "--rir-early-ms also reach the --dynamic-mix-cv loader (the same banks, reshuffle=False: a fixed validation set)")
+    ap.add_argument("--loss", choices=("pit", "mixit"), default="pit", help="pit: permutation-invariant SI-SNR against the "
+                    "sources; mixit: mixture invariant training (needs --dynamic-mix and --dynamic-mix-cv): every minibatch is a "
+                    "4-speaker mixture whose two 2-speaker halves are the only references the loss sees")
+    ap.add_argument("--mixit-outputs", type=int, default=4, metavar="M", help="--loss mixit: the number of model outputs, 2 .. 8")
+    ap.add_argument("--snr-max", default="30", metavar="DB | none", help="--loss mixit: the soft threshold of the SNR loss in dB")
     return ap
 
 
@@ -153,6 +168,16 @@ def main(argv=None):
         raise SystemExit("--speed-perturb applies to --dynamic-mix only")
     if (a.noise or a.rirs) and not a.dynamic_mix:
         raise SystemExit("--noise and --rirs apply to --dynamic-mix only")
+    mixit = a.loss == "mixit"
+    if mixit:
+        if not a.dynamic_mix:
+            raise SystemExit("--loss mixit needs --dynamic-mix: its minibatches are 4-speaker mixtures drawn on the device")
+        if not a.dynamic_mix_cv:
+            raise SystemExit("--loss mixit needs --dynamic-mix-cv: every other validation set would be scored with the PIT "
+                             "criterion against isolated sources, which is not the loss being trained")
+        if not 2 <= a.mixit_outputs <= 8:
+            raise SystemExit("--mixit-outputs must be 2 .. 8")
+    speakers = 4 if mixit else 2
     world, rank, device = parallel.init_distributed()
     tr = cv = None
     if a.dynamic_mix or a.dynamic_mix_cv:
@@ -165,12 +190,15 @@ def main(argv=None):
                 from .resample import parse_speed_range
                 speeds = parse_speed_range(a.speed_perturb)
             tr = DynamicMixLoader(DeviceCorpus.from_manifest(a.dynamic_mix, 8000, device, resample=auto), a.batch_size, a.segment_len,
-                                  steps_per_epoch=a.steps_per_epoch, seed=a.seed, rank=rank, speeds=speeds, rirs=rirs, noise=noise,
-                                  snr_db=snr_db)
+                                  num_speakers=speakers, steps_per_epoch=a.steps_per_epoch, seed=a.seed, rank=rank, speeds=speeds,
+                                  rirs=rirs, noise=noise, snr_db=snr_db)
         if a.dynamic_mix_cv:
             cv = DynamicMixLoader(DeviceCorpus.from_manifest(a.dynamic_mix_cv, 8000, device, resample=auto), a.batch_size,
-                                  a.segment_len, steps_per_epoch=a.cv_steps, seed=a.seed + 1, rank=rank, reshuffle=False, rirs=rirs,
-                                  noise=noise, snr_db=snr_db)
+                                  a.segment_len, num_speakers=speakers, steps_per_epoch=a.cv_steps, seed=a.seed + 1, rank=rank,
+                                  reshuffle=False, rirs=rirs, noise=noise, snr_db=snr_db)
+        if mixit:
+            from .mixit import MixtureOfMixtures
+            tr, cv = MixtureOfMixtures(tr), MixtureOfMixtures(cv)
     if a.data_dir:
         from .data import AudioDataLoader, AudioDataset
         if tr is None:
@@ -183,9 +211,14 @@ def main(argv=None):
         tr = SyntheticLoader(a.batches, a.batch_size, rank=rank, world=world)
     if cv is None:
         cv = SyntheticLoader(1, a.batch_size, first_utt=10 ** 6, rank=rank, world=world)
+    config = TINY if a.tiny else None
+    extra = {}
+    if mixit:
+        config = dict(TINY if a.tiny else PAPER, C=a.mixit_outputs)
+        extra = dict(loss="mixit", snr_max=None if a.snr_max.lower() == "none" else float(a.snr_max))
     return train({'tr_loader': tr, 'cv_loader': cv}, a.epochs, a.model_path, save_folder=a.save_folder, lr=a.lr,
-                 optimizer_type=a.optimizer, momentum=a.momentum, l2=a.l2, config=TINY if a.tiny else None,
-                 enable_checkpoint=int(a.checkpoint), continue_from=a.continue_from)
+                 optimizer_type=a.optimizer, momentum=a.momentum, l2=a.l2, config=config,
+                 enable_checkpoint=int(a.checkpoint), continue_from=a.continue_from, **extra)
 
 
 if __name__ == "__main__":

@@ -881,6 +881,31 @@ size_t ctn_stoi_score_workspace(long long B, int C, long long E, long long T);
 int ctn_stoi_score(const double* env, const int* kcount, long long B, int C, long long E, long long T, double* d_stoi,
                    double* d_estoi, int* m_out, int* k_out, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- mixture invariant training loss (csrc/ctn_mixit.hip) --------------------------------------------------------------------
+ * S. Wisdom et al., "Unsupervised Sound Separation Using Mixture Invariant Training", NeurIPS 2020 (MixIT), with the paper's
+ * soft-thresholded SNR (no mean removal: SNR, not SI-SNR).  mixtures: [B,2,T] fp32, the two reference mixtures; estimates:
+ * [B,M,T] fp32, 2 <= M <= 8, NOT modified; lengths: [B] int64, clamped to [0, T], only t < len counts; tau = 10^(-snr_max/10)
+ * >= 0 (0: no threshold).  An assignment a in [0, 2^M) sends source i to mixture (a >> i) & 1 (a mixture may get no source):
+ *     err_n = sum_t (sum_{i in A_n} e_i - x_n)^2,  Xx_n = sum_t x_n^2,  l_n = 10 log10((err_n + tau Xx_n + 1e-8) / (Xx_n + 1e-8)),
+ *     L(a) = (l_0 + l_1) / 2;  assign [B] int64 = the first a, ascending, that attains min_a L(a) (fp64, strict <),
+ *     per_utt [B] = L(assign), snr [B,2] = -l_n(assign), loss [1] = mean_b per_utt (fp64 mean, rounded once),
+ *     coef [B,2] = c_n = (10 / ln 10) / (err_n + tau Xx_n + 1e-8): the backward table.  len = 0: per_utt = 0, assign = 0.
+ * Forward: one sweep collects the fp64 moments G = e e^T (upper triangle), Xe = x e^T and Xx per utterance and time chunk
+ * (ctn_sisnr_chunks(T) chunks: the partition depends on T alone, so an utterance's result is bitwise the same in any batch, at
+ * any batch index and for any pointer alignment), then the 2^M assignments are scored on those scalars.  Rows are read 16 bytes
+ * per lane when T % 4 == 0 and the base pointers are 16-byte aligned.  workspace: ctn_mixit_workspace() bytes (0: bad sizes).
+ * Backward: d_estimates[b,i,t] = [t < len] * scale_b * c_n * (sum_{k in A_n} e_k[t] - x_n[t]), n = bit i of assign[b], the
+ * remix added in fp32 in ascending k; scale_b = g_loss[0] / B + g_per[b] for upstream gradients g_loss [1] of loss and g_per [B]
+ * of per_utt (either may be NULL).  Fixed-order reductions, no atomics, no read-back, no synchronisation: graph-capturable.
+ * Arguments are checked before any launch (CTN_ERR_ARG). */
+size_t ctn_mixit_workspace(int B, int M, int T);
+int ctn_mixit_fwd(const float* mixtures, const float* estimates, const long long* lengths, int B, int M, int T, double tau,
+                  float* per_utt, long long* assign, float* snr, float* loss, float* coef, void* workspace,
+                  size_t workspace_bytes, void* stream);
+int ctn_mixit_bwd(const float* mixtures, const float* estimates, const long long* lengths, const long long* assign,
+                  const float* coef, const float* g_loss, const float* g_per, int B, int M, int T, float* d_estimates,
+                  void* stream);
+
 #ifdef __cplusplus
 }
 #endif
