@@ -14,7 +14,10 @@ def _pit(source, estimate_source, source_lengths):
 
 
 def cal_loss(source, estimate_source, source_lengths):
-    """-> (loss, max_snr [B,1], estimate_source masked IN PLACE like the reference, reorder_estimate_source)."""
+    """-> (loss, max_snr [B,1], estimate_source masked IN PLACE like the reference, reorder_estimate_source).
+
+    The kernel sums the source over t < length only; the reference instead divides the full-length sum by the length, so
+    the two agree only for zero-padded sources, which is what every loader here produces."""
     loss, max_snr, est, idx = _pit(source, estimate_source, source_lengths)   # loss = 0 - mean(max_snr), in-kernel
     perms = ops._perms(source.size(1), source.device)[1]
     return loss, max_snr, est, reorder_source(est, perms, idx)

@@ -431,7 +431,10 @@ int ctn_overlap_add_bwd(const float* dout, float* dsignal, int Bn, int frames, i
 /* ---- PIT SI-SNR loss, src/pit_criterion.py:12-77 -----------------------------------------
  * source, estimate: [B,C,T]; lengths: [B] int64; perms: [nperm,C] int32 in itertools order.
  * estimate is masked IN PLACE for t >= len (reference :38).  Outputs: max_snr [B], best_idx [B] int64,
- * loss [1] = -mean(max_snr), snr_out [B,C,C] (optional), and the backward tables coef [B,C,4], jsel [B,C]. */
+ * loss [1] = -mean(max_snr), snr_out [B,C,C] (optional), and the backward tables coef [B,C,4], jsel [B,C].
+ * Source samples at t >= len are never read: every sum, the source mean included, runs over t < len.  The reference
+ * instead divides the source's full-length sum by len (:41), so the two agree only for a source that is zero at
+ * t >= len, which is what every loader here produces. */
 int ctn_sisnr_pit_fwd(const float* source, float* estimate, const long long* lengths, const int* perms, int nperm,
                       int B, int C, int T, float* max_snr, long long* best_idx, float* loss, float* snr_out,
                       float* coef, int* jsel, void* workspace, size_t workspace_bytes, void* stream);

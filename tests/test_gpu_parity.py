@@ -1048,19 +1048,33 @@ def test_gemm_arithmetic_switch_and_its_guards():
     assert e32 < 1e-6 and e6 < 1e-6 and torch.equal(o3, o6) and not torch.equal(o32, o6)
 
 
-@pytest.mark.parametrize("L,N,T,M", [(20, 256, 8000, 2), (16, 72, 3001, 3), (32, 64, 5000, 1), (40, 100, 4444, 2)])
+@pytest.mark.parametrize("L,N,T,M", [(20, 256, 8000, 2), (16, 72, 3001, 3), (32, 64, 5000, 1), (40, 100, 4444, 2),
+                                     (20, 64, 20, 2),       # T = L: a single frame
+                                     (32, 65, 47, 3),       # T = L + S - 1: the last, partial hop is dropped (K = 1); N = 65
+                                     (16, 65, 2056, 1),     # K = 256: exactly one block of frames; one channel past a block of 64
+                                     (16, 65, 2067, 2)])    # K = 257: one frame in the second block, and 3 samples left over
 def test_encoder_kernel_matches_conv1d(L, N, T, M):
     """ctn_encoder_fwd (sliding windows staged in LDS, no im2col buffer) against torch's Conv1d(1, N, L, stride L/2) + ReLU
-    in fp64 (src/conv_tasnet.py:106-121): ragged frame count, channel counts that do not fill the 64-channel block."""
+    in fp64 (src/conv_tasnet.py:106-121): ragged frame count, channel counts that do not fill the 64-channel block, the
+    edges of the 256-frame and 64-channel blocks.  The mixture is placed twice inside a larger buffer: once with 1e30 right
+    behind its last sample, so that a read past T shows up as garbage in frame K-1 (or as the next row's samples) and not as
+    a fault, and once with its last row ending where the allocation ends."""
     K = (T - L) // (L // 2) + 1
     Kp = ops.padded_frames(K)
     mix = torch.randn(M, T, generator=g(41))
     U = torch.randn(N, 1, L, generator=g(42)) * 0.3
     ref = torch.relu(torch.nn.functional.conv1d(mix.double().unsqueeze(1), U.double(), stride=L // 2))
-    w = torch.full((M, N, Kp), 7.0, device=DEV)
-    mix_d, U_d = mix.to(DEV), U.to(DEV)          # (named: a temporary's memory may be recycled before the kernel runs)
-    ctn.lib.call("ctn_encoder_fwd", ops._p(mix_d), ops._p(U_d), ops._p(w), M, T, N, L, K, Kp, ops._stream())
-    assert rel_err(w[..., :K], ref) * tol_scale() < 2e-6            # fp32 FMA chains under either GEMM arithmetic
-    assert float(w[..., K:].abs().max()) == 0.0
+    assert ref.shape == (M, N, K)
+    U_d = U.to(DEV)                              # (named: a temporary's memory may be recycled before the kernel runs)
+    guard = 4096
+    buf = torch.full((guard + M * T + guard,), 1e30, device=DEV)
+    buf[guard:guard + M * T] = mix.flatten().to(DEV)
+    tail = torch.full((guard + M * T,), 1e30, device=DEV)
+    tail[guard:] = mix.flatten().to(DEV)
+    for mix_d in (buf[guard:guard + M * T].view(M, T), tail[guard:].view(M, T)):
+        w = torch.full((M, N, Kp), 7.0, device=DEV)
+        ctn.lib.call("ctn_encoder_fwd", ops._p(mix_d), ops._p(U_d), ops._p(w), M, T, N, L, K, Kp, ops._stream())
+        assert rel_err(w[..., :K], ref) * tol_scale() < 2e-6            # fp32 FMA chains under either GEMM arithmetic
+        assert float(w[..., K:].abs().max()) == 0.0 if Kp > K else True
     with pytest.raises(ctn.CtnError):
         ctn.lib.call("ctn_encoder_fwd", ops._p(mix_d), ops._p(U_d), ops._p(w), M, T, N, 24, K, Kp, ops._stream())
