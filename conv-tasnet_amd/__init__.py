@@ -19,5 +19,7 @@ from .longform import separate_long, frame_ragged, stitch_ragged, plan_segments,
 from .stoi import stoi, stoi_batch, stoi_both, stoi_improvement  # noqa: F401  (ctn.stoi is the function; the module: conv_tasnet_amd.stoi)
 from . import mixit  # noqa: F401
 from .mixit import cal_mixit_loss, remix, pair_batch, MixtureOfMixtures, MixItCriterion  # noqa: F401
+from . import varpit  # noqa: F401
+from .varpit import cal_varpit_loss, VarPitCriterion, output_levels, count_sources, evaluate_variable  # noqa: F401
 
 __version__ = "0.1.0"

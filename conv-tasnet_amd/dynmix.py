@@ -239,10 +239,14 @@ class DynamicMixLoader:
     per mixture) at an SNR drawn uniformly from the tenths of a dB in snr_db = (lo, hi), relative to the sources' 0-dB reference
     level (unit RMS, before the plan's +-q).  The peak rescale to 0.9 covers the noisy mixture and the targets.
     With either option the mix is ctn_dynmix_gather_aug, which has the chunked form only (gather_mode plays no part).
-    With rirs=None and noise=None the launches and the bits are those of a loader without these arguments."""
+    With rirs=None and noise=None the launches and the bits are those of a loader without these arguments.
+    min_speakers: None, or m in [1, num_speakers]: every mixture holds a drawn number n_b in [m, C] of speakers (one more Philox
+    block per mixture, csrc/ctn_dynmix_active.hip); the plan is that of min_speakers=None with gain[b, c >= n_b] = 0, so
+    sources[b, c >= n_b] are zeros that add nothing to the mixture or its peak: training data for varpit.cal_varpit_loss.
+    `last_active()` returns the counts.  With None the launches and the bits are those of a loader without the argument."""
 
     def __init__(self, corpus, batch_size, segment_len, num_speakers=2, steps_per_epoch=1000, seed=0, rank=None,
-                 reshuffle=True, gather_mode=None, speeds=None, rirs=None, noise=None, snr_db=(-6, 3)):
+                 reshuffle=True, gather_mode=None, speeds=None, rirs=None, noise=None, snr_db=(-6, 3), min_speakers=None):
         if rank is None:
             from . import parallel
             rank = torch.distributed.get_rank() if parallel.world_size() > 1 else parallel.env_world()[1]
@@ -255,6 +259,8 @@ class DynamicMixLoader:
             raise ValueError("mixtures of 2..4 speakers, got %d" % num_speakers)
         if batch_size < 1 or steps_per_epoch < 1:
             raise ValueError("batch_size and steps_per_epoch must be positive")
+        if min_speakers is not None and not 1 <= int(min_speakers) <= int(num_speakers):
+            raise ValueError("min_speakers must be in [1, %d], got %r" % (num_speakers, min_speakers))
         self.corpus, self.B, self.T, self.C = corpus, int(batch_size), int(segment_len), int(num_speakers)
         self.steps_per_epoch, self.seed, self.rank, self.reshuffle = int(steps_per_epoch), seed, rank, bool(reshuffle)
         self.gather_mode = GATHER_MODE if gather_mode is None else int(gather_mode)
@@ -283,6 +289,9 @@ class DynamicMixLoader:
         self._aug = None
         if rirs is not None or noise is not None:
             self._aug = _Augment(self.B, self.C, self.T, dev, rirs, noise, snr_db)
+        self.min_speakers = None if min_speakers is None else int(min_speakers)
+        if self.min_speakers is not None:
+            self._n_active = torch.zeros(self.B, dtype=torch.int32, device=dev)
 
     # Solver: loader.dataset.set_epoch(epoch).  A property, not an attribute: `self.dataset = self` is a reference cycle, and a
     # dropped loader's device buffers would then stay allocated until the cyclic collector happens to run
@@ -307,6 +316,9 @@ class DynamicMixLoader:
         stream = torch.cuda.current_stream(self.device).cuda_stream
         if aug is not None:
             aug.plan(self.seed, self.epoch, self.rank, self._step, stream)          # reads the step word, leaves it alone
+        if self.min_speakers is not None:                                           # likewise
+            lib.call("ctn_dynmix_plan_active", self.seed, self.epoch, self.rank, _ptr(self._step), B, C, self.min_speakers,
+                     _ptr(self._n_active), stream)
         if self.speeds is not None:
             lib.call("ctn_dynmix_plan_speed", _ptr(self._spk_ptr), _ptr(self._utt_ids), len(self.tables["spk_ptr"]) - 1,
                      _ptr(c.lens), _ptr(c.inv_rms), _ptr(c.w), _ptr(self._pct), len(self.speeds), self.seed, self.epoch, self.rank,
@@ -316,6 +328,8 @@ class DynamicMixLoader:
             lib.call("ctn_dynmix_plan", _ptr(self._spk_ptr), _ptr(self._utt_ids), len(self.tables["spk_ptr"]) - 1, _ptr(c.lens),
                      _ptr(c.inv_rms), _ptr(c.w), self.seed, self.epoch, self.rank, _ptr(self._step), B, C, T,
                      _ptr(self._plan_utt), _ptr(self._plan_start), _ptr(self._plan_q), _ptr(self._gain), stream)
+        if self.min_speakers is not None:
+            lib.call("ctn_dynmix_mask_active", _ptr(self._n_active), B, C, _ptr(self._gain), stream)
         if aug is not None:                  # speed_segments -> reverb -> gather_aug (include/ctn_hip.h: the pipeline of one step)
             if self.speeds is not None:
                 self._seg.segments(c, self._banks, self._plan_utt, self._plan_start, self._plan_pct, stream)
@@ -347,6 +361,12 @@ class DynamicMixLoader:
         and with speeds the drawn percents plan_pct [B,C] i32 as a fifth element."""
         plan = self._plan_utt.clone(), self._plan_start.clone(), self._plan_q.clone(), self._gain.clone()
         return plan if self.speeds is None else plan + (self._plan_pct.clone(),)
+
+    def last_active(self):
+        """A copy of the last minibatch's speaker counts n_active [B] i32 (min_speakers only)."""
+        if self.min_speakers is None:
+            raise ValueError("this loader was built without min_speakers: every mixture holds %d speakers" % self.C)
+        return self._n_active.clone()
 
     def last_peak(self):
         """peak [B] of the last minibatch before the rescale to 0.9."""

@@ -50,24 +50,29 @@ class SyntheticLoader:
 
 def train(data, epochs, model_path, save_folder="exp/models", continue_from="", config=None, lr=1e-3,
           max_grad_norm=5, half_lr=1, early_stop=1, print_freq=10, enable_checkpoint=0, optimizer_type='adam',
-          momentum=0.0, l2=0.0, loss='pit', snr_max=30.0):
+          momentum=0.0, l2=0.0, loss='pit', snr_max=30.0, inactive_snr_max=20.0):
     """data = {'tr_loader': ..., 'cv_loader': ...}.  Returns the Solver after training.
 
     loss 'pit': the reference's permutation-invariant SI-SNR against [B,C,T] sources.  loss 'mixit': mixture invariant
     training (mixit.cal_mixit_loss, soft threshold snr_max dB or None): both loaders yield the two reference mixtures
     [B,2,T] in place of the sources (mixit.MixtureOfMixtures) and config['C'] is the number of model outputs, 2 .. 8.
+    loss 'varpit': PIT with inactive sources (varpit.cal_varpit_loss, soft thresholds snr_max and inactive_snr_max dB or None)
+    for loaders whose mixtures hold 1 .. config['C'] speakers, the others' sources being zeros (DynamicMixLoader(min_speakers=)).
 
     optimizer_type 'sgd' -> FlatSGD(lr, momentum, weight_decay=l2), 'adam' -> FlatAdam(lr, weight_decay=l2)
     (src/train.py:87-98); any other value prints 'Not support optimizer' and returns None, as the reference does."""
     if optimizer_type not in ('sgd', 'adam'):
         print("Not support optimizer")
         return None
-    if loss not in ('pit', 'mixit'):
-        raise ValueError("loss must be 'pit' or 'mixit', got %r" % (loss,))
+    if loss not in ('pit', 'mixit', 'varpit'):
+        raise ValueError("loss must be 'pit' or 'mixit' or 'varpit', got %r" % (loss,))
     criterion = None
     if loss == 'mixit':
         from .mixit import MixItCriterion
         criterion = MixItCriterion(snr_max)
+    if loss == 'varpit':
+        from .varpit import VarPitCriterion
+        criterion = VarPitCriterion(snr_max, inactive_snr_max)
     world, rank, device = parallel.init_distributed()
     cfg = dict(PAPER if config is None else config)
     torch.manual_seed(0)
@@ -125,11 +130,19 @@ def build_parser():
     ap.add_argument("--rir-early-ms", default="50", metavar="MS | full", help="the training targets keep the direct path and the "
                     "reflections of this many milliseconds behind it; full: the reverberant sources.  --noise, --snr, --rirs and "
                     "--rir-early-ms also reach the --dynamic-mix-cv loader (the same banks, reshuffle=False: a fixed validation set)")
-    ap.add_argument("--loss", choices=("pit", "mixit"), default="pit", help="pit: permutation-invariant SI-SNR against the "
-                    "sources; mixit: mixture invariant training (needs --dynamic-mix and --dynamic-mix-cv): every minibatch is a "
-                    "4-speaker mixture whose two 2-speaker halves are the only references the loss sees")
+    ap.add_argument("--loss", choices=("pit", "mixit", "varpit"), default="pit", help="pit: permutation-invariant SI-SNR against "
+                    "the sources; mixit: mixture invariant training (needs --dynamic-mix and --dynamic-mix-cv): every minibatch is a "
+                    "4-speaker mixture whose two 2-speaker halves are the only references the loss sees; varpit: PIT with inactive "
+                    "sources for mixtures of --min-speakers .. --speakers talkers (needs --dynamic-mix and --dynamic-mix-cv)")
     ap.add_argument("--mixit-outputs", type=int, default=4, metavar="M", help="--loss mixit: the number of model outputs, 2 .. 8")
-    ap.add_argument("--snr-max", default="30", metavar="DB | none", help="--loss mixit: the soft threshold of the SNR loss in dB")
+    ap.add_argument("--snr-max", default="30", metavar="DB | none", help="--loss mixit / varpit: the soft threshold of the SNR loss "
+                    "in dB")
+    ap.add_argument("--min-speakers", type=int, default=None, metavar="M", help="--dynamic-mix only: every mixture holds a drawn "
+                    "number of speakers in [M, --speakers]; the sources of the others are zeros.  Also reaches --dynamic-mix-cv")
+    ap.add_argument("--speakers", type=int, default=None, metavar="C", help="--loss varpit: the number of model outputs and the "
+                    "largest number of speakers in a mixture, 2 .. 4 (default 2)")
+    ap.add_argument("--inactive-snr-max", default="20", metavar="DB | none", help="--loss varpit: the soft threshold in dB of the "
+                    "loss of an output paired with a silent reference")
     return ap
 
 
@@ -177,7 +190,21 @@ def main(argv=None):
                              "criterion against isolated sources, which is not the loss being trained")
         if not 2 <= a.mixit_outputs <= 8:
             raise SystemExit("--mixit-outputs must be 2 .. 8")
+    varpit = a.loss == "varpit"
+    if a.min_speakers is not None and not a.dynamic_mix:
+        raise SystemExit("--min-speakers applies to --dynamic-mix only")
+    if a.speakers is not None and not varpit:
+        raise SystemExit("--speakers applies to --loss varpit only")
     speakers = 4 if mixit else 2
+    if varpit:
+        if not a.dynamic_mix or not a.dynamic_mix_cv:
+            raise SystemExit("--loss varpit needs --dynamic-mix and --dynamic-mix-cv: mixtures with silent sources are drawn on "
+                             "the device, and every other validation set would be scored with the PIT criterion")
+        speakers = 2 if a.speakers is None else a.speakers
+        if not 2 <= speakers <= 4:
+            raise SystemExit("--speakers must be 2 .. 4")
+    if a.min_speakers is not None and not 1 <= a.min_speakers <= speakers:
+        raise SystemExit("--min-speakers must be 1 .. %d" % speakers)
     world, rank, device = parallel.init_distributed()
     tr = cv = None
     if a.dynamic_mix or a.dynamic_mix_cv:
@@ -191,11 +218,12 @@ def main(argv=None):
                 speeds = parse_speed_range(a.speed_perturb)
             tr = DynamicMixLoader(DeviceCorpus.from_manifest(a.dynamic_mix, 8000, device, resample=auto), a.batch_size, a.segment_len,
                                   num_speakers=speakers, steps_per_epoch=a.steps_per_epoch, seed=a.seed, rank=rank, speeds=speeds,
-                                  rirs=rirs, noise=noise, snr_db=snr_db)
+                                  rirs=rirs, noise=noise, snr_db=snr_db, min_speakers=a.min_speakers)
         if a.dynamic_mix_cv:
             cv = DynamicMixLoader(DeviceCorpus.from_manifest(a.dynamic_mix_cv, 8000, device, resample=auto), a.batch_size,
                                   a.segment_len, num_speakers=speakers, steps_per_epoch=a.cv_steps, seed=a.seed + 1, rank=rank,
-                                  reshuffle=False, rirs=rirs, noise=noise, snr_db=snr_db)
+                                  reshuffle=False, rirs=rirs, noise=noise, snr_db=snr_db,
+                                  min_speakers=a.min_speakers if a.dynamic_mix else None)
         if mixit:
             from .mixit import MixtureOfMixtures
             tr, cv = MixtureOfMixtures(tr), MixtureOfMixtures(cv)
@@ -216,6 +244,10 @@ def main(argv=None):
     if mixit:
         config = dict(TINY if a.tiny else PAPER, C=a.mixit_outputs)
         extra = dict(loss="mixit", snr_max=None if a.snr_max.lower() == "none" else float(a.snr_max))
+    if varpit:
+        config = dict(TINY if a.tiny else PAPER, C=speakers)
+        extra = dict(loss="varpit", snr_max=None if a.snr_max.lower() == "none" else float(a.snr_max),
+                     inactive_snr_max=None if a.inactive_snr_max.lower() == "none" else float(a.inactive_snr_max))
     return train({'tr_loader': tr, 'cv_loader': cv}, a.epochs, a.model_path, save_folder=a.save_folder, lr=a.lr,
                  optimizer_type=a.optimizer, momentum=a.momentum, l2=a.l2, config=config,
                  enable_checkpoint=int(a.checkpoint), continue_from=a.continue_from, **extra)

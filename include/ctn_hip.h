@@ -909,6 +909,50 @@ int ctn_mixit_bwd(const float* mixtures, const float* estimates, const long long
                   const float* coef, const float* g_loss, const float* g_per, int B, int M, int T, float* d_estimates,
                   void* stream);
 
+/* ---- PIT with inactive sources: variable speaker counts (csrc/ctn_varpit.hip) ---------------------------------------------------
+ * A C-output model trained on mixtures of 1 .. C speakers: S. Wisdom et al., "What's all the FUSS about free universal sound
+ * separation data?", ICASSP 2021.  sources: [B,C,T] fp32, a reference row may be all zeros; estimates: [B,C,T] fp32, NOT modified;
+ * lengths: [B] int64, clamped to [0, T], only t < len counts; 2 <= C <= 6; perms: [C!,C] int32 in itertools.permutations order,
+ * nperm = C!, perm[i] = j pairs estimate i with reference j; tau = 10^(-snr_max/10) >= 0, tau0 = 10^(-inactive_snr_max/10) >= 0.
+ * Moments over t < len, no mean removal (SNR, not SI-SNR):
+ *     Ss_j = sum s_j^2,  Ee_i = sum e_i^2,  Es_ij = sum e_i s_j,  Xx = sum_t (sum_j s_j[t])^2  (inner sum in fp64, ascending j):
+ *     the energy of the clean mixture, so the criterion needs nothing beyond (sources, estimates, lengths).
+ * Reference j is active iff Ss_j > 0.  Pair losses:
+ *     active:    l_ij = 10 log10((max(Ss_j - 2 Es_ij + Ee_i, 0) + tau Ss_j + 1e-8) / (Ss_j + 1e-8))
+ *     inactive:  l_ij = 10 log10((Ee_i + tau0 Xx + 1e-8) / (Xx + 1e-8))                 (the same value for every inactive j)
+ *     L(p) = (sum_i l_{i,p(i)}) / C in fp64, ascending i;  perm_idx [B] int64 = the first p in table order that attains min_p L(p)
+ *     (strict <).  Permutations that differ only in which inactive reference an output takes add the same values in the same
+ *     order: their sums are bitwise equal, the tie is exact and the first one wins.
+ *     per_utt [B] = L(perm_idx), pair [B,C,C] = l as fp32, active [B,C] int32, loss [1] = mean_b per_utt (fp64 mean, rounded once),
+ *     coef [B,C,2] = (c_i, a_i): c_i = (20 / ln 10) / D_i with D_i the numerator argument of the chosen pair of estimate i, a_i = 1
+ *     for an active reference and 0 for an inactive one: the backward table.  len = 0: per_utt = 0, perm_idx = 0.
+ * Forward: one sweep collects the C^2 + 2C + 1 fp64 moments per utterance and time chunk (ctn_sisnr_chunks(T) chunks: the
+ * partition depends on T alone, so an utterance's result is bitwise the same in any batch, at any batch index and for any
+ * pointer alignment), then one wave per utterance scores the C! permutations on those scalars.  Rows are read 16 bytes per lane
+ * when T % 4 == 0 and the base pointers are 16-byte aligned.  workspace: ctn_varpit_workspace() bytes (0: bad sizes).
+ * Backward: d_estimates[b,i,t] = [t < len] * (scale_b / C) * c_i * (e_i[t] - a_i s_j[t]), j = perms[perm_idx[b]][i]; scale_b =
+ * g_loss[0] / B + g_per[b] for upstream gradients g_loss [1] of loss and g_per [B] of per_utt (either may be NULL); every fp32
+ * operation rounded once.  Fixed-order reductions, no atomics, no read-back, no synchronisation: graph-capturable.
+ * Arguments are checked before any launch (CTN_ERR_ARG). */
+size_t ctn_varpit_workspace(int B, int C, int T);
+int ctn_varpit_fwd(const float* sources, const float* estimates, const long long* lengths, const int* perms, int nperm, int B,
+                   int C, int T, double tau, double tau0, float* per_utt, long long* perm_idx, float* pair, int* active,
+                   float* loss, float* coef, void* workspace, size_t workspace_bytes, void* stream);
+int ctn_varpit_bwd(const float* sources, const float* estimates, const long long* lengths, const int* perms,
+                   const long long* perm_idx, const float* coef, const float* g_loss, const float* g_per, int B, int C, int T,
+                   float* d_estimates, void* stream);
+
+/* ---- variable speaker counts in the dynamic mixer (csrc/ctn_dynmix_active.hip) ---------------------------------------------------
+ * ctn_dynmix_plan_active: n_active[b] = min_speakers + below(r.w[0], C - min_speakers + 1) with r = philox4x32_10(1024, b, step,
+ *   epoch, k0, k1), key and below() as in ctn_dynmix_plan; 1 <= min_speakers <= C.  The c0 words 0 .. 3, 256 + c, 512 + c and 768
+ *   belong to the other draws, which are untouched.  Launched BEFORE ctn_dynmix_plan / ctn_dynmix_plan_speed on the same stream:
+ *   it reads the step word and leaves it alone.
+ * ctn_dynmix_mask_active: gain[b,c] = +0 for c >= n_active[b], launched behind the plan.  The gather, speed, reverberation and
+ *   noise kernels then run unchanged: a masked source row is zeros and adds nothing to the mixture or its peak. */
+int ctn_dynmix_plan_active(long long seed, int epoch, int rank, const unsigned* step, int B, int C, int min_speakers, int* n_active,
+                           void* stream);
+int ctn_dynmix_mask_active(const int* n_active, int B, int C, float* gain, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
