@@ -187,8 +187,6 @@ __global__ __launch_bounds__(NT) void bn_bwd_apply_kernel(const float* __restric
     }
 }
 
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 }  // namespace
 
 extern "C" {
@@ -201,7 +199,7 @@ int ctn_bn_fwd(const float* Y, float* Out, const float* alpha, const float* gamm
     CTN_REQUIRE(training ? part != nullptr : (running_mean && running_var),
                 "ctn_bn_fwd: training needs the partials workspace, eval needs running statistics");
     CTN_REQUIRE((running_mean == nullptr) == (running_var == nullptr), "ctn_bn_fwd: running_mean / running_var go together");
-    CTN_REQUIRE(aligned16(Y) && aligned16(Out), "ctn_bn_fwd: pointers must be 16-byte aligned");
+    CTN_REQUIRE(ctn_aligned16(Y) && ctn_aligned16(Out), "ctn_bn_fwd: pointers must be 16-byte aligned");
     hipStream_t st = (hipStream_t)stream;
     const dim3 rows((unsigned)(M * ctn_cdiv(Ch, ROWS))), chans((unsigned)ctn_cdiv(Ch, NT));
     if (training) {
@@ -222,7 +220,7 @@ int ctn_bn_bwd(const float* dOut, const float* Y, float* dY, const float* alpha,
     CTN_REQUIRE(dOut && Y && dY && gamma && mr && part && coef && dgamma && dbeta, "ctn_bn_bwd: null pointer");
     CTN_REQUIRE(!alpha || dalpha_part, "ctn_bn_bwd: dalpha_part required with alpha");
     CTN_REQUIRE(M > 0 && Ch > 0 && K > 0 && Kp >= K && Kp % 4 == 0, "ctn_bn_bwd: bad sizes M=%d Ch=%d K=%d Kp=%d", M, Ch, K, Kp);
-    CTN_REQUIRE(aligned16(dOut) && aligned16(Y) && aligned16(dY), "ctn_bn_bwd: pointers must be 16-byte aligned");
+    CTN_REQUIRE(ctn_aligned16(dOut) && ctn_aligned16(Y) && ctn_aligned16(dY), "ctn_bn_bwd: pointers must be 16-byte aligned");
     hipStream_t st = (hipStream_t)stream;
     const dim3 rows((unsigned)(M * ctn_cdiv(Ch, ROWS))), chans((unsigned)ctn_cdiv(Ch, NT));
     hipLaunchKernelGGL(bn_bwd_row_sums_kernel, rows, dim3(NT), 0, st, dOut, Y, alpha, mr, M, Ch, K, Kp, part);

@@ -270,7 +270,6 @@ unsigned grid_for(long long n) {
     if (b < 1) b = 1;
     return (unsigned)b;
 }
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 }  // namespace
 
@@ -309,7 +308,7 @@ int ctn_mask_apply(const float* score, const float* w, float* sw, int M, int C, 
     CTN_REQUIRE(M > 0 && C > 0 && N > 0 && Kp > 0 && Kp % 4 == 0, "ctn_mask_apply: bad sizes");
     CTN_REQUIRE(softmax >= 0 && softmax <= 2, "ctn_mask_apply: mode must be 0 (relu), 1 (softmax) or 2 (identity)");
     CTN_REQUIRE(softmax != 1 || C <= MAXC, "ctn_mask_apply: softmax mask supports at most %d speakers", MAXC);
-    CTN_REQUIRE(aligned16(score) && aligned16(w) && aligned16(sw), "ctn_mask_apply: alignment");
+    CTN_REQUIRE(ctn_aligned16(score) && ctn_aligned16(w) && ctn_aligned16(sw), "ctn_mask_apply: alignment");
     const long long NK = (long long)N * Kp;
     hipLaunchKernelGGL(mask_apply_kernel, dim3(grid_for((long long)M * NK / 4)), dim3(NT), 0, (hipStream_t)stream,
                        score, w, sw, M, C, NK, softmax);
@@ -323,7 +322,7 @@ int ctn_mask_apply_bwd(const float* dsw, const float* score, const float* w, flo
     CTN_REQUIRE(M > 0 && C > 0 && N > 0 && Kp > 0 && Kp % 4 == 0, "ctn_mask_apply_bwd: bad sizes");
     CTN_REQUIRE(softmax >= 0 && softmax <= 2, "ctn_mask_apply_bwd: mode must be 0 (relu), 1 (softmax) or 2 (identity)");
     CTN_REQUIRE(softmax != 1 || C <= MAXC, "ctn_mask_apply_bwd: softmax mask supports at most %d speakers", MAXC);
-    CTN_REQUIRE(aligned16(dsw) && aligned16(score) && aligned16(w) && aligned16(dscore) && aligned16(dw), "ctn_mask_apply_bwd: alignment");
+    CTN_REQUIRE(ctn_aligned16(dsw) && ctn_aligned16(score) && ctn_aligned16(w) && ctn_aligned16(dscore) && ctn_aligned16(dw), "ctn_mask_apply_bwd: alignment");
     const long long NK = (long long)N * Kp;
     hipLaunchKernelGGL(mask_apply_bwd_kernel, dim3(grid_for((long long)M * NK / 4)), dim3(NT), 0, (hipStream_t)stream,
                        dsw, score, w, dscore, dw, M, C, NK, softmax);

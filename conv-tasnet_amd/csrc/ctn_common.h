@@ -36,6 +36,8 @@ void ctn_set_error(const char* fmt, ...);
 
 static inline int ctn_cdiv(int a, int b) { return (a + b - 1) / b; }
 static inline long long ctn_cdivll(long long a, long long b) { return (a + b - 1) / b; }
+// the 16-byte (float4, packed-operand) paths take nothing else; host and device
+__host__ __device__ static inline bool ctn_aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
 
 // ---- chained weight gradients (library-internal: the composite stacks of ctn_block.hip call these, ctn_gemm.hip defines them) ----
 // A chained launch leaves its split-K slabs unsummed and records them in *chain; the next chained launch ON THE SAME STREAM sums

@@ -582,7 +582,7 @@ int ctn_pw_gemm(const float* W, const float* X, float* Out, int M, int R, int Cn
     CTN_REQUIRE(!(residual && epi_part), "ctn_pw_gemm: residual and stats epilogues are exclusive");
     CTN_REQUIRE(!pro_part || (pro_gamma && pro_beta && pro_alpha && pro_nparts > 0), "ctn_pw_gemm: incomplete prologue arguments");
     CTN_REQUIRE(!epi_part || epi_alpha, "ctn_pw_gemm: stats epilogue needs alpha");
-    CTN_REQUIRE(!residual || aligned16(residual), "ctn_pw_gemm: residual must be 16-byte aligned");
+    CTN_REQUIRE(!residual || ctn_aligned16(residual), "ctn_pw_gemm: residual must be 16-byte aligned");
     PwArgs a{};
     a.W = W; a.X = X; a.Out = Out; a.M = M; a.R = R; a.Cn = Cn; a.K = K; a.Kp = Kp;
     a.pro_part = pro_part; a.pro_nparts = pro_nparts; a.pro_gamma = pro_gamma; a.pro_beta = pro_beta;
@@ -607,7 +607,7 @@ static int dgrad_gln(const char* fn, const float* W, int planes, const float* dO
     int rc = check_common(fn, W, dOut, dN, M, R, Cn, K, Kp);
     if (rc) return rc;
     CTN_REQUIRE(y && gamma && alpha && ms && sums_part, "%s: null pointer", fn);
-    CTN_REQUIRE(aligned16(y), "%s: y must be 16-byte aligned", fn);
+    CTN_REQUIRE(ctn_aligned16(y), "%s: y must be 16-byte aligned", fn);
     CTN_REQUIRE(!planes || b3_fwd(R), "%s: pre-split weight pieces need the b3 arithmetic and R >= 64", fn);
     PwArgs a{};
     a.W = W; a.X = dOut; a.Out = dN; a.M = M; a.R = R; a.Cn = Cn; a.K = K; a.Kp = Kp;
@@ -640,7 +640,7 @@ size_t ctn_split_b3_bytes(int R, int Cn) { return ctn_b3_planes_bytes(arith_np()
 // k_major = 1: src is stored [Cn, R] (its transpose is the operand).  HOST arrays of device pointers; see include/ctn_hip.h.
 int ctn_split_b3_batch(const void* const* src, void* const* dst, int n, int R, int Cn, int k_major, void* stream) {
     CTN_REQUIRE(src && dst && n > 0 && R > 0 && Cn > 0, "ctn_split_b3_batch: bad arguments");
-    for (int i = 0; i < n; ++i) CTN_REQUIRE(src[i] && dst[i] && aligned16(dst[i]), "ctn_split_b3_batch: matrix %d: null or unaligned pointer", i);
+    for (int i = 0; i < n; ++i) CTN_REQUIRE(src[i] && dst[i] && ctn_aligned16(dst[i]), "ctn_split_b3_batch: matrix %d: null or unaligned pointer", i);
     CTN_REQUIRE(arith_np() != 0, "ctn_split_b3_batch: the fp32-MFMA arithmetic has no piece form");
     ctn_b3_launch_split(arith_np(), src, dst, n, R, Cn, k_major, (hipStream_t)stream);
     CTN_CHECK_LAUNCH("ctn_split_b3_batch");
@@ -799,7 +799,7 @@ size_t ctn_split_h3_bytes(int R, int Cn) { return ctn_b3_planes_bytes(4, R, Cn);
 
 int ctn_split_h3_batch(const void* const* src, void* const* dst, int n, int R, int Cn, int k_major, void* stream) {
     CTN_REQUIRE(src && dst && n > 0 && R > 0 && Cn > 0 && (R * Cn) % 4 == 0, "ctn_split_h3_batch: bad arguments");
-    for (int i = 0; i < n; ++i) CTN_REQUIRE(src[i] && dst[i] && aligned16(src[i]) && aligned16(dst[i]), "ctn_split_h3_batch: matrix %d: null or unaligned pointer", i);
+    for (int i = 0; i < n; ++i) CTN_REQUIRE(src[i] && dst[i] && ctn_aligned16(src[i]) && ctn_aligned16(dst[i]), "ctn_split_h3_batch: matrix %d: null or unaligned pointer", i);
     ctn_b3_launch_split(4, src, dst, n, R, Cn, k_major, (hipStream_t)stream);
     CTN_CHECK_LAUNCH("ctn_split_h3_batch");
     return CTN_OK;
@@ -807,14 +807,14 @@ int ctn_split_h3_batch(const void* const* src, void* const* dst, int n, int R, i
 
 int ctn_absmax_batch(const void* const* src, void* const* dst, int n, int len, void* stream) {
     CTN_REQUIRE(src && dst && n > 0 && len > 0, "ctn_absmax_batch: bad arguments");
-    for (int i = 0; i < n; ++i) CTN_REQUIRE(src[i] && dst[i] && aligned16(src[i]), "ctn_absmax_batch: array %d: null or unaligned pointer", i);
+    for (int i = 0; i < n; ++i) CTN_REQUIRE(src[i] && dst[i] && ctn_aligned16(src[i]), "ctn_absmax_batch: array %d: null or unaligned pointer", i);
     ctn_b3_launch_absmax(src, dst, 0, n, len, (hipStream_t)stream);
     CTN_CHECK_LAUNCH("ctn_absmax_batch");
     return CTN_OK;
 }
 
 int ctn_absmax_rows(const float* x, int M, long long n, unsigned* amax, void* stream) {
-    CTN_REQUIRE(x && amax && M > 0 && n > 0 && n % 4 == 0 && aligned16(x), "ctn_absmax_rows: bad arguments");
+    CTN_REQUIRE(x && amax && M > 0 && n > 0 && n % 4 == 0 && ctn_aligned16(x), "ctn_absmax_rows: bad arguments");
     int nb = (int)ctn_cdivll(n, 1024 * 8);
     if (nb > 256) nb = 256;
     hipLaunchKernelGGL(absmax_rows_kernel, dim3(nb, M), dim3(256), 0, (hipStream_t)stream, x, n, amax);
@@ -833,7 +833,7 @@ int ctn_pw_gemm_h3(const void* Wp, const float* X, float* Out, int M, int R, int
     CTN_REQUIRE(!(residual && epi_part), "ctn_pw_gemm_h3: residual and stats epilogues are exclusive");
     CTN_REQUIRE(!pro_part || (pro_gamma && pro_beta && pro_alpha && pro_nparts > 0 && pro_gbmax), "ctn_pw_gemm_h3: incomplete prologue arguments");
     CTN_REQUIRE(!epi_part || epi_alpha, "ctn_pw_gemm_h3: stats epilogue needs alpha");
-    CTN_REQUIRE(!residual || aligned16(residual), "ctn_pw_gemm_h3: residual must be 16-byte aligned");
+    CTN_REQUIRE(!residual || ctn_aligned16(residual), "ctn_pw_gemm_h3: residual must be 16-byte aligned");
     CTN_REQUIRE(!out_amax || residual, "ctn_pw_gemm_h3: out_amax comes with the residual epilogue");
     PwArgs a{};
     a.W = (const float*)Wp; a.X = X; a.Out = Out; a.M = M; a.R = R; a.Cn = Cn; a.K = K; a.Kp = Kp;
@@ -853,7 +853,7 @@ int ctn_pw_dgrad_gln_h3(const void* Wp, const float* dOut, float* dN, int M, int
     int rc = check_common("ctn_pw_dgrad_gln_h3", (const float*)Wp, dOut, dN, M, R, Cn, K, Kp);
     if (rc) return rc;
     CTN_REQUIRE(y && gamma && alpha && ms && sums_part && g_amax, "ctn_pw_dgrad_gln_h3: null pointer");
-    CTN_REQUIRE(aligned16(y) && R >= 64, "ctn_pw_dgrad_gln_h3: y must be 16-byte aligned, R >= 64");
+    CTN_REQUIRE(ctn_aligned16(y) && R >= 64, "ctn_pw_dgrad_gln_h3: y must be 16-byte aligned, R >= 64");
     PwArgs a{};
     a.W = (const float*)Wp; a.X = dOut; a.Out = dN; a.M = M; a.R = R; a.Cn = Cn; a.K = K; a.Kp = Kp;
     a.bwd_y = y; a.bwd_gamma = gamma; a.bwd_alpha = alpha; a.bwd_ms = ms; a.bwd_part = sums_part;
@@ -884,7 +884,7 @@ int ctn_pw_dgrad_cln(const void* W, int w_form, const float* dOut, float* dN, in
     if (rc) return rc;
     CTN_REQUIRE(w_form >= 1 && w_form <= 3, "ctn_pw_dgrad_cln: w_form must be 1 (fp32 [Cn, R]), 2 (b6 pieces) or 3 (h3 pieces)");
     CTN_REQUIRE(y && gamma && alpha && mean && rstd && col_part, "ctn_pw_dgrad_cln: null pointer");
-    CTN_REQUIRE(aligned16(y) && aligned16(mean) && aligned16(rstd) && aligned16(col_part), "ctn_pw_dgrad_cln: y, mean, rstd, col_part must be 16-byte aligned");
+    CTN_REQUIRE(ctn_aligned16(y) && ctn_aligned16(mean) && ctn_aligned16(rstd) && ctn_aligned16(col_part), "ctn_pw_dgrad_cln: y, mean, rstd, col_part must be 16-byte aligned");
     CTN_REQUIRE(w_form != 3 || (g_amax && R >= 64), "ctn_pw_dgrad_cln: h3 pieces need the operand's maximum and R >= 64");
     CTN_REQUIRE(w_form != 2 || b3_fwd(R), "ctn_pw_dgrad_cln: b6 pieces need a split-bf16 arithmetic and R >= 64");
     PwArgs a{};
@@ -913,7 +913,7 @@ int ctn_pw_dgrad_gln2(const void* W, int w_form, const float* dOut, float* dN, i
     if (rc) return rc;
     CTN_REQUIRE(w_form >= 1 && w_form <= 3, "ctn_pw_dgrad_gln2: w_form must be 1 (fp32 [Cn, R]), 2 (b6 pieces) or 3 (h3 pieces)");
     CTN_REQUIRE(y && gamma && alpha && ms && gamma1 && beta1 && D && sums_part, "ctn_pw_dgrad_gln2: null pointer");
-    CTN_REQUIRE(aligned16(y) && P >= 1 && P <= 8 && dilation >= 1, "ctn_pw_dgrad_gln2: y must be 16-byte aligned, 1 <= P <= 8");
+    CTN_REQUIRE(ctn_aligned16(y) && P >= 1 && P <= 8 && dilation >= 1, "ctn_pw_dgrad_gln2: y must be 16-byte aligned, 1 <= P <= 8");
     CTN_REQUIRE(w_form != 3 || (g_amax && R >= 64), "ctn_pw_dgrad_gln2: h3 pieces need the operand's maximum and R >= 64");
     CTN_REQUIRE(w_form != 2 || b3_fwd(R), "ctn_pw_dgrad_gln2: b6 pieces need a split-bf16 arithmetic and R >= 64");
     const int halo = (P - 1) * dilation;
@@ -939,7 +939,7 @@ int ctn_pw_gemm_cln(const void* W, int w_form, const float* X, float* Out, int M
     int rc = check_common("ctn_pw_gemm_cln", (const float*)W, X, Out, M, R, Cn, K, Kp);
     if (rc) return rc;
     CTN_REQUIRE(w_form >= 0 && w_form <= 3, "ctn_pw_gemm_cln: w_form must be 0 (fp32 [R, Cn]), 1 (fp32 [Cn, R]), 2 (b6 pieces) or 3 (h3 pieces)");
-    CTN_REQUIRE(alpha && col_part && aligned16(col_part), "ctn_pw_gemm_cln: null or unaligned pointer");
+    CTN_REQUIRE(alpha && col_part && ctn_aligned16(col_part), "ctn_pw_gemm_cln: null or unaligned pointer");
     CTN_REQUIRE(w_form != 3 || (x_amax && R >= 64), "ctn_pw_gemm_cln: h3 pieces need the operand's maximum and R >= 64");
     CTN_REQUIRE(w_form != 2 || b3_fwd(R), "ctn_pw_gemm_cln: b6 pieces need a split-bf16 arithmetic and R >= 64");
     PwArgs a{};

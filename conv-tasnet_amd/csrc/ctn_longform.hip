@@ -37,8 +37,6 @@ __host__ __device__ inline long long lf_nseg(long long T, long long seg, long lo
     return T <= seg ? 1 : 1 + (T - seg + hop - 1) / hop;
 }
 
-__host__ __device__ inline bool lf_aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
 // the recording r in [0, R) with seg_ptr[r] <= s < seg_ptr[r + 1], or -1 when the device table has no such entry (only entries
 // 0 .. R of seg_ptr are read, whatever they hold)
 __device__ __forceinline__ long long lf_find_rec(const long long* __restrict__ seg_ptr, long long R, long long s) {
@@ -75,7 +73,7 @@ __global__ __launch_bounds__(LF_NT) void longform_frame_kernel(const float* __re
     const long long left = T - i * hop - u0;                                // samples of the recording from u0 on (may be <= 0)
     const float* __restrict__ src = x + io + i * hop + u0;
     float* __restrict__ dst = segs + s * seg + u0;
-    if (lf_aligned16(src) && lf_aligned16(dst)) {
+    if (ctn_aligned16(src) && ctn_aligned16(dst)) {
         for (int k = 4 * threadIdx.x; k < n; k += 4 * LF_NT) {
             if (k + 4 <= n && k + 4 <= left) {
                 *reinterpret_cast<float4*>(dst + k) = *reinterpret_cast<const float4*>(src + k);
@@ -122,8 +120,8 @@ __global__ __launch_bounds__(LF_NT) void longform_costs_kernel(const float* __re
     const int ov = seg - hop;
     const float* const prev = est + (s - 1) * C * seg + hop;                // row a: prev + a * seg
     const float* const cur = est + s * C * seg;                             // row b: cur + b * seg
-    const bool pvec = lf_aligned16(prev) && (seg & 3) == 0;
-    const bool cvec = lf_aligned16(cur) && (seg & 3) == 0;
+    const bool pvec = ctn_aligned16(prev) && (seg & 3) == 0;
+    const bool cvec = ctn_aligned16(cur) && (seg & 3) == 0;
     float acc[C * C][4];
 #pragma unroll
     for (int p = 0; p < C * C; ++p)
@@ -267,7 +265,7 @@ __global__ __launch_bounds__(LF_NT) void longform_assemble_kernel(const float* _
     const int n = (int)min((long long)LF_CHUNK, own - u0);
     const int ov = seg - hop;
     const int nfade = i >= 1 ? (int)max(0LL, min((long long)n, ov - u0)) : 0;   // leading samples of this chunk that are cross-faded
-    const bool tvec = lf_aligned16(fi + u0) && lf_aligned16(fo + u0);
+    const bool tvec = ctn_aligned16(fi + u0) && ctn_aligned16(fo + u0);
     for (int a = 0; a < C; ++a) {
         const int gc = g[s * C + a];
         if ((unsigned)gc >= (unsigned)C) continue;                          // never an address from a bad order entry
@@ -279,7 +277,7 @@ __global__ __launch_bounds__(LF_NT) void longform_assemble_kernel(const float* _
             if ((unsigned)gp >= (unsigned)C) continue;
             prv = est + ((s - 1) * C + gp) * seg + hop + u0;
         }
-        const bool vec = lf_aligned16(cur) && lf_aligned16(dst) && (nfade == 0 || (tvec && lf_aligned16(prv)));
+        const bool vec = ctn_aligned16(cur) && ctn_aligned16(dst) && (nfade == 0 || (tvec && ctn_aligned16(prv)));
         if (vec) {
             const int nf4 = nfade & ~3, n4 = n & ~3;                        // whole float4 groups of the fade and of the chunk
             for (int k = 4 * threadIdx.x; k < n4; k += 4 * LF_NT) {

@@ -13,17 +13,14 @@
 //   keeps the first minimum and emits per_utt, assign, snr, the mean loss and the backward coefficients c_n.
 // Backward: d_e[b,i,t] = [t < len] * scale_b * c_n * (sum_{k in A_n} e_k[t] - x_n[t]),  n = bit i of assign_b.
 //
-// The textbook form materialises the [B, 2^M, 2, T] remixes; this one needs none.  The time partition and the lane that owns
-// a sample depend on T alone, and the aligned (16 bytes per lane) and the scalar load paths add the same values in the same
-// order, so an utterance's result is bitwise the same in any batch, at any batch index and at any alignment.
-#include "ctn_common.h"
-
-extern "C" int ctn_sisnr_chunks(int T);      // csrc/ctn_loss.hip: the time partition, a function of T alone
+// The textbook form materialises the [B, 2^M, 2, T] remixes; this one needs none.  The sweep, the reductions, the first-minimum
+// rule and the load and store paths are the skeleton of ctn_moment_loss.h, shared with ctn_varpit.hip; it keeps the promise that
+// an utterance's result is bitwise the same in any batch, at any batch index and at any alignment.  This file holds MixIT's own
+// algebra: which moments, the 2^M enumeration, the coefficients and the backward body.
+#include "ctn_moment_loss.h"
 
 namespace {
 
-constexpr int NT = 256;            // moments and backward kernels
-constexpr int NTA = 1024;          // assignment kernel: 16 waves, one utterance per wave at a time
 constexpr int MINM = 2, MAXM = 8;
 constexpr double EPSD = 1e-8;
 
@@ -32,74 +29,23 @@ __host__ __device__ constexpr int g_at(int M, int i, int k) { return i * M - i *
 __host__ __device__ constexpr int xe_at(int M, int n, int i) { return M * (M + 1) / 2 + n * M + i; }
 __host__ __device__ constexpr int xx_at(int M, int n) { return M * (M + 1) / 2 + 2 * M + n; }
 
-struct Quad { float v[4]; };
-
-// four consecutive samples of one row starting at t (t % 4 == 0); samples at or beyond `len` read as 0 and are not touched
-template <bool VEC>
-__device__ __forceinline__ Quad load4(const float* __restrict__ row, int t, int len) {
-    Quad q;
-    if (VEC && t + 4 <= len) {
-        const float4 f = *reinterpret_cast<const float4*>(row + t);
-        q.v[0] = f.x; q.v[1] = f.y; q.v[2] = f.z; q.v[3] = f.w;
-    } else {
+// the sweep's policy: the rows x [2,T] and e [M,T] of an utterance, sample j of the loaded quads
+template <int M>
+struct MixitMoments {
+    static constexpr int NREF = 2, NEST = M, NV = nmom(M);
+    static __device__ __forceinline__ void accumulate(double (&acc)[NV], const Quad (&xv)[2], const Quad (&ev)[M], int j) {
 #pragma unroll
-        for (int j = 0; j < 4; ++j) q.v[j] = t + j < len ? row[t + j] : 0.f;
-    }
-    return q;
-}
-
-// partial[b][chunk][nmom(M)]; chunk % 4 == 0.  Lane tid owns the quads (t0 + 4 tid) + 4 NT k of its chunk, in ascending k.
-template <int M, bool VEC>
-__global__ __launch_bounds__(NT) void mixit_moments_kernel(const float* __restrict__ x, const float* __restrict__ e,
-                                                           const long long* __restrict__ lens, int T, int chunk, int nchunk,
-                                                           double* __restrict__ partial) {
-    constexpr int NV = nmom(M);
-    __shared__ double red[NT / 64][NV];
-    const int b = blockIdx.x / nchunk, ch = blockIdx.x % nchunk;
-    const int tid = threadIdx.x;
-    long long ll = lens[b];
-    if (ll > T) ll = T;
-    if (ll < 0) ll = 0;
-    const int len = (int)ll;
-    const int t0 = ch * chunk, t1 = min(min(t0 + chunk, T), len);
-    const float* __restrict__ xb = x + (size_t)b * 2 * T;
-    const float* __restrict__ eb = e + (size_t)b * M * T;
-    double acc[NV];
+        for (int i = 0; i < M; ++i) {
+            const double ei = (double)ev[i].v[j];
 #pragma unroll
-    for (int q = 0; q < NV; ++q) acc[q] = 0.0;
-    for (int t = t0 + 4 * tid; t < t1; t += 4 * NT) {
-        Quad xv[2], ev[M];
+            for (int k = i; k < M; ++k) acc[g_at(M, i, k)] += ei * (double)ev[k].v[j];
 #pragma unroll
-        for (int n = 0; n < 2; ++n) xv[n] = load4<VEC>(xb + (size_t)n * T, t, len);
-#pragma unroll
-        for (int i = 0; i < M; ++i) ev[i] = load4<VEC>(eb + (size_t)i * T, t, len);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-#pragma unroll
-            for (int i = 0; i < M; ++i) {
-                const double ei = (double)ev[i].v[j];
-#pragma unroll
-                for (int k = i; k < M; ++k) acc[g_at(M, i, k)] += ei * (double)ev[k].v[j];
-#pragma unroll
-                for (int n = 0; n < 2; ++n) acc[xe_at(M, n, i)] += (double)xv[n].v[j] * ei;
-            }
-#pragma unroll
-            for (int n = 0; n < 2; ++n) acc[xx_at(M, n)] += (double)xv[n].v[j] * (double)xv[n].v[j];
+            for (int n = 0; n < 2; ++n) acc[xe_at(M, n, i)] += (double)xv[n].v[j] * ei;
         }
-    }
 #pragma unroll
-    for (int q = 0; q < NV; ++q) {
-        const double v = wave_sum(acc[q]);
-        if ((tid & 63) == 0) red[tid >> 6][q] = v;
+        for (int n = 0; n < 2; ++n) acc[xx_at(M, n)] += (double)xv[n].v[j] * (double)xv[n].v[j];
     }
-    __syncthreads();
-    if (tid < NV) {
-        double s = red[0][tid];
-#pragma unroll
-        for (int w = 1; w < NT / 64; ++w) s += red[w][tid];
-        partial[((size_t)b * nchunk + ch) * NV + tid] = s;
-    }
-}
+};
 
 // One block of 16 waves; wave w takes utterances w, w + 16, ...  coef [B,2], snr [B,2].
 __global__ __launch_bounds__(NTA) void mixit_assign_kernel(const double* __restrict__ partial, int B, int M, int nchunk,
@@ -110,17 +56,11 @@ __global__ __launch_bounds__(NTA) void mixit_assign_kernel(const double* __restr
     __shared__ double mo[NW][nmom(MAXM)];
     __shared__ double wsum[NW];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const int nv = nmom(M), na = 1 << M;
+    const int na = 1 << M;
     double local = 0.0;                       // lane 0: sum of this wave's per-utterance losses, ascending b
-    for (int b0 = 0; b0 < B; b0 += NW) {      // block-uniform trip count: the barriers below are reached by every wave
+    for (int b0 = 0; b0 < B; b0 += NW) {      // block-uniform trip count: the barriers of sum_chunks_to_lds are reached by every wave
         const int b = b0 + w;
-        __syncthreads();                      // mo[w] may still be read for the previous utterance
-        if (b < B && lane < nv) {
-            double s = 0.0;
-            for (int ch = 0; ch < nchunk; ++ch) s += partial[((size_t)b * nchunk + ch) * nv + lane];
-            mo[w][lane] = s;
-        }
-        __syncthreads();
+        sum_chunks_to_lds(partial, b, B, nmom(M), nchunk, mo[w]);
         if (b >= B) continue;
         const double* m = mo[w];
         const double xx0 = m[xx_at(M, 0)], xx1 = m[xx_at(M, 1)];
@@ -141,15 +81,9 @@ __global__ __launch_bounds__(NTA) void mixit_assign_kernel(const double* __restr
             const double L = (l0 + l1) * 0.5;
             if (besta == na || L < bestL) { bestL = L; besta = a; bl0 = l0; bl1 = l1; be0 = e0; be1 = e1; }
         }
-        // first minimum over the wave: smaller L wins, equal L -> smaller a (lanes without an assignment carry a = na)
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const double oL = __shfl_xor(bestL, o, 64), ol0 = __shfl_xor(bl0, o, 64), ol1 = __shfl_xor(bl1, o, 64);
-            const double oe0 = __shfl_xor(be0, o, 64), oe1 = __shfl_xor(be1, o, 64);
-            const int oa = __shfl_xor(besta, o, 64);
-            const bool take = oa < na && (besta == na || oL < bestL || (oL == bestL && oa < besta));
-            if (take) { bestL = oL; besta = oa; bl0 = ol0; bl1 = ol1; be0 = oe0; be1 = oe1; }
-        }
+        wave_first_min(bestL, besta, na);
+        const int src = besta & 63;           // the lane whose own first minimum is the winner: its l_n and err_n are the winner's
+        bl0 = __shfl(bl0, src, 64), bl1 = __shfl(bl1, src, 64), be0 = __shfl(be0, src, 64), be1 = __shfl(be1, src, 64);
         if (lane == 0) {
             per_utt[b] = (float)bestL;
             assign[b] = (long long)besta;
@@ -161,14 +95,7 @@ __global__ __launch_bounds__(NTA) void mixit_assign_kernel(const double* __restr
             local += bestL;
         }
     }
-    if (lane == 0) wsum[w] = local;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double tot = wsum[0];
-#pragma unroll
-        for (int k = 1; k < NW; ++k) tot += wsum[k];
-        loss[0] = (float)(tot / (double)B);
-    }
+    mean_over_waves(local, wsum, B, loss);
 }
 
 // Each lane takes four consecutive samples of one utterance: reads the M + 2 rows, writes the M rows of d_e.
@@ -182,14 +109,9 @@ __global__ __launch_bounds__(NT) void mixit_bwd_kernel(const float* __restrict__
     const int b = blockIdx.x / ntile, tile = blockIdx.x % ntile;
     const int t = (tile * NT + threadIdx.x) * 4;
     if (t >= T) return;
-    long long ll = lens[b];
-    if (ll > T) ll = T;
-    if (ll < 0) ll = 0;
-    const int len = (int)ll;
+    const int len = clamped_len(lens, b, T);
     const int a = (int)assign[b];
-    float scale = 0.f;
-    if (g_loss != nullptr) scale = g_loss[0] / (float)B;
-    if (g_per != nullptr) scale += g_per[b];
+    const float scale = upstream_scale(g_loss, g_per, b, B);
     const float wn[2] = {scale * coef[2 * (size_t)b], scale * coef[2 * (size_t)b + 1]};
     const float* __restrict__ xb = x + (size_t)b * 2 * T;
     const float* __restrict__ eb = e + (size_t)b * M * T;
@@ -222,52 +144,9 @@ __global__ __launch_bounds__(NT) void mixit_bwd_kernel(const float* __restrict__
         float o[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) o[j] = t + j < len ? (n ? mix[1].v[j] : mix[0].v[j]) : 0.f;
-        float* __restrict__ dst = db + (size_t)i * T + t;
-        if (VEC) {                              // T % 4 == 0: the whole quad is inside the row
-            *reinterpret_cast<float4*>(dst) = make_float4(o[0], o[1], o[2], o[3]);
-        } else {
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-                if (t + j < T) dst[j] = o[j];
-        }
+        store4<VEC>(db + (size_t)i * T + t, o, t, T);
     }
 }
-
-inline bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
-
-inline int mixit_chunk(int T, int nchunk) { return ctn_cdiv(ctn_cdiv(T, nchunk), 4) * 4; }
-
-template <int M>
-void launch_moments(bool vec, unsigned grid, hipStream_t st, const float* x, const float* e, const long long* lens, int T,
-                    int chunk, int nchunk, double* partial) {
-    if (vec)
-        hipLaunchKernelGGL((mixit_moments_kernel<M, true>), dim3(grid), dim3(NT), 0, st, x, e, lens, T, chunk, nchunk, partial);
-    else
-        hipLaunchKernelGGL((mixit_moments_kernel<M, false>), dim3(grid), dim3(NT), 0, st, x, e, lens, T, chunk, nchunk, partial);
-}
-
-template <int M>
-void launch_bwd(bool vec, unsigned grid, hipStream_t st, const float* x, const float* e, const long long* lens,
-                const long long* assign, const float* coef, const float* g_loss, const float* g_per, int B, int T, int ntile,
-                float* de) {
-    if (vec)
-        hipLaunchKernelGGL((mixit_bwd_kernel<M, true>), dim3(grid), dim3(NT), 0, st, x, e, lens, assign, coef, g_loss, g_per, B, T,
-                           ntile, de);
-    else
-        hipLaunchKernelGGL((mixit_bwd_kernel<M, false>), dim3(grid), dim3(NT), 0, st, x, e, lens, assign, coef, g_loss, g_per, B, T,
-                           ntile, de);
-}
-
-#define MIXIT_DISPATCH(M, CALL)                 \
-    switch (M) {                                \
-        case 2: CALL(2); break;                 \
-        case 3: CALL(3); break;                 \
-        case 4: CALL(4); break;                 \
-        case 5: CALL(5); break;                 \
-        case 6: CALL(6); break;                 \
-        case 7: CALL(7); break;                 \
-        default: CALL(8); break;                \
-    }
 
 }  // namespace
 
@@ -286,18 +165,12 @@ int ctn_mixit_fwd(const float* mixtures, const float* estimates, const long long
     CTN_REQUIRE(M >= MINM && M <= MAXM, "ctn_mixit_fwd: M = %d outside %d .. %d", M, MINM, MAXM);
     CTN_REQUIRE(B > 0 && T > 0 && tau >= 0.0, "ctn_mixit_fwd: bad sizes (B = %d, T = %d) or tau < 0", B, T);
     const int nchunk = ctn_sisnr_chunks(T);
-    CTN_REQUIRE((long long)B * nchunk < (1ll << 31) && (long long)T + 4 * NT < (1ll << 31), "ctn_mixit_fwd: B * chunks or T too large");
-    if (workspace == nullptr || workspace_bytes < ctn_mixit_workspace(B, M, T)) {
-        ctn_set_error("ctn_mixit_fwd: workspace too small");
-        return CTN_ERR_WORKSPACE;
-    }
+    if (const int rc = grid_guard("ctn_mixit_fwd", "chunks", B, nchunk, T)) return rc;
+    if (const int rc = workspace_guard("ctn_mixit_fwd", workspace, workspace_bytes, ctn_mixit_workspace(B, M, T))) return rc;
     hipStream_t st = (hipStream_t)stream;
-    const bool vec = (T % 4 == 0) && aligned16(mixtures) && aligned16(estimates);
-    const int chunk = mixit_chunk(T, nchunk);
-    const unsigned grid = (unsigned)(B * nchunk);
-#define CALL(MM) launch_moments<MM>(vec, grid, st, mixtures, estimates, lengths, T, chunk, nchunk, (double*)workspace)
-    MIXIT_DISPATCH(M, CALL)
-#undef CALL
+    dispatch_n<MINM, MAXM>(M, [&](auto m) {
+        launch_moment_sweep<MixitMoments<decltype(m)::value>>(mixtures, estimates, lengths, B, T, nchunk, (double*)workspace, st);
+    });
     CTN_CHECK_LAUNCH("ctn_mixit_fwd/moments");
     hipLaunchKernelGGL(mixit_assign_kernel, dim3(1), dim3(NTA), 0, st, (const double*)workspace, B, M, nchunk, tau, per_utt,
                        assign, snr, loss, coef);
@@ -311,14 +184,15 @@ int ctn_mixit_bwd(const float* mixtures, const float* estimates, const long long
     CTN_REQUIRE(mixtures && estimates && lengths && assign && coef && d_estimates, "ctn_mixit_bwd: null pointer");
     CTN_REQUIRE(M >= MINM && M <= MAXM, "ctn_mixit_bwd: M = %d outside %d .. %d", M, MINM, MAXM);
     CTN_REQUIRE(B > 0 && T > 0, "ctn_mixit_bwd: bad sizes (B = %d, T = %d)", B, T);
-    const int ntile = ctn_cdiv(ctn_cdiv(T, 4), NT);
-    CTN_REQUIRE((long long)B * ntile < (1ll << 31) && (long long)T + 4 * NT < (1ll << 31), "ctn_mixit_bwd: B * tiles or T too large");
-    const bool vec = (T % 4 == 0) && aligned16(mixtures) && aligned16(estimates) && aligned16(d_estimates);
-    const unsigned grid = (unsigned)(B * ntile);
-    hipStream_t st = (hipStream_t)stream;
-#define CALL(MM) launch_bwd<MM>(vec, grid, st, mixtures, estimates, lengths, assign, coef, g_loss, g_per, B, T, ntile, d_estimates)
-    MIXIT_DISPATCH(M, CALL)
-#undef CALL
+    const int ntile = bwd_tiles(T);
+    if (const int rc = grid_guard("ctn_mixit_bwd", "tiles", B, ntile, T)) return rc;
+    const bool vec = (T % 4 == 0) && ctn_aligned16(mixtures) && ctn_aligned16(estimates) && ctn_aligned16(d_estimates);
+    dispatch_n<MINM, MAXM>(M, [&](auto m) {
+        constexpr int MM = decltype(m)::value;
+        auto kernel = vec ? &mixit_bwd_kernel<MM, true> : &mixit_bwd_kernel<MM, false>;
+        hipLaunchKernelGGL(kernel, dim3((unsigned)(B * ntile)), dim3(NT), 0, (hipStream_t)stream, mixtures, estimates, lengths, assign,
+                           coef, g_loss, g_per, B, T, ntile, d_estimates);
+    });
     CTN_CHECK_LAUNCH("ctn_mixit_bwd");
     return CTN_OK;
 }

@@ -161,8 +161,6 @@ __global__ __launch_bounds__(NT) void clip_adam_l2_kernel(float* __restrict__ p,
         }
 }
 
-inline bool aligned16(const void* ptr) { return (reinterpret_cast<uintptr_t>(ptr) & 15) == 0; }
-
 // sumsq partials of the clip, shared by the SGD and Adam+L2 entry points; -> number of partials
 inline int launch_sumsq(const float* grads, long long n, double* workspace, hipStream_t st) {
     long long nb = ctn_cdivll(n / 4 + 1, NT);
@@ -212,7 +210,7 @@ int ctn_clip_sgd_step(float* params, const float* grads, float* momentum_buf, lo
     CTN_REQUIRE(params && grads && workspace, "ctn_clip_sgd_step: null pointer");
     CTN_REQUIRE(momentum == 0.f || momentum_buf, "ctn_clip_sgd_step: null pointer (momentum_buf with momentum != 0)");
     CTN_REQUIRE(n > 0, "ctn_clip_sgd_step: bad sizes");
-    CTN_REQUIRE(aligned16(grads) && aligned16(params) && (momentum == 0.f || aligned16(momentum_buf)),
+    CTN_REQUIRE(ctn_aligned16(grads) && ctn_aligned16(params) && (momentum == 0.f || ctn_aligned16(momentum_buf)),
                 "ctn_clip_sgd_step: grads, params and momentum_buf must be 16-byte aligned");
     CTN_REQUIRE(!nesterov || (momentum > 0.f && dampening == 0.f),
                 "ctn_clip_sgd_step: nesterov momentum requires a momentum and zero dampening");
@@ -239,7 +237,7 @@ int ctn_clip_adam_l2_step(float* params, const float* grads, float* exp_avg, flo
                           float weight_decay, float* total_norm_out, double* workspace, void* stream) {
     CTN_REQUIRE(params && grads && exp_avg && exp_avg_sq && workspace, "ctn_clip_adam_l2_step: null pointer");
     CTN_REQUIRE(n > 0 && step >= 1, "ctn_clip_adam_l2_step: bad sizes");
-    CTN_REQUIRE(aligned16(grads) && aligned16(params) && aligned16(exp_avg) && aligned16(exp_avg_sq),
+    CTN_REQUIRE(ctn_aligned16(grads) && ctn_aligned16(params) && ctn_aligned16(exp_avg) && ctn_aligned16(exp_avg_sq),
                 "ctn_clip_adam_l2_step: grads, params, exp_avg and exp_avg_sq must be 16-byte aligned");
     hipStream_t st = (hipStream_t)stream;
     const int nb = launch_sumsq(grads, n, workspace, st);

@@ -561,8 +561,6 @@ __global__ __launch_bounds__(256) void stream_reset_slots_kernel(ResetArgs a) {
     }
 }
 
-bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
 }  // namespace
 
 // =====================================================================================================================
@@ -587,7 +585,7 @@ size_t ctn_stream_pack_gemm_bytes(int R, int Cn) {
 int ctn_stream_pack_gemm(const float* W, int R, int Cn, void* packed, void* stream) {
     CTN_REQUIRE(W && packed, "ctn_stream_pack_gemm: null pointer");
     CTN_REQUIRE(R > 0 && Cn > 0, "ctn_stream_pack_gemm: bad sizes");
-    CTN_REQUIRE(aligned16(packed), "ctn_stream_pack_gemm: packed must be 16-byte aligned");
+    CTN_REQUIRE(ctn_aligned16(packed), "ctn_stream_pack_gemm: packed must be 16-byte aligned");
     const long long n = (long long)c16(R) * c16(Cn) * 256;
     hipLaunchKernelGGL(stream_pack_kernel, dim3((unsigned)ctn_cdivll(n, 256)), dim3(256), 0, (hipStream_t)stream, W, (float*)packed, R, Cn);
     CTN_CHECK_LAUNCH("ctn_stream_pack_gemm");
@@ -603,7 +601,7 @@ int ctn_stream_pack(const void* const* params, int nblocks, int B, int H, int P,
     CTN_REQUIRE(params && packed, "ctn_stream_pack: null pointer");
     CTN_REQUIRE(nblocks > 0 && B > 0 && H > 0 && B % 16 == 0 && H % 16 == 0, "ctn_stream_pack: B and H must be positive multiples of 16");
     CTN_REQUIRE(P >= 1 && P <= ST_MAXP, "ctn_stream_pack: kernel size must be 1..%d", ST_MAXP);
-    CTN_REQUIRE(aligned16(packed), "ctn_stream_pack: packed must be 16-byte aligned");
+    CTN_REQUIRE(ctn_aligned16(packed), "ctn_stream_pack: packed must be 16-byte aligned");
     for (int i = 0; i < nblocks * 9; ++i) CTN_REQUIRE(params[i], "ctn_stream_pack: block %d parameter %d is null", i / 9, i % 9);
     const size_t bf = block_floats(B, H, P);
     for (int i = 0; i < nblocks; ++i) {
@@ -699,7 +697,7 @@ int ctn_stream_tcn_cln(const void* packed, const int* dilation, int nblocks, flo
     CTN_REQUIRE(P >= 1 && P <= ST_MAXP, "ctn_stream_tcn_cln: kernel size must be 1..%d (got %d)", ST_MAXP, P);
     CTN_REQUIRE(max_frames >= 1 && max_frames <= (1 << 20), "ctn_stream_tcn_cln: bad max_frames");
     CTN_REQUIRE(frames >= 1 && frames <= max_frames, "ctn_stream_tcn_cln: frames must be 1..max_frames (got %d, max_frames %d)", frames, max_frames);
-    CTN_REQUIRE(aligned16(packed) && aligned16(state), "ctn_stream_tcn_cln: packed and state must be 16-byte aligned");
+    CTN_REQUIRE(ctn_aligned16(packed) && ctn_aligned16(state), "ctn_stream_tcn_cln: packed and state must be 16-byte aligned");
     for (int j = 0; j < nblocks; ++j)
         CTN_REQUIRE(dilation[j] >= 1 && dilation[j] <= (1 << 20), "ctn_stream_tcn_cln: bad dilation %d of block %d", dilation[j], j);
     const size_t lds = ((size_t)(B + H) * ST_TC + ST_GRP * ST_TC) * sizeof(float);
@@ -716,7 +714,7 @@ int ctn_stream_front(const float* x, int xld, const void* Up, const float* g0, c
     CTN_REQUIRE(N > 0 && B > 0 && N % 16 == 0 && B % 16 == 0, "ctn_stream_front: N and B must be positive multiples of 16 (got %d, %d)", N, B);
     CTN_REQUIRE(L >= 4 && L % 4 == 0, "ctn_stream_front: L must be a multiple of 4 (got %d)", L);
     CTN_REQUIRE((long long)xld >= (long long)(frames + 1) * (L / 2), "ctn_stream_front: sample buffer row shorter than frames + 1 hops");
-    CTN_REQUIRE(aligned16(Up) && aligned16(Wbp), "ctn_stream_front: packed weights must be 16-byte aligned");
+    CTN_REQUIRE(ctn_aligned16(Up) && ctn_aligned16(Wbp), "ctn_stream_front: packed weights must be 16-byte aligned");
     const size_t lds = ((size_t)(c16(L) * 16 + N + B) * ST_TC + ST_GRP * ST_TC) * sizeof(float);
     CTN_REQUIRE(lds <= ST_MAX_LDS, "ctn_stream_front: N + B = %d needs %zu bytes of LDS per tile (limit %zu)", N + B, lds, ST_MAX_LDS);
     FrontArgs a;
@@ -736,7 +734,7 @@ int ctn_stream_back(const float* y, const float* w, const void* Wmp, const void*
     CTN_REQUIRE(softmax == 0 || softmax == 1, "ctn_stream_back: mask must be 0 (relu) or 1 (softmax)");
     CTN_REQUIRE(C <= ST_MAXC, "ctn_stream_back: at most %d speakers", ST_MAXC);
     CTN_REQUIRE((long long)xld >= (long long)(frames + 1) * (L / 2), "ctn_stream_back: sample buffer row shorter than frames + 1 hops");
-    CTN_REQUIRE(aligned16(Wmp) && aligned16(Vp), "ctn_stream_back: packed weights must be 16-byte aligned");
+    CTN_REQUIRE(ctn_aligned16(Wmp) && ctn_aligned16(Vp), "ctn_stream_back: packed weights must be 16-byte aligned");
     const size_t lds = ((size_t)B + (size_t)C * N + (size_t)C * c16(L) * 16) * ST_TC * sizeof(float);
     CTN_REQUIRE(lds <= ST_MAX_LDS, "ctn_stream_back: B + C*N = %d needs %zu bytes of LDS per tile (limit %zu)", B + C * N, lds, ST_MAX_LDS);
     BackArgs a;
@@ -785,7 +783,7 @@ int ctn_stream_front_ragged(const float* x, int xld, const void* Up, const float
     CTN_REQUIRE(N > 0 && B > 0 && N % 16 == 0 && B % 16 == 0, "ctn_stream_front_ragged: N and B must be positive multiples of 16 (got %d, %d)", N, B);
     CTN_REQUIRE(L >= 4 && L % 4 == 0, "ctn_stream_front_ragged: L must be a multiple of 4 (got %d)", L);
     CTN_REQUIRE((long long)xld >= (long long)(frames + 1) * (L / 2), "ctn_stream_front_ragged: sample buffer row shorter than frames + 1 hops");
-    CTN_REQUIRE(aligned16(Up) && aligned16(Wbp), "ctn_stream_front_ragged: packed weights must be 16-byte aligned");
+    CTN_REQUIRE(ctn_aligned16(Up) && ctn_aligned16(Wbp), "ctn_stream_front_ragged: packed weights must be 16-byte aligned");
     const size_t lds = ((size_t)(c16(L) * 16 + N + B) * ST_TC + ST_GRP * ST_TC) * sizeof(float);
     CTN_REQUIRE(lds <= ST_MAX_LDS, "ctn_stream_front_ragged: N + B = %d needs %zu bytes of LDS per tile (limit %zu)", N + B, lds, ST_MAX_LDS);
     FrontArgs a;
@@ -806,7 +804,7 @@ int ctn_stream_tcn_cln_ragged(const void* packed, const int* dilation, int nbloc
     CTN_REQUIRE(P >= 1 && P <= ST_MAXP, "ctn_stream_tcn_cln_ragged: kernel size must be 1..%d (got %d)", ST_MAXP, P);
     CTN_REQUIRE(max_frames >= 1 && max_frames <= (1 << 20), "ctn_stream_tcn_cln_ragged: bad max_frames");
     CTN_REQUIRE(frames >= 1 && frames <= max_frames, "ctn_stream_tcn_cln_ragged: frames must be 1..max_frames (got %d, max_frames %d)", frames, max_frames);
-    CTN_REQUIRE(aligned16(packed) && aligned16(state), "ctn_stream_tcn_cln_ragged: packed and state must be 16-byte aligned");
+    CTN_REQUIRE(ctn_aligned16(packed) && ctn_aligned16(state), "ctn_stream_tcn_cln_ragged: packed and state must be 16-byte aligned");
     for (int j = 0; j < nblocks; ++j)
         CTN_REQUIRE(dilation[j] >= 1 && dilation[j] <= (1 << 20), "ctn_stream_tcn_cln_ragged: bad dilation %d of block %d", dilation[j], j);
     const size_t lds = ((size_t)(B + H) * ST_TC + ST_GRP * ST_TC) * sizeof(float);
@@ -826,7 +824,7 @@ int ctn_stream_back_ragged(const float* y, const float* w, const void* Wmp, cons
     CTN_REQUIRE(softmax == 0 || softmax == 1, "ctn_stream_back_ragged: mask must be 0 (relu) or 1 (softmax)");
     CTN_REQUIRE(C <= ST_MAXC, "ctn_stream_back_ragged: at most %d speakers", ST_MAXC);
     CTN_REQUIRE((long long)xld >= (long long)(frames + 1) * (L / 2), "ctn_stream_back_ragged: sample buffer row shorter than frames + 1 hops");
-    CTN_REQUIRE(aligned16(Wmp) && aligned16(Vp), "ctn_stream_back_ragged: packed weights must be 16-byte aligned");
+    CTN_REQUIRE(ctn_aligned16(Wmp) && ctn_aligned16(Vp), "ctn_stream_back_ragged: packed weights must be 16-byte aligned");
     const size_t lds = ((size_t)B + (size_t)C * N + (size_t)C * c16(L) * 16) * ST_TC * sizeof(float);
     CTN_REQUIRE(lds <= ST_MAX_LDS, "ctn_stream_back_ragged: B + C*N = %d needs %zu bytes of LDS per tile (limit %zu)", B + C * N, lds, ST_MAX_LDS);
     BackArgs a;
@@ -848,7 +846,7 @@ int ctn_stream_reset_slots(void* state, float* x, int xld, float* ola_tail, void
     CTN_REQUIRE(P >= 1 && P <= ST_MAXP, "ctn_stream_reset_slots: kernel size must be 1..%d (got %d)", ST_MAXP, P);
     CTN_REQUIRE(max_frames >= 1 && max_frames <= (1 << 20), "ctn_stream_reset_slots: bad max_frames");
     CTN_REQUIRE(L >= 4 && L % 4 == 0 && xld >= L / 2, "ctn_stream_reset_slots: L must be a multiple of 4 and xld at least one hop");
-    CTN_REQUIRE(aligned16(state), "ctn_stream_reset_slots: state must be 16-byte aligned");
+    CTN_REQUIRE(ctn_aligned16(state), "ctn_stream_reset_slots: state must be 16-byte aligned");
     for (int j = 0; j < nblocks; ++j)
         CTN_REQUIRE(dilation[j] >= 1 && dilation[j] <= (1 << 20), "ctn_stream_reset_slots: bad dilation %d of block %d", dilation[j], j);
     for (int i = 0; i < nslots; ++i)

@@ -1289,8 +1289,6 @@ __global__ __launch_bounds__(NT) void dw_bwd_taps_kernel(const float* __restrict
     dD[(size_t)h * P + j] = s;
 }
 
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 }  // namespace
 
 extern "C" int ctn_absmax_rows(const float* x, int M, long long n, unsigned* amax, void* stream);      // ctn_gemm.hip
@@ -1306,7 +1304,7 @@ int ctn_dw_fwd(const float* Y, float* Z, const float* D, int M, int H, int K, in
     CTN_REQUIRE(!amax_out || epi_part, "ctn_dw_fwd: amax_out comes with the statistics epilogue");
     CTN_REQUIRE(M > 0 && H > 0 && K > 0 && Kp >= K && Kp % 4 == 0, "ctn_dw_fwd: bad sizes");
     CTN_REQUIRE(P >= 1 && P <= MAXP && dilation >= 1, "ctn_dw_fwd: kernel size %d unsupported (max %d)", P, MAXP);
-    CTN_REQUIRE(aligned16(Y) && aligned16(Z), "ctn_dw_fwd: pointers must be 16-byte aligned");
+    CTN_REQUIRE(ctn_aligned16(Y) && ctn_aligned16(Z), "ctn_dw_fwd: pointers must be 16-byte aligned");
     const int halo = (P - 1) * dilation;
     CTN_REQUIRE(causal || halo % 2 == 0, "ctn_dw_fwd: non-causal 'same' padding needs (P-1)*dilation even");
     const bool small = halo <= 192;
@@ -1330,7 +1328,7 @@ int ctn_dw_fwd_cln(const float* Y, float* Z, const float* D, int M, int H, int K
     CTN_REQUIRE(Y && Z && D && mean && rstd && gamma && beta && alpha, "ctn_dw_fwd_cln: null pointer");
     CTN_REQUIRE(M > 0 && H > 0 && K > 0 && Kp >= K && Kp % 4 == 0, "ctn_dw_fwd_cln: bad sizes");
     CTN_REQUIRE(P >= 1 && P <= MAXP && dilation >= 1, "ctn_dw_fwd_cln: kernel size %d unsupported (max %d)", P, MAXP);
-    CTN_REQUIRE(aligned16(Y) && aligned16(Z) && aligned16(mean) && aligned16(rstd), "ctn_dw_fwd_cln: pointers must be 16-byte aligned");
+    CTN_REQUIRE(ctn_aligned16(Y) && ctn_aligned16(Z) && ctn_aligned16(mean) && ctn_aligned16(rstd), "ctn_dw_fwd_cln: pointers must be 16-byte aligned");
     const int halo = (P - 1) * dilation;
     CTN_REQUIRE(causal || halo % 2 == 0, "ctn_dw_fwd_cln: non-causal 'same' padding needs (P-1)*dilation even");
     const bool small = halo <= 192;
@@ -1388,7 +1386,7 @@ int ctn_dw_bwd(const float* dN2, const float* Dz, const float* Y1, float* dN1, c
     CTN_REQUIRE(dN2 && Y1 && dN1 && D && pc, "ctn_dw_bwd: null pointer");
     CTN_REQUIRE(M > 0 && H > 0 && K > 0 && Kp >= K && Kp % 4 == 0, "ctn_dw_bwd: bad sizes");
     CTN_REQUIRE(P >= 1 && P <= MAXP && dilation >= 1, "ctn_dw_bwd: kernel size %d unsupported (max %d)", P, MAXP);
-    CTN_REQUIRE(aligned16(dN2) && aligned16(Y1) && aligned16(dN1) && (!fused || aligned16(Dz)), "ctn_dw_bwd: alignment");
+    CTN_REQUIRE(ctn_aligned16(dN2) && ctn_aligned16(Y1) && ctn_aligned16(dN1) && (!fused || ctn_aligned16(Dz)), "ctn_dw_bwd: alignment");
     const int halo = (P - 1) * dilation;
     CTN_REQUIRE(causal || halo % 2 == 0, "ctn_dw_bwd: non-causal 'same' padding needs (P-1)*dilation even");
     // patch size by halo: the dilation-128 blocks of the paper stack (halo 256) ran at 107 us with the 1792-float patches
@@ -1402,8 +1400,8 @@ int ctn_dw_bwd(const float* dN2, const float* Dz, const float* Y1, float* dN1, c
                     "ctn_dw_bwd: fused mode needs every norm argument");
     const bool xcln = fused == 2 && g1 != nullptr;        // the cLN form with the first norm's output recomputed from Y1 = h1
     if (fused == 2) {       // (ms2 carries the per-frame constants fc [M][4][Kp]; ms1 / sums2_part the first norm's mean / rstd [M][Kp])
-        CTN_REQUIRE(Dz && g2 && a2 && ms2 && aligned16(ms2), "ctn_dw_bwd_cln: null or unaligned argument");
-        CTN_REQUIRE(!xcln || (b1 && a1 && ms1 && sums2_part && aligned16(ms1) && aligned16(sums2_part)), "ctn_dw_bwd_cln: incomplete first-norm arguments");
+        CTN_REQUIRE(Dz && g2 && a2 && ms2 && ctn_aligned16(ms2), "ctn_dw_bwd_cln: null or unaligned argument");
+        CTN_REQUIRE(!xcln || (b1 && a1 && ms1 && sums2_part && ctn_aligned16(ms1) && ctn_aligned16(sums2_part)), "ctn_dw_bwd_cln: incomplete first-norm arguments");
     }
     DwBwdArgs a{};
     a.dN2 = dN2; a.Dz = Dz; a.Y1 = Y1; a.dN1 = dN1; a.D = D;
@@ -1496,7 +1494,7 @@ int ctn_dw_bwd_cln_finalize(const float* pc, int P, int M, int H, float* dD, flo
 int ctn_cln_bwd_frame(const double* col_part, int nparts, const float* mean, const float* rstd, float* fc, int M, int Ch, int Kp,
                       void* stream) {
     CTN_REQUIRE(col_part && mean && rstd && fc && nparts > 0 && M > 0 && Ch > 0 && Kp > 0, "ctn_cln_bwd_frame: bad arguments");
-    CTN_REQUIRE(aligned16(col_part), "ctn_cln_bwd_frame: col_part must be 16-byte aligned");
+    CTN_REQUIRE(ctn_aligned16(col_part), "ctn_cln_bwd_frame: col_part must be 16-byte aligned");
     hipLaunchKernelGGL(cln_bwd_frame_kernel, dim3((unsigned)ctn_cdivll((long long)M * Kp, NT)), dim3(NT), 0, (hipStream_t)stream,
                        col_part, nparts, mean, rstd, fc, M, Ch, Kp);
     CTN_CHECK_LAUNCH("ctn_cln_bwd_frame");
@@ -1505,7 +1503,7 @@ int ctn_cln_bwd_frame(const double* col_part, int nparts, const float* mean, con
 
 int ctn_cln_stats_frame(const double* col_part, int nparts, float* mean, float* rstd, int M, int Ch, int Kp, void* stream) {
     CTN_REQUIRE(col_part && mean && rstd && nparts > 0 && M > 0 && Ch > 0 && Kp > 0, "ctn_cln_stats_frame: bad arguments");
-    CTN_REQUIRE(aligned16(col_part), "ctn_cln_stats_frame: col_part must be 16-byte aligned");
+    CTN_REQUIRE(ctn_aligned16(col_part), "ctn_cln_stats_frame: col_part must be 16-byte aligned");
     hipLaunchKernelGGL(cln_stats_frame_kernel, dim3((unsigned)ctn_cdivll((long long)M * Kp, NT)), dim3(NT), 0, (hipStream_t)stream,
                        col_part, nparts, mean, rstd, M, Ch, Kp);
     CTN_CHECK_LAUNCH("ctn_cln_stats_frame");
@@ -1524,7 +1522,7 @@ int ctn_gln_prelu_bwd(const float* dN, const float* Y, float* dY, int M, int H, 
                       float* dalpha_part, unsigned* amax_out, void* stream) {
     CTN_REQUIRE(dN && Y && dY && gamma && alpha && ms && sums_part && dalpha_part && nparts > 0, "ctn_gln_prelu_bwd: null pointer");
     CTN_REQUIRE(M > 0 && H > 0 && K > 0 && Kp >= K && Kp % 4 == 0, "ctn_gln_prelu_bwd: bad sizes");
-    CTN_REQUIRE(aligned16(dN) && aligned16(Y) && aligned16(dY), "ctn_gln_prelu_bwd: alignment");
+    CTN_REQUIRE(ctn_aligned16(dN) && ctn_aligned16(Y) && ctn_aligned16(dY), "ctn_gln_prelu_bwd: alignment");
     hipLaunchKernelGGL(gln_prelu_bwd_kernel, dim3((unsigned)(M * ctn_cdiv(H, ROWS))), dim3(NT), 0, (hipStream_t)stream,
                        dN, Y, dY, M, H, K, Kp, gamma, alpha, ms, sums_part, nparts, dalpha_part, amax_out);
     CTN_CHECK_LAUNCH("ctn_gln_prelu_bwd");
@@ -1535,7 +1533,7 @@ int ctn_gln_bwd_sums(const float* dN, const float* Y, int M, int H, int K, int K
                      const float* ms, double* sums_part, float* pc, void* stream) {
     CTN_REQUIRE(dN && Y && gamma && alpha && ms && sums_part && pc, "ctn_gln_bwd_sums: null pointer");
     CTN_REQUIRE(M > 0 && H > 0 && K > 0 && Kp >= K && Kp % 4 == 0, "ctn_gln_bwd_sums: bad sizes");
-    CTN_REQUIRE(aligned16(dN) && aligned16(Y), "ctn_gln_bwd_sums: alignment");
+    CTN_REQUIRE(ctn_aligned16(dN) && ctn_aligned16(Y), "ctn_gln_bwd_sums: alignment");
     hipLaunchKernelGGL(gln_bwd_sums_kernel, dim3((unsigned)(M * ctn_cdiv(H, ROWS))), dim3(NT), 0, (hipStream_t)stream,
                        dN, Y, M, H, K, Kp, gamma, alpha, ms, sums_part, pc);
     CTN_CHECK_LAUNCH("ctn_gln_bwd_sums");
@@ -1567,7 +1565,7 @@ int ctn_gln_fuse(void) {         // (CTN_GLN_FUSE=0|1 at first use; default belo
 int g_ctn_cln_lean = 1;          // ctn_tune("cln_lean", 0 | 1): the specialised backward kernel for the stacks' form
 
 static bool cln_v4_ok(int Ch, int Kp, const void* a, const void* b, const void* c) {
-    return Ch <= 8 * C4_NG && Kp % C4_FR == 0 && aligned16(a) && aligned16(b) && aligned16(c);
+    return Ch <= 8 * C4_NG && Kp % C4_FR == 0 && ctn_aligned16(a) && ctn_aligned16(b) && ctn_aligned16(c);
 }
 
 int ctn_cln_fwd(const float* Y, float* Out, float* mean, float* rstd, int M, int Ch, int K, int Kp,
@@ -1575,7 +1573,7 @@ int ctn_cln_fwd(const float* Y, float* Out, float* mean, float* rstd, int M, int
     CTN_REQUIRE(Y && Out && mean && rstd && gamma && beta, "ctn_cln_fwd: null pointer");
     CTN_REQUIRE(M > 0 && Ch > 0 && K > 0 && Kp >= K, "ctn_cln_fwd: bad sizes");
     hipStream_t st = (hipStream_t)stream;
-    if (cln_v4_ok(Ch, Kp, Y, Out, mean) && aligned16(rstd)) {     // 16-byte accesses along frames (round 2)
+    if (cln_v4_ok(Ch, Kp, Y, Out, mean) && ctn_aligned16(rstd)) {     // 16-byte accesses along frames (round 2)
         const bool small = g_ctn_cln_fr == 16;                     // (Kp % 32 == 0 was checked: 16 divides it)
         const dim3 grid((unsigned)(M * (Kp / (small ? 16 : C4_FR))));
 #define CTN_CLN_FWD4(CPT_) do { if (small) hipLaunchKernelGGL((cln_fwd_v4_kernel<CPT_, 256, 16>), grid, dim3(256), 0, st, Y, Out, mean, rstd, M, Ch, K, Kp, gamma, beta, alpha, amax_out); \
@@ -1615,11 +1613,11 @@ int ctn_cln_bwd(const float* dOut, const float* Y, float* dY, const float* mean,
     CTN_REQUIRE(dOut && Y && dY && mean && rstd && gamma && pc, "ctn_cln_bwd: null pointer");
     CTN_REQUIRE(M > 0 && Ch > 0 && K > 0 && Kp >= K && Kp % 4 == 0, "ctn_cln_bwd: bad sizes");
     CTN_REQUIRE(!alpha || dalpha_part, "ctn_cln_bwd: dalpha_part required with alpha");
-    CTN_REQUIRE(aligned16(dOut) && aligned16(Y) && aligned16(mean) && aligned16(rstd), "ctn_cln_bwd: alignment");
+    CTN_REQUIRE(ctn_aligned16(dOut) && ctn_aligned16(Y) && ctn_aligned16(mean) && ctn_aligned16(rstd), "ctn_cln_bwd: alignment");
     hipStream_t st = (hipStream_t)stream;
     float* const dap = alpha ? dalpha_part : nullptr;
     const int rows = ctn_cln_bwd_blocks(M, Kp);
-    if (cln_v4_ok(Ch, Kp, dOut, Y, dY) && Kp % g_ctn_cln_fr == 0 && (!add || aligned16(add)) && (!relu_ref || aligned16(relu_ref))) {
+    if (cln_v4_ok(Ch, Kp, dOut, Y, dY) && Kp % g_ctn_cln_fr == 0 && (!add || ctn_aligned16(add)) && (!relu_ref || ctn_aligned16(relu_ref))) {
         // one pass: input gradient AND the parameter-gradient partials (dY may alias dOut: each thread reads its elements
         // of dOut before it writes them)
         const dim3 grid((unsigned)rows);

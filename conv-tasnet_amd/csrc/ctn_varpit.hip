@@ -15,17 +15,14 @@
 //   coefficients are emitted.
 // Backward: d_e[b,i,t] = [t < len] * scale_b / C * c_i * (e_i[t] - a_i s_j[t]),  j = perm_idx(i).
 //
-// The time partition and the lane that owns a sample depend on T alone, and the aligned (16 bytes per lane) and the scalar load
-// paths add the same values in the same order, so an utterance's result is bitwise the same in any batch, at any batch index and
-// at any alignment.
-#include "ctn_common.h"
-
-extern "C" int ctn_sisnr_chunks(int T);      // csrc/ctn_loss.hip: the time partition, a function of T alone
+// The sweep, the reductions, the first-minimum rule and the load and store paths are the skeleton of ctn_moment_loss.h, shared
+// with ctn_mixit.hip; it keeps the promise that an utterance's result is bitwise the same in any batch, at any batch index and at
+// any alignment.  This file holds this loss's own algebra: which moments, the pair losses and active flags, the C! enumeration,
+// the coefficients and the backward body.
+#include "ctn_moment_loss.h"
 
 namespace {
 
-constexpr int NT = 256;            // moments and backward kernels
-constexpr int NTA = 1024;          // assignment kernel: 16 waves, one utterance per wave at a time
 constexpr int MINC = 2, MAXC = 6;
 constexpr double EPSD = 1e-8;
 
@@ -36,22 +33,6 @@ __host__ __device__ constexpr int ee_at(int C, int i) { return C * C + C + i; }
 __host__ __device__ constexpr int xx_at(int C) { return C * C + 2 * C; }
 constexpr int nfact(int C) { return C <= 1 ? 1 : C * nfact(C - 1); }
 
-struct Quad { float v[4]; };
-
-// four consecutive samples of one row starting at t (t % 4 == 0); samples at or beyond `len` read as 0 and are not touched
-template <bool VEC>
-__device__ __forceinline__ Quad load4(const float* __restrict__ row, int t, int len) {
-    Quad q;
-    if (VEC && t + 4 <= len) {
-        const float4 f = *reinterpret_cast<const float4*>(row + t);
-        q.v[0] = f.x; q.v[1] = f.y; q.v[2] = f.z; q.v[3] = f.w;
-    } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) q.v[j] = t + j < len ? row[t + j] : 0.f;
-    }
-    return q;
-}
-
 // acc + m * m in two roundings.  Every other product of the sweep is one of two fp32 values and exact in fp64, so a fused and an
 // unfused multiply-add give the same bits there; this one is not, and is kept unfused in both load paths.
 __device__ __forceinline__ double add_square(double acc, double m) {
@@ -60,64 +41,29 @@ __device__ __forceinline__ double add_square(double acc, double m) {
     return acc + p;
 }
 
-// partial[b][chunk][nmom(C)]; chunk % 4 == 0.  Lane tid owns the quads (t0 + 4 tid) + 4 NT k of its chunk, in ascending k.
-template <int C, bool VEC>
-__global__ __launch_bounds__(NT) void varpit_moments_kernel(const float* __restrict__ s, const float* __restrict__ e,
-                                                            const long long* __restrict__ lens, int T, int chunk, int nchunk,
-                                                            double* __restrict__ partial) {
-    constexpr int NV = nmom(C);
-    __shared__ double red[NT / 64][NV];
-    const int b = blockIdx.x / nchunk, ch = blockIdx.x % nchunk;
-    const int tid = threadIdx.x;
-    long long ll = lens[b];
-    if (ll > T) ll = T;
-    if (ll < 0) ll = 0;
-    const int len = (int)ll;
-    const int t0 = ch * chunk, t1 = min(min(t0 + chunk, T), len);
-    const float* __restrict__ sb = s + (size_t)b * C * T;
-    const float* __restrict__ eb = e + (size_t)b * C * T;
-    double acc[NV];
+// the sweep's policy: the rows s [C,T] and e [C,T] of an utterance, sample k of the loaded quads
+template <int C>
+struct VarpitMoments {
+    static constexpr int NREF = C, NEST = C, NV = nmom(C);
+    static __device__ __forceinline__ void accumulate(double (&acc)[NV], const Quad (&sv)[C], const Quad (&ev)[C], int k) {
+        double sd[C];
+        double mix = 0.0;
 #pragma unroll
-    for (int q = 0; q < NV; ++q) acc[q] = 0.0;
-    for (int t = t0 + 4 * tid; t < t1; t += 4 * NT) {
-        Quad sv[C], ev[C];
+        for (int j = 0; j < C; ++j) {
+            sd[j] = (double)sv[j].v[k];
+            mix += sd[j];                                       // the clean mixture: ascending j
+            acc[ss_at(C, j)] += sd[j] * sd[j];
+        }
+        acc[xx_at(C)] = add_square(acc[xx_at(C)], mix);
 #pragma unroll
-        for (int j = 0; j < C; ++j) sv[j] = load4<VEC>(sb + (size_t)j * T, t, len);
+        for (int i = 0; i < C; ++i) {
+            const double ei = (double)ev[i].v[k];
+            acc[ee_at(C, i)] += ei * ei;
 #pragma unroll
-        for (int i = 0; i < C; ++i) ev[i] = load4<VEC>(eb + (size_t)i * T, t, len);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            double sd[C];
-            double mix = 0.0;
-#pragma unroll
-            for (int j = 0; j < C; ++j) {
-                sd[j] = (double)sv[j].v[k];
-                mix += sd[j];                                       // the clean mixture: ascending j
-                acc[ss_at(C, j)] += sd[j] * sd[j];
-            }
-            acc[xx_at(C)] = add_square(acc[xx_at(C)], mix);
-#pragma unroll
-            for (int i = 0; i < C; ++i) {
-                const double ei = (double)ev[i].v[k];
-                acc[ee_at(C, i)] += ei * ei;
-#pragma unroll
-                for (int j = 0; j < C; ++j) acc[es_at(C, i, j)] += ei * sd[j];
-            }
+            for (int j = 0; j < C; ++j) acc[es_at(C, i, j)] += ei * sd[j];
         }
     }
-#pragma unroll
-    for (int q = 0; q < NV; ++q) {
-        const double v = wave_sum(acc[q]);
-        if ((tid & 63) == 0) red[tid >> 6][q] = v;
-    }
-    __syncthreads();
-    if (tid < NV) {
-        double r = red[0][tid];
-#pragma unroll
-        for (int w = 1; w < NT / 64; ++w) r += red[w][tid];
-        partial[((size_t)b * nchunk + ch) * NV + tid] = r;
-    }
-}
+};
 
 // One block of 16 waves; wave w takes utterances w, w + 16, ...  pair [B,C,C], active [B,C], coef [B,C,2].
 __global__ __launch_bounds__(NTA) void varpit_assign_kernel(const double* __restrict__ partial, const int* __restrict__ perms,
@@ -135,13 +81,7 @@ __global__ __launch_bounds__(NTA) void varpit_assign_kernel(const double* __rest
     double local = 0.0;                       // lane 0: sum of this wave's per-utterance losses, ascending b
     for (int b0 = 0; b0 < B; b0 += NW) {      // block-uniform trip count: the barriers below are reached by every wave
         const int b = b0 + w;
-        __syncthreads();                      // mo[w], pl[w], pd[w] may still be read for the previous utterance
-        if (b < B && lane < nv) {
-            double r = 0.0;
-            for (int ch = 0; ch < nchunk; ++ch) r += partial[((size_t)b * nchunk + ch) * nv + lane];
-            mo[w][lane] = r;
-        }
-        __syncthreads();
+        sum_chunks_to_lds(partial, b, B, nv, nchunk, mo[w]);      // its first barrier also guards pl[w], pd[w]
         const double* m = mo[w];
         if (b < B && lane < cc) {
             const int i = lane / C, j = lane % C;
@@ -172,14 +112,7 @@ __global__ __launch_bounds__(NTA) void varpit_assign_kernel(const double* __rest
             const double L = sum / (double)C;
             if (bestp == nperm || L < bestL) { bestL = L; bestp = p; }
         }
-        // first minimum over the wave: smaller L wins, equal L -> smaller p (lanes without a permutation carry p = nperm)
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const double oL = __shfl_xor(bestL, o, 64);
-            const int op = __shfl_xor(bestp, o, 64);
-            const bool take = op < nperm && (bestp == nperm || oL < bestL || (oL == bestL && op < bestp));
-            if (take) { bestL = oL; bestp = op; }
-        }
+        wave_first_min(bestL, bestp, nperm);
         if (lane < C) {
             const int j = min(max(perms[bestp * C + lane], 0), C - 1);
             const bool act = m[ss_at(C, j)] > 0.0;
@@ -194,14 +127,7 @@ __global__ __launch_bounds__(NTA) void varpit_assign_kernel(const double* __rest
             local += bestL;
         }
     }
-    if (lane == 0) wsum[w] = local;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double tot = wsum[0];
-#pragma unroll
-        for (int k = 1; k < NW; ++k) tot += wsum[k];
-        loss[0] = (float)(tot / (double)B);
-    }
+    mean_over_waves(local, wsum, B, loss);
 }
 
 // Each lane takes four consecutive samples of one utterance: reads the C estimate rows and the paired active reference rows,
@@ -216,17 +142,11 @@ __global__ __launch_bounds__(NT) void varpit_bwd_kernel(const float* __restrict_
     const int b = blockIdx.x / ntile, tile = blockIdx.x % ntile;
     const int t = (tile * NT + threadIdx.x) * 4;
     if (t >= T) return;
-    long long ll = lens[b];
-    if (ll > T) ll = T;
-    if (ll < 0) ll = 0;
-    const int len = (int)ll;
+    const int len = clamped_len(lens, b, T);
     long long p = idx[b];
     if (p < 0) p = 0;
     if (p >= nfact(C)) p = nfact(C) - 1;
-    float scale = 0.f;
-    if (g_loss != nullptr) scale = g_loss[0] / (float)B;
-    if (g_per != nullptr) scale += g_per[b];
-    scale = scale / (float)C;
+    const float scale = upstream_scale(g_loss, g_per, b, B) / (float)C;
     const float* __restrict__ sb = s + (size_t)b * C * T;
     const float* __restrict__ eb = e + (size_t)b * C * T;
     float* __restrict__ db = de + (size_t)b * C * T;
@@ -248,50 +168,9 @@ __global__ __launch_bounds__(NT) void varpit_bwd_kernel(const float* __restrict_
                 o[k] = t + k < len ? wi * r : 0.f;
             }
         }
-        float* __restrict__ dst = db + (size_t)i * T + t;
-        if (VEC) {                              // T % 4 == 0: the whole quad is inside the row
-            *reinterpret_cast<float4*>(dst) = make_float4(o[0], o[1], o[2], o[3]);
-        } else {
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-                if (t + k < T) dst[k] = o[k];
-        }
+        store4<VEC>(db + (size_t)i * T + t, o, t, T);
     }
 }
-
-inline bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
-
-inline int varpit_chunk(int T, int nchunk) { return ctn_cdiv(ctn_cdiv(T, nchunk), 4) * 4; }
-
-template <int C>
-void launch_moments(bool vec, unsigned grid, hipStream_t st, const float* s, const float* e, const long long* lens, int T,
-                    int chunk, int nchunk, double* partial) {
-    if (vec)
-        hipLaunchKernelGGL((varpit_moments_kernel<C, true>), dim3(grid), dim3(NT), 0, st, s, e, lens, T, chunk, nchunk, partial);
-    else
-        hipLaunchKernelGGL((varpit_moments_kernel<C, false>), dim3(grid), dim3(NT), 0, st, s, e, lens, T, chunk, nchunk, partial);
-}
-
-template <int C>
-void launch_bwd(bool vec, unsigned grid, hipStream_t st, const float* s, const float* e, const long long* lens, const int* perms,
-                const long long* idx, const float* coef, const float* g_loss, const float* g_per, int B, int T, int ntile,
-                float* de) {
-    if (vec)
-        hipLaunchKernelGGL((varpit_bwd_kernel<C, true>), dim3(grid), dim3(NT), 0, st, s, e, lens, perms, idx, coef, g_loss, g_per,
-                           B, T, ntile, de);
-    else
-        hipLaunchKernelGGL((varpit_bwd_kernel<C, false>), dim3(grid), dim3(NT), 0, st, s, e, lens, perms, idx, coef, g_loss, g_per,
-                           B, T, ntile, de);
-}
-
-#define VARPIT_DISPATCH(C, CALL)                \
-    switch (C) {                                \
-        case 2: CALL(2); break;                 \
-        case 3: CALL(3); break;                 \
-        case 4: CALL(4); break;                 \
-        case 5: CALL(5); break;                 \
-        default: CALL(6); break;                \
-    }
 
 inline int host_fact(int C) { int f = 1; for (int k = 2; k <= C; ++k) f *= k; return f; }
 
@@ -314,18 +193,12 @@ int ctn_varpit_fwd(const float* sources, const float* estimates, const long long
     CTN_REQUIRE(nperm == host_fact(C), "ctn_varpit_fwd: nperm = %d, C! = %d permutations are needed", nperm, host_fact(C));
     CTN_REQUIRE(B > 0 && T > 0 && tau >= 0.0 && tau0 >= 0.0, "ctn_varpit_fwd: bad sizes (B = %d, T = %d) or a threshold < 0", B, T);
     const int nchunk = ctn_sisnr_chunks(T);
-    CTN_REQUIRE((long long)B * nchunk < (1ll << 31) && (long long)T + 4 * NT < (1ll << 31), "ctn_varpit_fwd: B * chunks or T too large");
-    if (workspace == nullptr || workspace_bytes < ctn_varpit_workspace(B, C, T)) {
-        ctn_set_error("ctn_varpit_fwd: workspace too small");
-        return CTN_ERR_WORKSPACE;
-    }
+    if (const int rc = grid_guard("ctn_varpit_fwd", "chunks", B, nchunk, T)) return rc;
+    if (const int rc = workspace_guard("ctn_varpit_fwd", workspace, workspace_bytes, ctn_varpit_workspace(B, C, T))) return rc;
     hipStream_t st = (hipStream_t)stream;
-    const bool vec = (T % 4 == 0) && aligned16(sources) && aligned16(estimates);
-    const int chunk = varpit_chunk(T, nchunk);
-    const unsigned grid = (unsigned)(B * nchunk);
-#define CALL(CC) launch_moments<CC>(vec, grid, st, sources, estimates, lengths, T, chunk, nchunk, (double*)workspace)
-    VARPIT_DISPATCH(C, CALL)
-#undef CALL
+    dispatch_n<MINC, MAXC>(C, [&](auto c) {
+        launch_moment_sweep<VarpitMoments<decltype(c)::value>>(sources, estimates, lengths, B, T, nchunk, (double*)workspace, st);
+    });
     CTN_CHECK_LAUNCH("ctn_varpit_fwd/moments");
     hipLaunchKernelGGL(varpit_assign_kernel, dim3(1), dim3(NTA), 0, st, (const double*)workspace, perms, nperm, B, C, nchunk, tau,
                        tau0, per_utt, perm_idx, pair, active, loss, coef);
@@ -339,14 +212,15 @@ int ctn_varpit_bwd(const float* sources, const float* estimates, const long long
     CTN_REQUIRE(sources && estimates && lengths && perms && perm_idx && coef && d_estimates, "ctn_varpit_bwd: null pointer");
     CTN_REQUIRE(C >= MINC && C <= MAXC, "ctn_varpit_bwd: C = %d outside %d .. %d", C, MINC, MAXC);
     CTN_REQUIRE(B > 0 && T > 0, "ctn_varpit_bwd: bad sizes (B = %d, T = %d)", B, T);
-    const int ntile = ctn_cdiv(ctn_cdiv(T, 4), NT);
-    CTN_REQUIRE((long long)B * ntile < (1ll << 31) && (long long)T + 4 * NT < (1ll << 31), "ctn_varpit_bwd: B * tiles or T too large");
-    const bool vec = (T % 4 == 0) && aligned16(sources) && aligned16(estimates) && aligned16(d_estimates);
-    const unsigned grid = (unsigned)(B * ntile);
-    hipStream_t st = (hipStream_t)stream;
-#define CALL(CC) launch_bwd<CC>(vec, grid, st, sources, estimates, lengths, perms, perm_idx, coef, g_loss, g_per, B, T, ntile, d_estimates)
-    VARPIT_DISPATCH(C, CALL)
-#undef CALL
+    const int ntile = bwd_tiles(T);
+    if (const int rc = grid_guard("ctn_varpit_bwd", "tiles", B, ntile, T)) return rc;
+    const bool vec = (T % 4 == 0) && ctn_aligned16(sources) && ctn_aligned16(estimates) && ctn_aligned16(d_estimates);
+    dispatch_n<MINC, MAXC>(C, [&](auto c) {
+        constexpr int CC = decltype(c)::value;
+        auto kernel = vec ? &varpit_bwd_kernel<CC, true> : &varpit_bwd_kernel<CC, false>;
+        hipLaunchKernelGGL(kernel, dim3((unsigned)(B * ntile)), dim3(NT), 0, (hipStream_t)stream, sources, estimates, lengths, perms,
+                           perm_idx, coef, g_loss, g_per, B, T, ntile, d_estimates);
+    });
     CTN_CHECK_LAUNCH("ctn_varpit_bwd");
     return CTN_OK;
 }

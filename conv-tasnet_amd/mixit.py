@@ -37,13 +37,8 @@ class MixIt(torch.autograd.Function):
             raise ValueError("MixIT over %d .. %d outputs, got %d" % (MIN_OUTPUTS, MAX_OUTPUTS, M))
         if Bn < 1 or T < 1:
             raise ValueError("empty batch or zero-length signals")
-        if not (estimates.is_contiguous() and estimates.dtype == F32):
-            raise ops.CtnError("estimate_source must be a contiguous fp32 tensor")
+        mixtures, lengths = ops._loss_inputs(mixtures, estimates, lengths)
         dev = estimates.device
-        mixtures = ops._c(mixtures.to(device=dev, dtype=F32))
-        lengths = ops._c(lengths.to(device=dev, dtype=torch.int64))
-        if lengths.shape != (Bn,):
-            raise ValueError("lengths must be [B]")
         loss = torch.empty((), dtype=F32, device=dev)
         per_utt = torch.empty((Bn,), dtype=F32, device=dev)
         snr = torch.empty((Bn, 2), dtype=F32, device=dev)
@@ -51,8 +46,6 @@ class MixIt(torch.autograd.Function):
         coef = torch.empty((Bn, 2), dtype=F32, device=dev)
         nbytes = lib.ctn_mixit_workspace(Bn, M, T)
         ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
-        ops._chk(mixtures, estimates)
-        ops._chk_aux(lengths)
         lib.call("ctn_mixit_fwd", ops._p(mixtures), ops._p(estimates), ops._p(lengths), Bn, M, T, float(tau), ops._p(per_utt),
                  ops._p(assign), ops._p(snr), ops._p(loss), ops._p(coef), ops._p(ws), nbytes, ops._stream())
         ctx.mark_non_differentiable(snr, assign)
@@ -65,9 +58,7 @@ class MixIt(torch.autograd.Function):
         mixtures, estimates, lengths, assign, coef = ctx.saved_tensors
         Bn, M, T = estimates.shape
         d_est = torch.empty_like(estimates)
-        g_loss = None if g_loss is None else ops._c(g_loss.to(F32))
-        g_per = None if g_per is None else ops._c(g_per.to(F32))
-        ops._chk(g_loss, g_per)
+        g_loss, g_per = ops._upstream(g_loss, g_per)
         lib.call("ctn_mixit_bwd", ops._p(mixtures), ops._p(estimates), ops._p(lengths), ops._p(assign), ops._p(coef),
                  ops._p(g_loss), ops._p(g_per), Bn, M, T, ops._p(d_est), ops._stream())
         return None, d_est, None, None

@@ -1231,6 +1231,28 @@ def _perms(C, device):
     return _perm_cache[key]
 
 
+def _loss_inputs(refs, estimates, lengths):
+    """What the moment-form losses (mixit.py, varpit.py) take: `estimates` [B, ., T] as it is, contiguous fp32, and the references
+    and lengths [B] moved to its device as contiguous fp32 / int64 -> (refs, lengths), checked for the C ABI."""
+    if not (estimates.is_contiguous() and estimates.dtype == F32):
+        raise CtnError("estimate_source must be a contiguous fp32 tensor")
+    refs = _c(refs.to(device=estimates.device, dtype=F32))
+    lengths = _c(lengths.to(device=estimates.device, dtype=torch.int64))
+    if lengths.shape != (estimates.size(0),):
+        raise ValueError("lengths must be [B]")
+    _chk(refs, estimates)
+    _chk_aux(lengths)
+    return refs, lengths
+
+
+def _upstream(g_loss, g_per):
+    """The upstream gradients of (loss, per_utt), either of which autograd may leave None, as the backward entry points take them."""
+    g_loss = None if g_loss is None else _c(g_loss.to(F32))
+    g_per = None if g_per is None else _c(g_per.to(F32))
+    _chk(g_loss, g_per)
+    return g_loss, g_per
+
+
 class SiSnrPit(torch.autograd.Function):
     """(source, estimate, lengths) -> (loss[], max_snr[B,1], estimate masked in place, best perm index [B])."""
 

@@ -33,15 +33,8 @@ class VarPit(torch.autograd.Function):
             raise ValueError("PIT with inactive sources over %d .. %d outputs, got %d" % (MIN_SOURCES, MAX_SOURCES, C))
         if Bn < 1 or T < 1:
             raise ValueError("empty batch or zero-length signals")
-        if not (estimates.is_contiguous() and estimates.dtype == F32):
-            raise ops.CtnError("estimate_source must be a contiguous fp32 tensor")
+        sources, lengths = ops._loss_inputs(sources, estimates, lengths)
         dev = estimates.device
-        sources = ops._c(sources.to(device=dev, dtype=F32))
-        lengths = ops._c(lengths.to(device=dev, dtype=torch.int64))
-        if lengths.shape != (Bn,):
-            raise ValueError("lengths must be [B]")
-        ops._chk(sources, estimates)
-        ops._chk_aux(lengths)
         perms = ops._perms(C, dev)[0]
         loss = torch.empty((), dtype=F32, device=dev)
         per_utt = torch.empty((Bn,), dtype=F32, device=dev)
@@ -64,9 +57,7 @@ class VarPit(torch.autograd.Function):
         sources, estimates, lengths, perms, perm_idx, coef = ctx.saved_tensors
         Bn, C, T = estimates.shape
         d_est = torch.empty_like(estimates)
-        g_loss = None if g_loss is None else ops._c(g_loss.to(F32))
-        g_per = None if g_per is None else ops._c(g_per.to(F32))
-        ops._chk(g_loss, g_per)
+        g_loss, g_per = ops._upstream(g_loss, g_per)
         lib.call("ctn_varpit_bwd", ops._p(sources), ops._p(estimates), ops._p(lengths), ops._p(perms), ops._p(perm_idx), ops._p(coef),
                  ops._p(g_loss), ops._p(g_per), Bn, C, T, ops._p(d_est), ops._stream())
         return None, d_est, None, None, None
