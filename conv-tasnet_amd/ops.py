@@ -15,6 +15,7 @@ autograd node:
   Backend  : mask 1x1 -> relu|softmax -> mask*w -> basis -> OLA   (src/conv_tasnet.py:191,206-215,131-146)
   SiSnrPit : PIT SI-SNR loss                                      (src/pit_criterion.py:12-77)
 """
+import collections
 import ctypes
 import itertools
 import os
@@ -127,14 +128,25 @@ def _emit(grad, sink):
 # ---------------------------------------------------------------------------------------
 # thin typed wrappers (one per entry point actually used below)
 # ---------------------------------------------------------------------------------------
+def _pro(pro):
+    """A forward prologue pro = (part[M,np,2] f64, gamma, beta, alpha) | None as the C calls take it: (part, np, gamma, beta, alpha)."""
+    return (None, 0, None, None, None) if pro is None else (pro[0], pro[0].shape[1], pro[1], pro[2], pro[3])
+
+
+def _out_epi(X, R, epi_alpha, parts=None):
+    """Out [M,R,Kp] of a forward kernel over X [M,.,Kp] and, with an epilogue PReLU, its statistics partials [M,parts,2] f64."""
+    M, _, Kp = X.shape
+    out = torch.empty((M, R, Kp), dtype=F32, device=X.device)
+    if epi_alpha is None:
+        return out, None
+    return out, torch.empty((M, parts or lib.ctn_pw_stats_parts(M, R, Kp), 2), dtype=F64, device=X.device)
+
+
 def pw_gemm(W, X, R, Cn, K, trans_w=False, pro=None, residual=None, epi_alpha=None, relu_out=False, ms_out=None):
     """Out[M,R,Kp] = op(W) . f(X).  pro = (part[M,np,2] f64, gamma, beta, alpha).  Returns (Out, epi_part|None)."""
     M, _, Kp = X.shape
-    out = torch.empty((M, R, Kp), dtype=F32, device=X.device)
-    epi_part = None
-    if epi_alpha is not None:
-        epi_part = torch.empty((M, lib.ctn_pw_stats_parts(M, R, Kp), 2), dtype=F64, device=X.device)
-    pp, npart, pg, pb, pa = (None, 0, None, None, None) if pro is None else (pro[0], pro[0].shape[1], pro[1], pro[2], pro[3])
+    out, epi_part = _out_epi(X, R, epi_alpha)
+    pp, npart, pg, pb, pa = _pro(pro)
     _chk(W, X, pg, pb, pa, residual, epi_alpha, ms_out)
     _chk_aux(pp)
     tw = int(trans_w)
@@ -196,14 +208,21 @@ def absmax_of(*vectors):
     return out
 
 
+def _weight_operand(W, R, Cn, k_major, amax):
+    """(Wp, form) of the GEMMs that take the composite stacks' weight forms (include/ctn_hip.h, w_form): 3 = h3 pieces when the other
+    operand's tracked maximum `amax` is given, 2 = b6 pieces under the split arithmetics, else 1 = the stored matrix."""
+    if amax is not None:
+        return h3_pieces(W, R, Cn, k_major), 3
+    if _b3_planes_ok(R):
+        return _b3_pieces(W, R, Cn, k_major), 2
+    return W, 1
+
+
 def pw_gemm_h3(Wp, X, R, Cn, K, x_amax, pro=None, gbmax=None, residual=None, epi_alpha=None, ms_out=None, out_amax=None):
     """ctn_pw_gemm_h3: Out = W . f(X) on h3 pieces Wp (h3_pieces).  Returns (Out, epi_part|None)."""
     M, _, Kp = X.shape
-    out = torch.empty((M, R, Kp), dtype=F32, device=X.device)
-    epi_part = None
-    if epi_alpha is not None:
-        epi_part = torch.empty((M, lib.ctn_pw_stats_parts(M, R, Kp), 2), dtype=F64, device=X.device)
-    pp, npart, pg, pb, pa = (None, 0, None, None, None) if pro is None else (pro[0], pro[0].shape[1], pro[1], pro[2], pro[3])
+    out, epi_part = _out_epi(X, R, epi_alpha)
+    pp, npart, pg, pb, pa = _pro(pro)
     _chk(X, pg, pb, pa, residual, epi_alpha, ms_out, gbmax)
     _chk_aux(pp, x_amax, out_amax)
     lib.call("ctn_pw_gemm_h3", _p(Wp), _p(X), _p(out), M, R, Cn, K, Kp, _p(pp), npart, _p(pg), _p(pb), _p(pa), _p(ms_out),
@@ -225,10 +244,7 @@ def pw_dgrad_gln_h3(Wp, dOut, R, Cn, K, y, gamma, alpha, ms, g_amax):
 def pw_wgrad_h3(dOut, X, R, Cn, K, g_amax, x_amax, pro=None, gbmax=None, out=None, ws_tag="wgrad_h3"):
     """ctn_pw_wgrad_h3: dW[R,Cn] = sum_{m,k} dOut[m,r,k] * f(X[m,c,k]).  pro = (gamma, beta, alpha, ms[M,2])."""
     M, _, Kp = X.shape
-    dW = torch.empty((R, Cn), dtype=F32, device=X.device) if out is None else out
-    nbytes = lib.ctn_pw_wgrad_h3_workspace(M, R, Cn, Kp)
-    ws = _workspace(nbytes, X.device, ws_tag)
-    pg, pb, pa, pms = (None, None, None, None) if pro is None else pro
+    dW, ws, nbytes, (pg, pb, pa, pms) = _wgrad_operands(lib.ctn_pw_wgrad_h3_workspace, X, R, Cn, pro, out, ws_tag)
     _chk(dOut, X, pg, pb, pa, pms, gbmax)
     _chk_aux(g_amax, x_amax)
     lib.call("ctn_pw_wgrad_h3", _p(dOut), _p(X), _p(dW), M, R, Cn, K, Kp, _p(pg), _p(pb), _p(pa), _p(pms), _p(g_amax), _p(x_amax),
@@ -256,12 +272,7 @@ def pw_dgrad_cln(W, dOut, R, Cn, K, y, gamma, alpha, mean, rstd, g_amax=None):
     form the composite stack uses (h3 pieces when g_amax is given, b6 pieces under the split arithmetics, else the stored matrix).
     Returns (dN, col_part [M, nparts, Kp, 2] f64)."""
     M, _, Kp = dOut.shape
-    if g_amax is not None:
-        Wp, form = h3_pieces(W, R, Cn, True), 3
-    elif _b3_planes_ok(R):
-        Wp, form = _b3_pieces(W, R, Cn, True), 2
-    else:
-        Wp, form = W, 1
+    Wp, form = _weight_operand(W, R, Cn, True, g_amax)
     dn = torch.empty((M, R, Kp), dtype=F32, device=dOut.device)
     part = torch.empty((M, lib.ctn_pw_col_parts(M, R, Kp, form), Kp, 2), dtype=F64, device=dOut.device)
     _chk(dOut, y, gamma, alpha, mean, rstd)
@@ -275,12 +286,7 @@ def pw_dgrad_gln2(W, dOut, R, Cn, K, y, gamma, alpha, ms, gamma1, beta1, D, dila
     """ctn_pw_dgrad_gln2: dN = W^T . dOut (W stored [Cn, R]) + the EIGHT per-utterance sums partials from which both norms' backward
     sums follow (include/ctn_hip.h), on the weight form the composite stack uses.  Returns (dN, sums_part [M, parts, 8] f64)."""
     M, _, Kp = dOut.shape
-    if g_amax is not None:
-        Wp, form = h3_pieces(W, R, Cn, True), 3
-    elif _b3_planes_ok(R):
-        Wp, form = _b3_pieces(W, R, Cn, True), 2
-    else:
-        Wp, form = W, 1
+    Wp, form = _weight_operand(W, R, Cn, True, g_amax)
     dn = torch.empty((M, R, Kp), dtype=F32, device=dOut.device)
     part = torch.empty((M, lib.ctn_pw_stats_parts(M, R, Kp), 8), dtype=F64, device=dOut.device)
     _chk(dOut, y, gamma, alpha, ms, gamma1, beta1, D)
@@ -294,12 +300,9 @@ def pw_gemm_cln(W, X, R, Cn, K, alpha, x_amax=None):
     """ctn_pw_gemm_cln: Out = W . X (W stored [R, Cn]) + the per-frame column partials of (sum p, sum p^2), p = prelu(Out, alpha), on
     the weight form the composite stack uses.  Returns (Out, col_part [M, nparts, Kp, 2] f64)."""
     M, _, Kp = X.shape
-    if x_amax is not None:
-        Wp, form = h3_pieces(W, R, Cn, False), 3
-    elif _b3_planes_ok(R):
-        Wp, form = _b3_pieces(W, R, Cn, False), 2
-    else:
-        Wp, form = W.reshape(R, Cn).t().contiguous(), 1          # the composite's [I, O] copy (ctn_transpose_batch)
+    Wp, form = _weight_operand(W, R, Cn, False, x_amax)
+    if form == 1:
+        Wp = W.reshape(R, Cn).t().contiguous()                   # the forward operand is [I, O]: the composite's copy (ctn_transpose_batch)
     out = torch.empty((M, R, Kp), dtype=F32, device=X.device)
     part = torch.empty((M, lib.ctn_pw_col_parts(M, R, Kp, form), Kp, 2), dtype=F64, device=X.device)
     _chk(X, alpha)
@@ -444,13 +447,19 @@ def _workspace(nbytes, device, tag):
     return buf
 
 
+def _wgrad_operands(ws_bytes, X, R, Cn, pro, out, ws_tag):
+    """What both weight-gradient wrappers set up: the destination dW [R,Cn] (`out` when given), the tagged workspace and its size
+    (ws_bytes: the entry point's workspace function), and pro = (gamma, beta, alpha, ms[M,2]) | None unpacked."""
+    M, _, Kp = X.shape
+    dW = torch.empty((R, Cn), dtype=F32, device=X.device) if out is None else out
+    nbytes = ws_bytes(M, R, Cn, Kp)
+    return dW, _workspace(nbytes, X.device, ws_tag), nbytes, (None, None, None, None) if pro is None else pro
+
+
 def pw_wgrad(dOut, X, R, Cn, K, pro=None, out=None, ws_tag="wgrad"):
     """dW[R,Cn] = sum_{m,k} dOut[m,r,k] * f(X[m,c,k]).  pro = (gamma, beta, alpha, ms[M,2]).  out: optional destination."""
     M, _, Kp = X.shape
-    dW = torch.empty((R, Cn), dtype=F32, device=X.device) if out is None else out
-    nbytes = lib.ctn_pw_wgrad_workspace(M, R, Cn, Kp)
-    ws = _workspace(nbytes, X.device, ws_tag)
-    pg, pb, pa, pms = (None, None, None, None) if pro is None else pro
+    dW, ws, nbytes, (pg, pb, pa, pms) = _wgrad_operands(lib.ctn_pw_wgrad_workspace, X, R, Cn, pro, out, ws_tag)
     _chk(dOut, X, pg, pb, pa, pms)
     lib.call("ctn_pw_wgrad", _p(dOut), _p(X), _p(dW), M, R, Cn, K, Kp, _p(pg), _p(pb),
              _p(pa), _p(pms), _p(ws), nbytes, _stream())
@@ -504,9 +513,8 @@ def cln_bwd(dOut, Y, mean, rstd, gamma, alpha, K, add=None, relu_ref=None, sinks
 def dw_fwd(Y, D, K, dilation, causal, pro=None, epi_alpha=None, ms_out=None):
     M, H, Kp = Y.shape
     P = D.shape[-1]
-    Z = torch.empty_like(Y)
-    epi_part = None if epi_alpha is None else torch.empty((M, H, 2), dtype=F64, device=Y.device)
-    pp, npart, pg, pb, pa = (None, 0, None, None, None) if pro is None else (pro[0], pro[0].shape[1], pro[1], pro[2], pro[3])
+    Z, epi_part = _out_epi(Y, H, epi_alpha, parts=H)
+    pp, npart, pg, pb, pa = _pro(pro)
     _chk(Y, D, pg, pb, pa, epi_alpha, ms_out)
     _chk_aux(pp)
     lib.call("ctn_dw_fwd", _p(Y), _p(Z), _p(D), M, H, K, Kp, P, dilation, int(causal),
@@ -578,6 +586,44 @@ class Frontend(torch.autograd.Function):
 
 
 # ---------------------------------------------------------------------------------------
+# What GlnBlock and ClnBlock share: which GEMM / weight-gradient entry point runs, where, and in which order (the composite stacks'
+# rules, kernel by kernel)
+# ---------------------------------------------------------------------------------------
+def _gemm(W, X, R, Cn, K, amax, k_major=False, gb=None, **kw):
+    """Out = op(W) . f(X): on h3 pieces when X's tracked maximum `amax` is passed (gb = the prologue's (gamma, beta), whose maxima the
+    kernel needs), through pw_gemm otherwise.  k_major: W is stored [Cn, R].  kw: pro, residual, epi_alpha, ms_out."""
+    if amax is None:
+        return pw_gemm(W, X, R, Cn, K, trans_w=k_major, **kw)
+    Wp = h3_pieces(W, R, Cn, k_major)
+    return pw_gemm_h3(Wp, X, R, Cn, K, amax, gbmax=None if gb is None else absmax_of(*gb), **kw)
+
+
+def _wgrad(side, direct, dOut, X, R, Cn, K, sink, pro=None, h3=None, **first):
+    """dW of a block's 1x1 conv: on the side stream (-> None; first: _wgrad_async's riders), or on the current stream through
+    pw_wgrad_h3 (h3 = (g_amax, x_amax, gbmax)) / pw_wgrad; written into the sink when `direct`."""
+    if side:
+        return _wgrad_async(dOut, X, R, Cn, K, sink, pro=pro, h3=h3, **first)
+    out = sink if direct else None
+    if h3 is not None:
+        return pw_wgrad_h3(dOut, X, R, Cn, K, h3[0], h3[1], pro=pro, gbmax=h3[2], out=out)
+    return pw_wgrad(dOut, X, R, Cn, K, pro=pro, out=out)
+
+
+def _first_conv_bwd(side, direct, w1, g, x, dout, K, sink, x_amax, **first):
+    """Backward of a block's first 1x1 conv from g = dh1 [M,H,Kp]: (dx = w1^T . g + dout, dW1).  The order of the launches is part of
+    the behaviour: a side-stream weight gradient is issued BEFORE the input-gradient GEMM, a current-stream one after it.
+    x_amax: the maximum of x tracked by the forward pass under the h3 arithmetic (g's is measured here), else None."""
+    H, B = g.shape[1], x.shape[1]
+    g_amax = None if x_amax is None else absmax_rows(g)
+    wg = dict(first, h3=None if x_amax is None else (g_amax, x_amax, None))
+    dW1 = _wgrad(True, direct, g, x, H, B, K, sink, **wg) if side else None
+    dx, _ = _gemm(w1, g, B, H, K, g_amax, k_major=True, residual=dout)
+    if not side:
+        dW1 = _wgrad(False, direct, g, x, H, B, K, sink, **wg)
+    return dx, dW1
+
+
+# ---------------------------------------------------------------------------------------
 # TemporalBlock, gLN: 3 kernels forward, 6 (+3 tiny reductions) backward
 # ---------------------------------------------------------------------------------------
 class GlnBlock(torch.autograd.Function):
@@ -592,19 +638,14 @@ class GlnBlock(torch.autograd.Function):
         ms1 = torch.empty((M, 2), dtype=F32, device=dev)
         ms2 = torch.empty((M, 2), dtype=F32, device=dev)
         h3 = _h3_block(B, H)
-        if h3:      # the composite stack's arithmetic, kernel by kernel: the tracked maxima are exact, so measuring them here
-            #         (absmax_rows) gives the scales -- and the bits -- of the composite, whose producers track them on the fly
-            ax = absmax_rows(x)
-            h1, st1 = pw_gemm_h3(h3_pieces(w1, H, B, False), x, H, B, K, ax, epi_alpha=a1)
-            d, st2 = dw_fwd(h1, D, K, dilation, causal, pro=(st1, g1, b1, a1), epi_alpha=a2, ms_out=ms1)
-            ad = absmax_rows(d)
-            out, _ = pw_gemm_h3(h3_pieces(w2, B, H, False), d, B, H, K, ad, pro=(st2, g2, b2, a2), gbmax=absmax_of(g2, b2), residual=x, ms_out=ms2)
-            ctx.h3 = (ax, ad)
-        else:
-            h1, st1 = pw_gemm(w1, x, H, B, K, epi_alpha=a1)
-            d, st2 = dw_fwd(h1, D, K, dilation, causal, pro=(st1, g1, b1, a1), epi_alpha=a2, ms_out=ms1)
-            out, _ = pw_gemm(w2, d, B, H, K, pro=(st2, g2, b2, a2), residual=x, ms_out=ms2)
-            ctx.h3 = None
+        # h3: the composite stack's arithmetic, kernel by kernel: the tracked maxima are exact, so measuring them here (absmax_rows)
+        # gives the scales -- and the bits -- of the composite, whose producers track them on the fly
+        ax = absmax_rows(x) if h3 else None
+        h1, st1 = _gemm(w1, x, H, B, K, ax, epi_alpha=a1)
+        d, st2 = dw_fwd(h1, D, K, dilation, causal, pro=(st1, g1, b1, a1), epi_alpha=a2, ms_out=ms1)
+        ad = absmax_rows(d) if h3 else None
+        out, _ = _gemm(w2, d, B, H, K, ad, pro=(st2, g2, b2, a2), gb=(g2, b2), residual=x, ms_out=ms2)
+        ctx.h3 = (ax, ad) if h3 else None
         ctx.save_for_backward(x, h1, d, ms1, ms2, w1, a1, g1, b1, D, a2, g2, b2, w2)
         ctx.cfg = (K, dilation, causal)
         ctx.sinks = tuple(_sink(p) for p in (w1, a1, g1, b1, D, a2, g2, b2, w2))
@@ -626,27 +667,19 @@ class GlnBlock(torch.autograd.Function):
         st = _stream()
         # -- second 1x1: input gradient (+ gLN2 backward sums) and weight gradient
         _chk(dout, x, h1, d)
-        h3 = ctx.h3
+        ax, ad = ctx.h3 or (None, None)         # h3 arithmetic: the operand maxima the forward pass measured
+        h3 = ax is not None
         fuse4 = lib.ctn_gln_fuse() != 0         # no gLN-1' / PReLU-1' pass (the composite's rule; include/ctn_hip.h, "gln_fuse")
-        ady = None
-        if h3 is not None:
-            ax, ad = h3
-            ady, gbm = absmax_rows(dout), absmax_of(g2, b2)
+        ady, gbm = (absmax_rows(dout), absmax_of(g2, b2)) if h3 else (None, None)
         if fuse4:
             dn2, s2p = pw_dgrad_gln2(w2, dout, H, B, K, d, g2, a2, ms2, g1, b1, D, dilation, causal, g_amax=ady)
-        elif h3 is not None:
+        elif h3:
             dn2, s2p = pw_dgrad_gln_h3(h3_pieces(w2, H, B, True), dout, H, B, K, d, g2, a2, ms2, ady)
         else:
             dn2, s2p = pw_dgrad_gln(w2, dout, H, B, K, d, g2, a2, ms2)
         np2 = s2p.shape[1]
         side = direct and _SIDE_ENABLED
-        if side:
-            _wgrad_async(dout, d, B, H, K, sinks[8], pro=(g2, b2, a2, ms2), h3=None if h3 is None else (ady, ad, gbm))
-            dW2 = None
-        elif h3 is not None:
-            dW2 = pw_wgrad_h3(dout, d, B, H, K, ady, ad, pro=(g2, b2, a2, ms2), gbmax=gbm, out=sinks[8] if direct else None)
-        else:
-            dW2 = pw_wgrad(dout, d, B, H, K, pro=(g2, b2, a2, ms2), out=sinks[8] if direct else None)
+        dW2 = _wgrad(side, direct, dout, d, B, H, K, sinks[8], pro=(g2, b2, a2, ms2), h3=(ady, ad, gbm) if h3 else None)
         # -- gLN2 <- PReLU2 <- depthwise <- gLN1 output, one pass
         Fr = lib.ctn_dw_bwd_rows(P, 3 if fuse4 else 1)
         pc = torch.empty((Fr, M, H), dtype=F32, device=dev)
@@ -683,21 +716,8 @@ class GlnBlock(torch.autograd.Function):
         if not side_fin:
             finish()
         # -- first 1x1
-        h3w = None if h3 is None else (absmax_rows(dn1), ax, None)
-        if side:
-            if side_fin:
-                _wgrad_async(dn1, x, H, B, K, sinks[0], first=finish, first_inputs=(pc, da1p), h3=h3w)
-            else:
-                _wgrad_async(dn1, x, H, B, K, sinks[0], h3=h3w)
-        if h3 is not None:
-            dx, _ = pw_gemm_h3(h3_pieces(w1, B, H, True), dn1, B, H, K, h3w[0], residual=dout)
-        else:
-            dx, _ = pw_gemm(w1, dn1, B, H, K, trans_w=True, residual=dout)
-        if not side:
-            if h3 is not None:
-                dW1 = pw_wgrad_h3(dn1, x, H, B, K, h3w[0], ax, out=sinks[0] if direct else None)
-            else:
-                dW1 = pw_wgrad(dn1, x, H, B, K, out=sinks[0] if direct else None)
+        fin = dict(first=finish, first_inputs=(pc, da1p)) if side_fin else {}
+        dx, dW1 = _first_conv_bwd(side, direct, w1, dn1, x, dout, K, sinks[0], ax, **fin)
         if direct:
             return (dx,) + (None,) * 12
         return (dx, dW1.view(H, B, 1), da1, dg1, db1, dD, da2, dg2, db2, dW2.view(B, H, 1), None, None, None)
@@ -707,8 +727,6 @@ class GlnBlock(torch.autograd.Function):
 # The whole stack of gLN TemporalBlocks as ONE autograd node over the composite entry points
 # (ctn_tcn_gln_fwd / ctn_tcn_gln_bwd): the host side of 32 blocks is two C calls instead of ~400.
 # ---------------------------------------------------------------------------------------
-import ctypes  # noqa: E402
-
 _COMPOSITE = os.environ.get("CTN_COMPOSITE", "1") != "0"
 _GRAD_BUCKETS = None     # parallel.GradientBuckets: the stack's backward is then issued bucket by bucket (enable_overlap)
 
@@ -751,24 +769,123 @@ def _ptr_table(tensors):
     return (ctypes.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
 
 
-def tcn_gln_infer(x0, K, dilations, causal, params):
-    """Forward of the stack without saving activations (torch.no_grad paths): two x slots, one h1 / d slot."""
+# ---- one routine for both stacks.  They differ in what is listed here: the entry points (include/ctn_hip.h: `entry`_fwd, _bwd and
+# their _workspace functions), the tags of the cached workspaces (forward, backward, backward call i of a bucketed pass), the
+# activations kept per block -- handed to both C calls in this order, between xs and amax --, whether the weight-gradient stream
+# also honours CTN_CLN_SIDE, and the cLN stack's guard on ctn_tune("cln_fuse").
+def _gln_acts(n, M, H, Kp, dev):
+    """h1, d [n,M,H,Kp] and (mean, rstd) of both norms [n,2,M,2]."""
+    return (torch.empty((n, M, H, Kp), dtype=F32, device=dev), torch.empty((n, M, H, Kp), dtype=F32, device=dev),
+            torch.empty((n, 2, M, 2), dtype=F32, device=dev))
+
+
+def _cln_acts(n, M, H, Kp, dev):
+    """h1, n1, d, n2 [n,M,H,Kp] and (mean1, rstd1, mean2, rstd2) [n,4,M,Kp]."""
+    fuse1 = lib.ctn_cln_fuse() >= 2            # the first norm's output is neither written nor read (include/ctn_hip.h, "cln_fuse")
+    hs = torch.empty((3 if fuse1 else 4, n, M, H, Kp), dtype=F32, device=dev)
+    hs = (hs[0], hs[0], hs[1], hs[2]) if fuse1 else tuple(hs)          # (n1s must be a valid pointer: never touched when fused)
+    return hs + (torch.empty((n, 4, M, Kp), dtype=F32, device=dev),)
+
+
+def _cln_fuse_guard(ctx, backward):
+    """Level 2 stores no n1: remember what the forward pass ran under; the backward pass must run under the same rule."""
+    if not backward:
+        ctx.fuse = lib.ctn_cln_fuse()
+    elif (lib.ctn_cln_fuse() >= 2) != (ctx.fuse >= 2):
+        raise CtnError("ctn_tune(\"cln_fuse\") changed between the forward and the backward pass of a cLN stack (%d -> %d): the first "
+                       "norm's output is stored only below level 2" % (ctx.fuse, lib.ctn_cln_fuse()))
+
+
+_Stack = collections.namedtuple("_Stack", "name entry tags acts cln_side guard")
+_GLN = _Stack("TcnGln", "ctn_tcn_gln", ("tcn_fwd", "tcn_bwd", "tcn_bwd_bucket%d"), _gln_acts, False, None)
+_CLN = _Stack("TcnCln", "ctn_tcn_cln", ("tcn_cln_fwd", "tcn_cln_bwd", "tcn_cln_bwd_bucket%d"), _cln_acts, True, _cln_fuse_guard)
+
+
+def _stack_forward(S, ctx, x0, K, dilations, causal, params):
+    """x0 [M,B,Kp] -> output of the last TemporalBlock.  ctx = None: inference -- nothing is kept: two ping-pong x slots and one slot
+    of every activation instead of one per block."""
+    save = ctx is not None
     nb = len(dilations)
+    if save:
+        if len(params) != nb * NPARAM:
+            raise ValueError("%s: expected %d parameter tensors, got %d" % (S.name, nb * NPARAM, len(params)))
+        x0 = _c(x0)
     M, B, Kp = x0.shape
     H, P = params[0].shape[0], params[4].shape[-1]
+    if save and (H % 4 or B % 4):
+        raise ValueError("HIP path needs B and H to be multiples of 4")
     dev = x0.device
     _chk(x0, *params)
-    xs = torch.empty((2, M, B, Kp), dtype=F32, device=dev)
-    h1 = torch.empty((M, H, Kp), dtype=F32, device=dev)
-    d = torch.empty((M, H, Kp), dtype=F32, device=dev)
-    ms = torch.empty((2, M, 2), dtype=F32, device=dev)
-    amax = torch.empty((nb, 2, M, AMAX_SLOTS), dtype=torch.int32, device=dev)     # h3 arithmetic: tracked operand maxima (zeroed by the call)
-    nbytes = lib.ctn_tcn_gln_fwd_workspace(M, B, H, Kp, nb)
-    ws = _workspace(nbytes, dev, "tcn_fwd")
+    xs = torch.empty((nb if save else 2, M, B, Kp), dtype=F32, device=dev)
+    acts = S.acts(nb if save else 1, M, H, Kp, dev)
+    amax = torch.empty((nb, 2, M, AMAX_SLOTS), dtype=torch.int32, device=dev)     # h3 arithmetic: tracked operand maxima of every block (zeroed by the call)
+    nbytes = getattr(lib, S.entry + "_fwd_workspace")(M, B, H, Kp, nb)
+    ws = _workspace(nbytes, dev, S.tags[0])
     dil = (ctypes.c_int * nb)(*dilations)
-    lib.call("ctn_tcn_gln_fwd", _ptr_table(params), dil, nb, _p(x0), _p(xs), _p(h1), _p(d), _p(ms), _p(amax), 0,
+    lib.call(S.entry + "_fwd", _ptr_table(params), dil, nb, _p(x0), _p(xs), *[_p(t) for t in acts], _p(amax), int(save),
              M, B, H, K, Kp, P, int(causal), _p(ws), nbytes, _stream(), _fwd_side(dev))
-    return xs[(nb - 1) & 1]
+    if not save:
+        return xs[(nb - 1) & 1]
+    # our own buffers, written once and read once by backward: plain attributes (released as soon as they are consumed)
+    ctx.acts = (x0, xs, acts, amax)
+    ctx.save_for_backward(*params)      # (autograd's version check: an in-place parameter update before backward is an error)
+    ctx.cfg = (K, dil, nb, causal, P)
+    if S.guard is not None:
+        S.guard(ctx, False)
+    ctx.sinks = tuple(_sink(p) for p in params)
+    return xs[nb - 1]
+
+
+def _stack_backward(S, ctx, dout):
+    if ctx.acts is None:
+        raise CtnError("composite TemporalBlock stack: backward called twice on one forward pass (its saved activations are "
+                       "released after the first); set CTN_COMPOSITE=0 for retain_graph=True")
+    x0, xs, acts, amax = ctx.acts
+    if S.guard is not None:
+        S.guard(ctx, True)
+    params = ctx.saved_tensors
+    K, dil, nb, causal, P = ctx.cfg
+    dout = _c(dout)
+    _, M, B, Kp = xs.shape
+    H = acts[0].shape[2]
+    dev = x0.device
+    _chk(dout)
+    direct = all(s is not None for s in ctx.sinks)
+    if direct:
+        _claim_sinks(params[0])
+        gdst = ctx.sinks
+    else:                       # plain autograd parameters: gradients land in one scratch buffer, returned as views
+        sizes = [(p.numel() + 3) // 4 * 4 for p in params]
+        flat = torch.empty((sum(sizes),), dtype=F32, device=dev)
+        gdst, o = [], 0
+        for p, n in zip(params, sizes):
+            gdst.append(flat[o:o + p.numel()].view(p.shape))
+            o += n
+    dxs = torch.empty((nb, M, B, Kp), dtype=F32, device=dev)
+    dh1s = torch.empty((nb, M, H, Kp), dtype=F32, device=dev)         # per block: the gradient at the first 1x1 conv's output
+    ws_bytes = getattr(lib, S.entry + "_bwd_workspace")
+    nbytes = ws_bytes(M, B, H, Kp, P, nb)
+    ws = _workspace(nbytes, dev, S.tags[1])
+    side = _side_stream(dev) if (direct and _SIDE_ENABLED and (_CLN_SIDE or not S.cln_side)) else None
+    ranges, gb = _bucket_ranges(nb, direct)
+    for i, (lo, hi) in enumerate(ranges):
+        # gradient buckets: every call but the last leaves the weight-gradient stream un-joined (its own workspace), and the
+        # bucket's all-reduce is issued BEHIND that stream -- all parameter gradients of the stack are produced there --
+        # while the main stream already runs the next bucket's chain
+        unjoined = gb is not None and side is not None and i + 1 < len(ranges)
+        nbi = ws_bytes(M, B, H, Kp, P, hi - lo) if gb is not None else nbytes
+        wsi = _workspace(nbi, dev, S.tags[2] % i) if unjoined else ws
+        sl = slice(lo * NPARAM, hi * NPARAM)
+        lib.call(S.entry + "_bwd", _ptr_table(params[sl]), _ptr_table(gdst[sl]), (ctypes.c_int * (hi - lo))(*dil[lo:hi]), hi - lo,
+                 _p(x0 if lo == 0 else xs[lo - 1]), _p(xs[lo]), *[_p(t[lo]) for t in acts], _p(amax[lo]),
+                 _p(dout if hi == nb else dxs[hi]), _p(dxs[lo]), _p(dh1s[lo]), M, B, H, K, Kp, P, int(causal), _p(wsi), nbi,
+                 _stream(), 0 if side is None else side.cuda_stream, int(unjoined))
+        if gb is not None:
+            with torch.cuda.stream(side if side is not None else torch.cuda.current_stream(dev)):
+                gb.bucket_ready(gdst[sl])
+    ctx.acts = None             # release 4 GB of saved activations as soon as they are consumed
+    # the call joined the side stream into the current one, so stream-ordered reuse of these buffers is safe
+    return (dxs[0], None, None, None) + ((None,) * len(params) if direct else tuple(gdst))
 
 
 class TcnGln(torch.autograd.Function):
@@ -776,103 +893,11 @@ class TcnGln(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x0, K, dilations, causal, *params):
-        nb = len(dilations)
-        if len(params) != nb * NPARAM:
-            raise ValueError("TcnGln: expected %d parameter tensors, got %d" % (nb * NPARAM, len(params)))
-        x0 = _c(x0)
-        M, B, Kp = x0.shape
-        H, P = params[0].shape[0], params[4].shape[-1]
-        if H % 4 or B % 4:
-            raise ValueError("HIP path needs B and H to be multiples of 4")
-        dev = x0.device
-        _chk(x0, *params)
-        xs = torch.empty((nb, M, B, Kp), dtype=F32, device=dev)
-        h1s = torch.empty((nb, M, H, Kp), dtype=F32, device=dev)
-        ds = torch.empty((nb, M, H, Kp), dtype=F32, device=dev)
-        ms = torch.empty((nb, 2, M, 2), dtype=F32, device=dev)
-        amax = torch.empty((nb, 2, M, AMAX_SLOTS), dtype=torch.int32, device=dev)     # h3 arithmetic: tracked maxima of every block's input / depthwise output
-        nbytes = lib.ctn_tcn_gln_fwd_workspace(M, B, H, Kp, nb)
-        ws = _workspace(nbytes, dev, "tcn_fwd")
-        dil = (ctypes.c_int * nb)(*dilations)
-        lib.call("ctn_tcn_gln_fwd", _ptr_table(params), dil, nb, _p(x0), _p(xs), _p(h1s), _p(ds), _p(ms), _p(amax), 1,
-                 M, B, H, K, Kp, P, int(causal), _p(ws), nbytes, _stream(), _fwd_side(dev))
-        # our own buffers, written once and read once by backward: plain attributes (released as soon as they are consumed)
-        ctx.acts = (x0, xs, h1s, ds, ms, amax)
-        ctx.save_for_backward(*params)      # (autograd's version check: an in-place parameter update before backward is an error)
-        ctx.cfg = (K, dil, nb, causal, P)
-        ctx.sinks = tuple(_sink(p) for p in params)
-        return xs[nb - 1]
+        return _stack_forward(_GLN, ctx, x0, K, dilations, causal, params)
 
     @staticmethod
     def backward(ctx, dout):
-        if ctx.acts is None:
-            raise CtnError("composite TemporalBlock stack: backward called twice on one forward pass (its saved activations are "
-                           "released after the first); set CTN_COMPOSITE=0 for retain_graph=True")
-        x0, xs, h1s, ds, ms, amax = ctx.acts
-        params = ctx.saved_tensors
-        K, dil, nb, causal, P = ctx.cfg
-        dout = _c(dout)
-        _, M, B, Kp = xs.shape
-        H = h1s.shape[2]
-        dev = x0.device
-        _chk(dout)
-        direct = all(s is not None for s in ctx.sinks)
-        if direct:
-            _claim_sinks(params[0])
-            gdst, flat = ctx.sinks, None
-        else:                       # plain autograd parameters: gradients land in one scratch buffer, returned as views
-            sizes = [(p.numel() + 3) // 4 * 4 for p in params]
-            flat = torch.empty((sum(sizes),), dtype=F32, device=dev)
-            gdst, o = [], 0
-            for p, n in zip(params, sizes):
-                gdst.append(flat[o:o + p.numel()].view(p.shape))
-                o += n
-        dxs = torch.empty((nb, M, B, Kp), dtype=F32, device=dev)
-        dn1s = torch.empty((nb, M, H, Kp), dtype=F32, device=dev)
-        nbytes = lib.ctn_tcn_gln_bwd_workspace(M, B, H, Kp, P, nb)
-        ws = _workspace(nbytes, dev, "tcn_bwd")
-        side = _side_stream(dev) if (direct and _SIDE_ENABLED) else None
-        ranges, gb = _bucket_ranges(nb, direct)
-        for i, (lo, hi) in enumerate(ranges):
-            # gradient buckets: every call but the last leaves the weight-gradient stream un-joined (its own workspace), and the
-            # bucket's all-reduce is issued BEHIND that stream -- all parameter gradients of the stack are produced there --
-            # while the main stream already runs the next bucket's chain
-            unjoined = gb is not None and side is not None and i + 1 < len(ranges)
-            nbi = lib.ctn_tcn_gln_bwd_workspace(M, B, H, Kp, P, hi - lo) if gb is not None else nbytes
-            wsi = _workspace(nbi, dev, "tcn_bwd_bucket%d" % i) if unjoined else ws
-            lib.call("ctn_tcn_gln_bwd", _ptr_table(params[lo * NPARAM:hi * NPARAM]), _ptr_table(gdst[lo * NPARAM:hi * NPARAM]),
-                     (ctypes.c_int * (hi - lo))(*dil[lo:hi]), hi - lo, _p(x0 if lo == 0 else xs[lo - 1]), _p(xs[lo]), _p(h1s[lo]),
-                     _p(ds[lo]), _p(ms[lo]), _p(amax[lo]), _p(dout if hi == nb else dxs[hi]), _p(dxs[lo]), _p(dn1s[lo]), M, B, H, K, Kp, P,
-                     int(causal), _p(wsi), nbi, _stream(), 0 if side is None else side.cuda_stream, int(unjoined))
-            if gb is not None:
-                with torch.cuda.stream(side if side is not None else torch.cuda.current_stream(dev)):
-                    gb.bucket_ready(gdst[lo * NPARAM:hi * NPARAM])
-        ctx.acts = None             # release 4 GB of saved activations as soon as they are consumed
-        # the call joined the side stream into the current one, so stream-ordered reuse of these buffers is safe
-        if direct:
-            return (dxs[0], None, None, None) + (None,) * len(params)
-        return (dxs[0], None, None, None) + tuple(gdst)
-
-
-def tcn_cln_infer(x0, K, dilations, causal, params):
-    """cLN stack without saving activations (torch.no_grad paths)."""
-    nb = len(dilations)
-    M, B, Kp = x0.shape
-    H, P = params[0].shape[0], params[4].shape[-1]
-    dev = x0.device
-    _chk(x0, *params)
-    xs = torch.empty((2, M, B, Kp), dtype=F32, device=dev)
-    fuse1 = lib.ctn_cln_fuse() >= 2
-    h = torch.empty((3 if fuse1 else 4, M, H, Kp), dtype=F32, device=dev)
-    h = (h[0], h[0], h[1], h[2]) if fuse1 else (h[0], h[1], h[2], h[3])
-    st = torch.empty((4, M, Kp), dtype=F32, device=dev)
-    amax = torch.empty((nb, 2, M, AMAX_SLOTS), dtype=torch.int32, device=dev)     # h3 arithmetic: tracked operand maxima (zeroed by the call)
-    nbytes = lib.ctn_tcn_cln_fwd_workspace(M, B, H, Kp, nb)
-    ws = _workspace(nbytes, dev, "tcn_cln_fwd")
-    dil = (ctypes.c_int * nb)(*dilations)
-    lib.call("ctn_tcn_cln_fwd", _ptr_table(params), dil, nb, _p(x0), _p(xs), _p(h[0]), _p(h[1]), _p(h[2]), _p(h[3]), _p(st), _p(amax), 0,
-             M, B, H, K, Kp, P, int(causal), _p(ws), nbytes, _stream(), _fwd_side(dev))
-    return xs[(nb - 1) & 1]
+        return _stack_backward(_GLN, ctx, dout)
 
 
 class TcnCln(torch.autograd.Function):
@@ -881,82 +906,21 @@ class TcnCln(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x0, K, dilations, causal, *params):
-        nb = len(dilations)
-        if len(params) != nb * NPARAM:
-            raise ValueError("TcnCln: expected %d parameter tensors, got %d" % (nb * NPARAM, len(params)))
-        x0 = _c(x0)
-        M, B, Kp = x0.shape
-        H, P = params[0].shape[0], params[4].shape[-1]
-        if H % 4 or B % 4:
-            raise ValueError("HIP path needs B and H to be multiples of 4")
-        dev = x0.device
-        _chk(x0, *params)
-        xs = torch.empty((nb, M, B, Kp), dtype=F32, device=dev)
-        fuse1 = lib.ctn_cln_fuse() >= 2            # the first norm's output is neither written nor read (include/ctn_hip.h, "cln_fuse")
-        hs = torch.empty((3 if fuse1 else 4, nb, M, H, Kp), dtype=F32, device=dev)          # h1, [n1,] d, n2
-        hs = (hs[0], hs[0], hs[1], hs[2]) if fuse1 else (hs[0], hs[1], hs[2], hs[3])          # (n1s must be a valid pointer: never touched when fused)
-        st = torch.empty((nb, 4, M, Kp), dtype=F32, device=dev)            # mean1, rstd1, mean2, rstd2
-        amax = torch.empty((nb, 2, M, AMAX_SLOTS), dtype=torch.int32, device=dev)     # h3 arithmetic: tracked maxima of every block's input / second norm output
-        nbytes = lib.ctn_tcn_cln_fwd_workspace(M, B, H, Kp, nb)
-        ws = _workspace(nbytes, dev, "tcn_cln_fwd")
-        dil = (ctypes.c_int * nb)(*dilations)
-        lib.call("ctn_tcn_cln_fwd", _ptr_table(params), dil, nb, _p(x0), _p(xs), _p(hs[0]), _p(hs[1]), _p(hs[2]), _p(hs[3]), _p(st), _p(amax), 1,
-                 M, B, H, K, Kp, P, int(causal), _p(ws), nbytes, _stream(), _fwd_side(dev))
-        ctx.acts = (x0, xs, hs, st, amax)
-        ctx.save_for_backward(*params)      # (autograd's version check: an in-place parameter update before backward is an error)
-        ctx.cfg = (K, dil, nb, causal, P)
-        ctx.fuse = lib.ctn_cln_fuse()       # what the forward pass stored (level 2: no n1) -- the backward pass must run under the same value
-        ctx.sinks = tuple(_sink(p) for p in params)
-        return xs[nb - 1]
+        return _stack_forward(_CLN, ctx, x0, K, dilations, causal, params)
 
     @staticmethod
     def backward(ctx, dout):
-        if ctx.acts is None:
-            raise CtnError("composite TemporalBlock stack: backward called twice on one forward pass (its saved activations are "
-                           "released after the first); set CTN_COMPOSITE=0 for retain_graph=True")
-        x0, xs, hs, st, amax = ctx.acts
-        if (lib.ctn_cln_fuse() >= 2) != (ctx.fuse >= 2):
-            raise CtnError("ctn_tune(\"cln_fuse\") changed between the forward and the backward pass of a cLN stack (%d -> %d): the first "
-                           "norm's output is stored only below level 2" % (ctx.fuse, lib.ctn_cln_fuse()))
-        params = ctx.saved_tensors
-        K, dil, nb, causal, P = ctx.cfg
-        dout = _c(dout)
-        _, M, B, Kp = xs.shape
-        H = hs[0].shape[2]
-        dev = x0.device
-        _chk(dout)
-        direct = all(s is not None for s in ctx.sinks)
-        if direct:
-            _claim_sinks(params[0])
-            gdst = ctx.sinks
-        else:
-            sizes = [(p.numel() + 3) // 4 * 4 for p in params]
-            flat = torch.empty((sum(sizes),), dtype=F32, device=dev)
-            gdst, o = [], 0
-            for p, n in zip(params, sizes):
-                gdst.append(flat[o:o + p.numel()].view(p.shape))
-                o += n
-        dxs = torch.empty((nb, M, B, Kp), dtype=F32, device=dev)
-        dh1s = torch.empty((nb, M, H, Kp), dtype=F32, device=dev)
-        nbytes = lib.ctn_tcn_cln_bwd_workspace(M, B, H, Kp, P, nb)
-        ws = _workspace(nbytes, dev, "tcn_cln_bwd")
-        side = _side_stream(dev) if (direct and _SIDE_ENABLED and _CLN_SIDE) else None
-        ranges, gb = _bucket_ranges(nb, direct)
-        for i, (lo, hi) in enumerate(ranges):            # (gradient buckets: as in TcnGln.backward)
-            unjoined = gb is not None and side is not None and i + 1 < len(ranges)
-            nbi = lib.ctn_tcn_cln_bwd_workspace(M, B, H, Kp, P, hi - lo) if gb is not None else nbytes
-            wsi = _workspace(nbi, dev, "tcn_cln_bwd_bucket%d" % i) if unjoined else ws
-            lib.call("ctn_tcn_cln_bwd", _ptr_table(params[lo * NPARAM:hi * NPARAM]), _ptr_table(gdst[lo * NPARAM:hi * NPARAM]),
-                     (ctypes.c_int * (hi - lo))(*dil[lo:hi]), hi - lo, _p(x0 if lo == 0 else xs[lo - 1]), _p(xs[lo]), _p(hs[0][lo]),
-                     _p(hs[1][lo]), _p(hs[2][lo]), _p(hs[3][lo]), _p(st[lo]), _p(amax[lo]), _p(dout if hi == nb else dxs[hi]), _p(dxs[lo]), _p(dh1s[lo]),
-                     M, B, H, K, Kp, P, int(causal), _p(wsi), nbi, _stream(), 0 if side is None else side.cuda_stream, int(unjoined))
-            if gb is not None:
-                with torch.cuda.stream(side if side is not None else torch.cuda.current_stream(dev)):
-                    gb.bucket_ready(gdst[lo * NPARAM:hi * NPARAM])
-        ctx.acts = None
-        if direct:
-            return (dxs[0], None, None, None) + (None,) * len(params)
-        return (dxs[0], None, None, None) + tuple(gdst)
+        return _stack_backward(_CLN, ctx, dout)
+
+
+def tcn_gln_infer(x0, K, dilations, causal, params):
+    """Forward of the gLN stack without saving activations (torch.no_grad paths)."""
+    return _stack_forward(_GLN, None, x0, K, dilations, causal, params)
+
+
+def tcn_cln_infer(x0, K, dilations, causal, params):
+    """cLN stack without saving activations (torch.no_grad paths)."""
+    return _stack_forward(_CLN, None, x0, K, dilations, causal, params)
 
 
 # ---------------------------------------------------------------------------------------
@@ -979,18 +943,12 @@ class ClnBlock(torch.autograd.Function):
             d = dw_fwd_cln(h1, D, K, dilation, causal, mean1, rstd1, g1, b1, a1)
             n1 = h1.new_empty(0)                    # never stored
         else:
-            if h3:
-                h1, _ = pw_gemm_h3(h3_pieces(w1, H, B, False), x, H, B, K, ax)
-            else:
-                h1, _ = pw_gemm(w1, x, H, B, K)
+            h1, _ = _gemm(w1, x, H, B, K, ax)
             n1, mean1, rstd1 = cln_fwd(h1, g1, b1, a1, K)
             d, _ = dw_fwd(n1, D, K, dilation, causal)
         n2, mean2, rstd2 = cln_fwd(d, g2, b2, a2, K)
-        if h3:
-            an = absmax_rows(n2)
-            out, _ = pw_gemm_h3(h3_pieces(w2, B, H, False), n2, B, H, K, an, residual=x)
-        else:
-            out, _ = pw_gemm(w2, n2, B, H, K, residual=x)
+        an = absmax_rows(n2) if h3 else None
+        out, _ = _gemm(w2, n2, B, H, K, an, residual=x)
         ctx.h3 = (ax, an) if h3 else None
         ctx.save_for_backward(x, h1, n1, d, n2, mean1, rstd1, mean2, rstd2, w1, a1, g1, D, a2, g2, w2, b1)
         ctx.cfg = (K, dilation, causal)
@@ -1015,25 +973,15 @@ class ClnBlock(torch.autograd.Function):
         # 1024-thread cLN kernels fill every wave slot); with the w4 kernel and the 5 us slab reduce it wins, 20.07 vs
         # 21.7 ms/step at paper size (CONFIG=causal benchmarks/ab_step.py).  CTN_CLN_SIDE=0 turns it off.
         side = direct and _SIDE_ENABLED and _CLN_SIDE
-        h3 = ctx.h3
+        ax, an = ctx.h3 or (None, None)                 # h3 arithmetic: the operand maxima the forward pass measured
+        h3 = ax is not None
         fuse = lib.ctn_cln_fuse() != 0 or ctx.fuse1     # the second norm's backward inside the GEMM epilogue + the depthwise backward (the composite's rule)
-        ady = None
-        if h3 is not None:
-            ax, an = h3
-            ady = absmax_rows(dout)
+        ady = absmax_rows(dout) if h3 else None
         if fuse:
             dn2, colp = pw_dgrad_cln(w2, dout, H, B, K, d, g2, a2, mean2, rstd2, g_amax=ady)
-        elif h3 is not None:
-            dn2, _ = pw_gemm_h3(h3_pieces(w2, H, B, True), dout, H, B, K, ady)
         else:
-            dn2, _ = pw_gemm(w2, dout, H, B, K, trans_w=True)
-        if side:
-            _wgrad_async(dout, n2, B, H, K, sk[8], h3=None if h3 is None else (ady, an, None))
-            dW2 = None
-        elif h3 is not None:
-            dW2 = pw_wgrad_h3(dout, n2, B, H, K, ady, an, out=sk[8] if direct else None)
-        else:
-            dW2 = pw_wgrad(dout, n2, B, H, K, out=sk[8] if direct else None)
+            dn2, _ = _gemm(w2, dout, H, B, K, ady, k_major=True)
+        dW2 = _wgrad(side, direct, dout, n2, B, H, K, sk[8], h3=(ady, an, None) if h3 else None)
         if fuse:
             fc = cln_bwd_frame(colp, mean2, rstd2, H)
             dn1, dD, dg2, db2, da2 = dw_bwd_cln(dn2, d, h1 if ctx.fuse1 else n1, D, K, dilation, causal, g2, a2, fc,
@@ -1048,19 +996,7 @@ class ClnBlock(torch.autograd.Function):
                      0, 0, 0, 0, 0, 0, 0, 0, 0, _p(pc), 0, _stream())
             dD = reduce_mid(pc, P, M, H).t().contiguous().view(H, 1, P)
         dh1, dg1, db1, da1 = cln_bwd(dn1, h1, mean1, rstd1, g1, a1, K, sinks=(sk[2], sk[3], sk[1]) if direct else None)
-        adh = None if h3 is None else absmax_rows(dh1)
-        if side:
-            _wgrad_async(dh1, x, H, B, K, sk[0], h3=None if h3 is None else (adh, ax, None))
-            dW1 = None
-        if h3 is not None:
-            dx, _ = pw_gemm_h3(h3_pieces(w1, B, H, True), dh1, B, H, K, adh, residual=dout)
-        else:
-            dx, _ = pw_gemm(w1, dh1, B, H, K, trans_w=True, residual=dout)
-        if not side:
-            if h3 is not None:
-                dW1 = pw_wgrad_h3(dh1, x, H, B, K, adh, ax, out=sk[0] if direct else None)
-            else:
-                dW1 = pw_wgrad(dh1, x, H, B, K, out=sk[0] if direct else None)
+        dx, dW1 = _first_conv_bwd(side, direct, w1, dh1, x, dout, K, sk[0], ax)
         if direct:
             if not fuse:
                 sk[4].copy_(dD)
@@ -1103,15 +1039,7 @@ class BnBlock(torch.autograd.Function):
     norms replaced by (PReLU +) BatchNorm1d.  bn1 / bn2 = (running_mean, running_var, training, eps, momentum)."""
 
     @staticmethod
-    def forward(ctx, *args):
-        return BnBlock._forward(ctx, *args)
-
-    @staticmethod
-    def backward(ctx, dout):
-        return BnBlock._backward(ctx, dout)
-
-    @staticmethod
-    def _forward(ctx, x, w1, a1, g1, b1, D, a2, g2, b2, w2, K, dilation, causal, bn1, bn2):
+    def forward(ctx, x, w1, a1, g1, b1, D, a2, g2, b2, w2, K, dilation, causal, bn1, bn2):
         x = _c(x)
         M, B, Kp = x.shape
         H = w1.shape[0]
@@ -1128,7 +1056,7 @@ class BnBlock(torch.autograd.Function):
         return out
 
     @staticmethod
-    def _backward(ctx, dout):
+    def backward(ctx, dout):
         x, h1, n1, d, n2, mr1, mr2, w1, a1, g1, D, a2, g2, w2 = ctx.saved_tensors
         K, dilation, causal, tr1, tr2 = ctx.cfg
         dout = _c(dout)
@@ -1289,9 +1217,7 @@ class SiSnrPit(torch.autograd.Function):
         source, estimate, lengths, coef, jsel = ctx.saved_tensors
         Bn, C, T = source.shape
         d_est = torch.empty_like(source)
-        g_loss = None if g_loss is None else _c(g_loss.to(F32))
-        g_max = None if g_max is None else _c(g_max.to(F32))
-        _chk(g_loss, g_max)
+        g_loss, g_max = _upstream(g_loss, g_max)
         lib.call("ctn_sisnr_pit_bwd", _p(source), _p(estimate), _p(lengths), _p(coef), _p(jsel), _p(g_loss), _p(g_max),
                  Bn, C, T, _p(d_est), _stream())
         if g_est is not None:
