@@ -546,7 +546,8 @@ __global__ __launch_bounds__(NT) void dw_bwd_kernel(DwBwdArgs a) {
         if constexpr (APPLY) {
             const float v5 = wave_sum(dal1);
             if (live && lane == 0) a.pc[(size_t)(P_ + 5) * MH + rc] = v5;
-            if (a.amax_out != nullptr) block_amax_atomic<NT>(amax1, red, a.amax_out + (size_t)m * CTN_AMAX_SLOTS, blockIdx.x % hb);
+            // (a dead wave's image is 0, but apply1 still gives it -rstd1 S1'/n: it must not reach the maximum)
+            if (a.amax_out != nullptr) block_amax_atomic<NT>(live ? amax1 : 0.f, red, a.amax_out + (size_t)m * CTN_AMAX_SLOTS, blockIdx.x % hb);
         }
     }
 }
