@@ -28,6 +28,28 @@ constexpr int BWD_BUF_S = 768, BWD_BUF_M = 1280, BWD_BUF_L = 1792;     // backwa
 __device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
 __device__ __forceinline__ int floor4(int v) { return (v >> 2) << 2; }  // arithmetic shift: floors negatives
 
+// Early loads.  The row kernels below issue a whole batch of a wave's 16-byte loads before they use the first of them, so a
+// wave pays one memory round trip per batch and its bandwidth does not hang on how many sibling waves the CU still holds.
+// Such a load is issued before the code that decides whether the frame exists, so it must not be able to fault: every
+// wave reads through a buffer resource that spans exactly its own row (no bytes at all for a dead wave), and a frame outside
+// [0, Kp) is sent to ROW_OOB, an offset past the end of any row: the hardware range check answers 0 and no address outside
+// the tensor is formed.  (make_rsrc / buf_ld4 as in ctn_gemm_common.h, whose other names collide with this file's.)
+typedef float f32x4v __attribute__((ext_vector_type(4)));
+constexpr int ROW_OOB = (int)0x80000000u;
+constexpr int CHUNK = 256;       // frames that one wave covers with one float4 per lane
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* base, unsigned bytes) {
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, bytes, 0x00020000);
+}
+__device__ __forceinline__ float4 buf_ld4(__amdgpu_buffer_rsrc_t r, int voff) {
+    const f32x4v f = __builtin_bit_cast(f32x4v, __builtin_amdgcn_raw_buffer_load_b128(r, voff, 0, 0));
+    return make_float4(f.x, f.y, f.z, f.w);
+}
+__device__ __forceinline__ float uni(float v) {      // a wave-uniform value into a scalar register
+    return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v)));
+}
+// byte offset of frame k (a multiple of 4) in a row of Kp frames; `in` = the lane takes part in this chunk at all
+__device__ __forceinline__ int row_voff(int k, int Kp, bool in) { return (in && k >= 0 && k < Kp) ? k * 4 : ROW_OOB; }
+
 // ---------------------------------------------------------------------------
 // depthwise forward:  z[k] = sum_j D[c,j] * n[k + j*dil - padl],  n = (PRO ? gLN(prelu(y)) : y)
 // ---------------------------------------------------------------------------
@@ -46,7 +68,8 @@ template <int PRO, bool EPI, int FWD_BUF, bool VEC4, int PT>      // PT: compile
 __global__ __launch_bounds__(NT) void dw_fwd_kernel(DwFwdArgs a) {
     __shared__ __attribute__((aligned(16))) float buf[ROWS][FWD_BUF];
     __shared__ double red[NT / 64];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);      // (scalar: the row and its buffer resources are wave-uniform)
     const int hb = (a.H + ROWS - 1) / ROWS;
     const int m = blockIdx.x / hb;
     const int c = (blockIdx.x % hb) * ROWS + wave;
@@ -55,10 +78,13 @@ __global__ __launch_bounds__(NT) void dw_fwd_kernel(DwFwdArgs a) {
     const float* __restrict__ y = a.Y + row;
     float* __restrict__ z = a.Z + row;
     float* __restrict__ L = buf[wave];
+    const unsigned rbytes = live ? (unsigned)a.Kp * 4u : 0u;
+    const __amdgpu_buffer_rsrc_t rsY = make_rsrc(y, rbytes);
 
     float mean = 0.f, rstd = 1.f, alpha = 0.f, g = 1.f, b = 0.f;
     const float* __restrict__ cmu = PRO == 2 ? a.cln_mean + (size_t)m * a.Kp : nullptr;
     const float* __restrict__ crs = PRO == 2 ? a.cln_rstd + (size_t)m * a.Kp : nullptr;
+    const __amdgpu_buffer_rsrc_t rsMu = make_rsrc(cmu, PRO == 2 ? rbytes : 0u), rsRs = make_rsrc(crs, PRO == 2 ? rbytes : 0u);
     if constexpr (PRO == 2) {
         alpha = a.pro_alpha[0];
         if (live) { g = a.pro_gamma[c]; b = a.pro_beta[c]; }
@@ -84,17 +110,32 @@ __global__ __launch_bounds__(NT) void dw_fwd_kernel(DwFwdArgs a) {
     const int halo = (P_ - 1) * a.dil;
     float s1 = 0.f, s2 = 0.f, amax = 0.f;
 
-    for (int k0 = 0; k0 < a.Kp; k0 += a.seg) {
-        const int kend = min(k0 + a.seg, a.Kp);
-        const int base = floor4(k0 - a.padl);
-        const int nfill = (kend - k0) + halo + 4;           // covers idx up to (kend-1-base-padl)+halo
-        for (int j = lane * 4; j < nfill; j += 256) {
+    // The image of a segment is filled in batches of NB chunks: all loads of a batch first, then the arithmetic and the LDS
+    // writes chunk by chunk.  The small patch is one batch.  On the float4 tap path the first batch of the next segment is
+    // issued before this segment's taps and stores, so its round trip runs beside them; on the scalar tap path (64-frame
+    // groups, 4 times as many tap iterations per segment) that measured 4 % slower alone (profiles/README.md), so there
+    // the batch is issued where it is used.
+    constexpr int NB = 4;
+    float4 rv[NB], rmu[NB], rrs[NB];
+    auto issue = [&](int base, int j0, int nfill) {        // chunk i of the batch: image floats j0 + CHUNK i + 4 lane ..+3
+#pragma unroll
+        for (int i = 0; i < NB; ++i) {
+            const int j = j0 + CHUNK * i + lane * 4;
+            const int off = row_voff(base + j, a.Kp, j < nfill);
+            rv[i] = buf_ld4(rsY, off);
+            if constexpr (PRO == 2) { rmu[i] = buf_ld4(rsMu, off); rrs[i] = buf_ld4(rsRs, off); }
+        }
+    };
+    auto consume = [&](int base, int j0, int nfill) {
+#pragma unroll
+        for (int i = 0; i < NB; ++i) {
+            const int j = j0 + CHUNK * i + lane * 4;
+            if (j >= nfill) continue;
             const int k = base + j;
-            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+            float4 v = rv[i];                               // 0 outside the row
             if (live && k >= 0 && k < a.Kp) {
-                v = ld4(y + k);
                 if constexpr (PRO == 2) {  // gamma ((prelu(x) - mean[k]) rstd[k]) + beta: the order of cln_fwd_v4_kernel
-                    const float4 mu = ld4(cmu + k), rs = ld4(crs + k);
+                    const float4 mu = rmu[i], rs = rrs[i];
                     v.x = k + 0 < a.K ? g * ((prelu_f(v.x, alpha) - mu.x) * rs.x) + b : 0.f;
                     v.y = k + 1 < a.K ? g * ((prelu_f(v.y, alpha) - mu.y) * rs.y) + b : 0.f;
                     v.z = k + 2 < a.K ? g * ((prelu_f(v.z, alpha) - mu.z) * rs.z) + b : 0.f;
@@ -115,7 +156,23 @@ __global__ __launch_bounds__(NT) void dw_fwd_kernel(DwFwdArgs a) {
             }
             *reinterpret_cast<float4*>(L + j) = v;
         }
+    };
+    auto nfill_of = [&](int k0) { return (min(k0 + a.seg, a.Kp) - k0) + halo + 4; };   // covers idx up to (kend-1-base-padl)+halo
+
+    constexpr bool AHEAD = VEC4;
+    if (AHEAD) issue(floor4(-a.padl), 0, nfill_of(0));
+    for (int k0 = 0; k0 < a.Kp; k0 += a.seg) {
+        const int kend = min(k0 + a.seg, a.Kp);
+        const int base = floor4(k0 - a.padl);
+        const int nfill = nfill_of(k0);
+        if (!AHEAD) issue(base, 0, nfill);
+        consume(base, 0, nfill);
+        for (int j0 = CHUNK * NB; j0 < nfill; j0 += CHUNK * NB) {
+            issue(base, j0, nfill);
+            consume(base, j0, nfill);
+        }
         __builtin_amdgcn_wave_barrier();   // the LDS patch is private to this wave; DS ops of one wave retire in order
+        if (AHEAD && k0 + a.seg < a.Kp) issue(floor4(k0 + a.seg - a.padl), 0, nfill_of(k0 + a.seg));
         if constexpr (VEC4) {
             // dilation and pad are multiples of 4: every tap of 4 consecutive frames is one aligned 16-byte LDS read
             // and the result leaves as a float4 (1 KiB per wave store)
@@ -208,6 +265,10 @@ struct DwBwdArgs {
     unsigned* amax_out;    // XM = 3: [M][CTN_AMAX_SLOTS] max |dY1[m]| (h3 arithmetic of the GEMMs that read it), optional
 };
 
+// registers of one batch of N chunks (the members a form does not load are never touched and cost nothing)
+template <int N_> struct DdRegs { static constexpr int N = N_; float4 n[N_], d[N_], f0[N_], f1[N_], f2[N_], f3[N_]; };
+template <int N_> struct XRegs { static constexpr int N = N_; float4 v[N_], mu[N_], rs[N_]; };
+
 template <int DDM, int XM, int BWD_BUF, bool VEC4, int PT>
 __global__ __launch_bounds__(NT) void dw_bwd_kernel(DwBwdArgs a) {
     static_assert((DDM == 0 && XM == 0) || (DDM == 1 && (XM == 1 || XM == 3)) || (DDM == 2 && (XM == 0 || XM == 2)), "supported forms");
@@ -217,7 +278,8 @@ __global__ __launch_bounds__(NT) void dw_bwd_kernel(DwBwdArgs a) {
     __shared__ __attribute__((aligned(16))) float bufA[ROWS][BWD_BUF];  // dd
     __shared__ __attribute__((aligned(16))) float bufB[ROWS][BWD_BUF];  // xh1 (FUSED) or x (PLAIN)
     __shared__ double red[NT / 64];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);      // (scalar: the row and its buffer resources are wave-uniform)
     const int hb = (a.H + ROWS - 1) / ROWS;
     const int m = blockIdx.x / hb;
     const int c = (blockIdx.x % hb) * ROWS + wave;
@@ -286,6 +348,11 @@ __global__ __launch_bounds__(NT) void dw_bwd_kernel(DwBwdArgs a) {
         al1 = a.a1[0];
         if (live) { g1 = a.g1[c]; b1 = a.b1[c]; }
     }
+    // buffer resources of the early loads: the wave's own rows, and the utterance's per-frame vectors of the cLN forms
+    const unsigned rbytes = live ? (unsigned)a.Kp * 4u : 0u;
+    const __amdgpu_buffer_rsrc_t rsN = make_rsrc(dn2, rbytes), rsD = make_rsrc(dz, DDM != 0 ? rbytes : 0u), rsY = make_rsrc(y1, rbytes);
+    const __amdgpu_buffer_rsrc_t rsF = make_rsrc(fcm, DDM == 2 && live ? (unsigned)a.Kp * 16u : 0u);
+    const __amdgpu_buffer_rsrc_t rsMu = make_rsrc(mu1f, XM == 2 ? rbytes : 0u), rsRs = make_rsrc(rs1f, XM == 2 ? rbytes : 0u);
     constexpr int NP = PT ? PT : MAXP;
     const int P_ = PT ? PT : a.P;
     float taps[NP];
@@ -294,14 +361,18 @@ __global__ __launch_bounds__(NT) void dw_bwd_kernel(DwBwdArgs a) {
     const int halo = (P_ - 1) * a.dil;
 
     // folded constants of the two norms: xh = x*(x>=0 ? rstd : alpha*rstd) - mean*rstd ;  da = rg2*dn2 - rc1 - xh*rc2
-    const float ar1 = al1 * rstd1, mr1 = mean1 * rstd1, ar2 = al2 * rstd2, mr2 = mean2 * rstd2;
-    const float rg2 = rstd2 * g2, rc1 = rstd2 * c1, rc2 = rstd2 * c2;
+    // (all wave-uniform, but computed by the vector ALU: uni() hands them to the scalar register file, which takes the float4
+    // gLN variants from 97 to 92 vector registers.  Those variants then sit at the scalar-register cap: 13 scalar values are
+    // spilled to lanes of one vector register, which the 92 include, and come back by v_readlane in the fill.  uni() on any
+    // subset of the constants gave 94-95 registers and 8-11 spills: profiles/dw_batched_resources.txt)
+    const float ar1 = uni(al1 * rstd1), mr1 = uni(mean1 * rstd1), ar2 = uni(al2 * rstd2), mr2 = uni(mean2 * rstd2);
+    const float rg2 = uni(rstd2 * g2), rc1 = uni(rstd2 * c1), rc2 = uni(rstd2 * c2);
     float dD[NP];
 #pragma unroll
     for (int j = 0; j < NP; ++j) dD[j] = 0.f;
     float dg2 = 0.f, db2 = 0.f, dal2 = 0.f, dg1 = 0.f, db1 = 0.f, t1 = 0.f, t2 = 0.f;
     float dal1 = 0.f, amax1 = 0.f;
-    const float rg1 = rstd1 * g1, rc1p = rstd1 * c1p, rc2p = rstd1 * c2p;       // APPLY: da1 = rstd1 (g1 dn1 - c1' - xh1 c2')
+    const float rg1 = uni(rstd1 * g1), rc1p = uni(rstd1 * c1p), rc2p = uni(rstd1 * c2p);       // APPLY: da1 = rstd1 (g1 dn1 - c1' - xh1 c2')
     // dh1 of one element: dn = dn1[k], xh = xhat1[k], h = h1[k] (its sign selects the PReLU branch); k < K
     auto apply1 = [&](float dn, float xh, float h) -> float {
         const float da = fmaf(-xh, rc2p, fmaf(rg1, dn, -rc1p));
@@ -320,13 +391,35 @@ __global__ __launch_bounds__(NT) void dw_bwd_kernel(DwBwdArgs a) {
         // dd image.  Frames of [k0, kend) belong to this segment: their parameter-gradient sums are taken here, and
         // when the segment lies inside [0, K) -- a uniform condition -- nothing in the loop is predicated.  The halo
         // frames on either side are transformed only (the neighbouring segment owns their sums).
-        auto fill_dd = [&](int kb, int ke, const bool own, const bool all_valid) {
-            for (int k = kb + lane * 4; k < ke; k += 256) {
-                float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+        //
+        // Loads come in batches of chunks (CHUNK frames, one float4 per lane and tensor): issue_dd / issue_x put a batch's loads
+        // in flight, use_dd / use_x then run the arithmetic and the LDS writes on it chunk by chunk, in the order of frames, so
+        // every per-lane sum adds its terms in the order it always did.  The gLN and plain forms take a segment in two batches
+        // (below); the cLN forms carry six vectors per dd chunk and go range by range, a chunk at a time.
+        auto issue_dd = [&](int kq, int ke, auto& r) {         // chunk i of the batch: frames kq + CHUNK i + 4 lane ..+3, below ke
+#pragma unroll
+            for (int i = 0; i < r.N; ++i) {
+                const int k = kq + CHUNK * i + lane * 4;
+                const int off = row_voff(k, a.Kp, k < ke);
+                r.n[i] = buf_ld4(rsN, off);
+                if constexpr (DDM != 0) r.d[i] = buf_ld4(rsD, off);
+                if constexpr (DDM == 2) {
+                    // (a.Kp * 4 bytes from one vector of fc to the next: an out-of-range frame must stay out of range)
+                    const int p4 = off == ROW_OOB ? 0 : a.Kp * 4;
+                    r.f0[i] = buf_ld4(rsF, off); r.f1[i] = buf_ld4(rsF, off + p4);
+                    r.f2[i] = buf_ld4(rsF, off + 2 * p4); r.f3[i] = buf_ld4(rsF, off + 3 * p4);
+                }
+            }
+        };
+        auto use_dd = [&](int kq, int ke, const auto& r, const bool own, const bool all_valid) {
+#pragma unroll
+            for (int i = 0; i < r.N; ++i) {
+                const int k = kq + CHUNK * i + lane * 4;
+                if (k >= ke) continue;
+                float4 v = r.n[i];                              // 0 outside the row
                 if (live && k >= 0 && k < a.Kp) {
-                    v = ld4(dn2 + k);
                     if constexpr (FUSED) {
-                        const float4 d = ld4(dz + k);
+                        const float4 d = r.d[i];
                         float vv[4] = {v.x, v.y, v.z, v.w};
                         const float dd_[4] = {d.x, d.y, d.z, d.w};
 #pragma unroll
@@ -344,8 +437,8 @@ __global__ __launch_bounds__(NT) void dw_bwd_kernel(DwBwdArgs a) {
                         v = make_float4(vv[0], vv[1], vv[2], vv[3]);
                     }
                     if constexpr (DDM == 2) {
-                        const float4 d = ld4(dz + k);
-                        const float4 f0 = ld4(fcm + k), f1 = ld4(fcm + a.Kp + k), f2 = ld4(fcm + 2 * a.Kp + k), f3 = ld4(fcm + 3 * a.Kp + k);
+                        const float4 d = r.d[i];
+                        const float4 f0 = r.f0[i], f1 = r.f1[i], f2 = r.f2[i], f3 = r.f3[i];
                         float vv[4] = {v.x, v.y, v.z, v.w};
                         const float dd_[4] = {d.x, d.y, d.z, d.w};
                         const float q0[4] = {f0.x, f0.y, f0.z, f0.w}, q1[4] = {f1.x, f1.y, f1.z, f1.w};
@@ -368,19 +461,25 @@ __global__ __launch_bounds__(NT) void dw_bwd_kernel(DwBwdArgs a) {
                 *reinterpret_cast<float4*>(LA + (k - baseA)) = v;
             }
         };
-        const int endA = baseA + ((nfill + 3) & ~3);
-        if (baseA < k0) fill_dd(baseA, k0, false, false);
-        if (kend <= a.K) fill_dd(max(k0, baseA), kend, true, true);
-        else fill_dd(max(k0, baseA), kend, true, false);
-        if (endA > kend) fill_dd(kend, endA, false, false);
-        for (int j = lane * 4; j < nfill; j += 256) {
-            {
+        auto issue_x = [&](int j0, auto& r) {                  // chunk i of the batch: image floats j0 + CHUNK i + 4 lane ..+3
+#pragma unroll
+            for (int i = 0; i < r.N; ++i) {
+                const int j = j0 + CHUNK * i + lane * 4;
+                const int off = row_voff(baseB + j, a.Kp, j < nfill);
+                r.v[i] = buf_ld4(rsY, off);
+                if constexpr (XM == 2) { r.mu[i] = buf_ld4(rsMu, off); r.rs[i] = buf_ld4(rsRs, off); }
+            }
+        };
+        auto use_x = [&](int j0, const auto& r) {
+#pragma unroll
+            for (int i = 0; i < r.N; ++i) {
+                const int j = j0 + CHUNK * i + lane * 4;
+                if (j >= nfill) continue;
                 const int k = baseB + j;
-                float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+                float4 v = r.v[i];                              // 0 outside the row
                 if (live && k >= 0 && k < a.Kp) {
-                    v = ld4(y1 + k);
                     if constexpr (XM == 2) {
-                        const float4 mu = ld4(mu1f + k), rs = ld4(rs1f + k);
+                        const float4 mu = r.mu[i], rs = r.rs[i];
                         v.x = (prelu_f(v.x, al1) - mu.x) * rs.x;
                         v.y = (prelu_f(v.y, al1) - mu.y) * rs.y;
                         v.z = (prelu_f(v.z, al1) - mu.z) * rs.z;
@@ -395,6 +494,51 @@ __global__ __launch_bounds__(NT) void dw_bwd_kernel(DwBwdArgs a) {
                 }
                 *reinterpret_cast<float4*>(LB + j) = v;
             }
+        };
+        // the batches of a range past its first one, each issued and used in turn
+        auto rest_dd = [&](int kb, int ke, auto& r, const bool own, const bool all_valid) {
+            for (int kq = kb + CHUNK * r.N; kq < ke; kq += CHUNK * r.N) {
+                issue_dd(kq, ke, r);
+                use_dd(kq, ke, r, own, all_valid);
+            }
+        };
+        auto rest_x = [&](auto& r) {
+            for (int j0 = CHUNK * r.N; j0 < nfill; j0 += CHUNK * r.N) {
+                issue_x(j0, r);
+                use_x(j0, r);
+            }
+        };
+        const int endA = baseA + ((nfill + 3) & ~3);
+        const int kown = max(k0, baseA);
+        const bool all_valid = kend <= a.K;
+        if constexpr (DDM == 2) {
+            DdRegs<1> r;
+            XRegs<XM == 2 ? 2 : 4> rx;
+            issue_dd(baseA, k0, r);     use_dd(baseA, k0, r, false, false);   rest_dd(baseA, k0, r, false, false);
+            issue_dd(kown, kend, r);
+            if (all_valid) { use_dd(kown, kend, r, true, true);   rest_dd(kown, kend, r, true, true); }
+            else           { use_dd(kown, kend, r, true, false);  rest_dd(kown, kend, r, true, false); }
+            issue_dd(kend, endA, r);    use_dd(kend, endA, r, false, false);  rest_dd(kend, endA, r, false, false);
+            issue_x(0, rx);             use_x(0, rx);                         rest_x(rx);
+        } else {
+            // Two round trips per small-patch segment: the segment's own frames (at most 704 = 3 chunks of two tensors), then
+            // both halos (a chunk each) together with the x image (at most 764 floats = 3 chunks).  All of it in one batch
+            // would be 13 float4 per lane and takes 127 registers; two waves per SIMD beside a weight-gradient workgroup
+            // need 92 or fewer (profiles/dw_batched_resources.txt).  The scalar tap path needs more registers for its taps
+            // and batches 2 chunks.  Larger patches run further batches of the same size (rest_dd / rest_x).
+            constexpr int NBO = VEC4 ? 3 : 2;
+            DdRegs<NBO> ro;
+            issue_dd(kown, kend, ro);
+            if (all_valid) { use_dd(kown, kend, ro, true, true);   rest_dd(kown, kend, ro, true, true); }
+            else           { use_dd(kown, kend, ro, true, false);  rest_dd(kown, kend, ro, true, false); }
+            DdRegs<1> rl, rr;
+            XRegs<NBO> rx;
+            issue_dd(baseA, k0, rl);
+            issue_dd(kend, endA, rr);
+            issue_x(0, rx);
+            use_dd(baseA, k0, rl, false, false);    rest_dd(baseA, k0, rl, false, false);
+            use_dd(kend, endA, rr, false, false);   rest_dd(kend, endA, rr, false, false);
+            use_x(0, rx);                           rest_x(rx);
         }
         __builtin_amdgcn_wave_barrier();   // wave-private LDS patches
         if constexpr (VEC4) {
@@ -562,7 +706,8 @@ __global__ __launch_bounds__(NT) void gln_prelu_bwd_kernel(const float* __restri
                                                            int nparts, float* __restrict__ dalpha_part,
                                                            unsigned* __restrict__ amax_out) {
     __shared__ double red[NT / 64];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);      // (scalar: the row and its buffer resources are wave-uniform)
     const int hb = (H + ROWS - 1) / ROWS;
     const int m = blockIdx.x / hb;
     const int c = (blockIdx.x % hb) * ROWS + wave;
@@ -578,24 +723,49 @@ __global__ __launch_bounds__(NT) void gln_prelu_bwd_kernel(const float* __restri
     const float c1 = (float)(S1 / n), c2 = (float)(S2 / n);
     const float mean = ms[2 * m], rstd = ms[2 * m + 1], al = alpha_p[0], g = live ? gamma[c] : 0.f;
     const float ar = al * rstd, mr = mean * rstd, rg = rstd * g, rc1 = rstd * c1, rc2 = rstd * c2;
-    const size_t row = ((size_t)m * H + c) * Kp;
+    const size_t row = ((size_t)m * H + (live ? c : 0)) * Kp;
+    const unsigned rbytes = live ? (unsigned)Kp * 4u : 0u;
+    const __amdgpu_buffer_rsrc_t rsN = make_rsrc(dN + row, rbytes), rsY = make_rsrc(Y + row, rbytes);
     float dal = 0.f, amax = 0.f;
-    for (int k = lane * 4; live && k < Kp; k += 256) {
-        const float4 dn = ld4(dN + row + k);
-        const float4 y = ld4(Y + row + k);
-        const float dv[4] = {dn.x, dn.y, dn.z, dn.w};
-        const float yv[4] = {y.x, y.y, y.z, y.w};
-        float o[4];
+    // The row goes in batches of NB chunks through a ring of NB register slots: the 2 NB loads of the first batch are issued
+    // before the first use, and a slot is reloaded for the next batch as soon as its chunk has been stored, so 2 NB loads
+    // stay in flight.  Arithmetic and stores run chunk by chunk in the order of frames (dal and amax take their terms as
+    // before).  dY may be dN: a lane only ever writes frames that it has read, and reads every frame before it writes it.
+    constexpr int NB = 4;
+    float4 rn[NB], ry[NB];
+    auto issue = [&](int i, int k) {
+        const int off = row_voff(k, Kp, true);
+        rn[i] = buf_ld4(rsN, off);
+        ry[i] = buf_ld4(rsY, off);
+    };
+    auto batch = [&](int kq, const bool full) {             // full: all NB chunks lie inside the row (uniform)
 #pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const float xh = fmaf(yv[e], yv[e] >= 0.f ? rstd : ar, -mr);
-            const float da = fmaf(-xh, rc2, fmaf(rg, dv[e], -rc1));
-            const bool valid = (k + e) < K;
-            if (valid && yv[e] < 0.f) dal += da * yv[e];
-            o[e] = valid ? (yv[e] >= 0.f ? da : al * da) : 0.f;
+        for (int i = 0; i < NB; ++i) {
+            const int k = kq + CHUNK * i + lane * 4;
+            if (full || k < Kp) {
+                const float dv[4] = {rn[i].x, rn[i].y, rn[i].z, rn[i].w};
+                const float yv[4] = {ry[i].x, ry[i].y, ry[i].z, ry[i].w};
+                float o[4];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const float xh = fmaf(yv[e], yv[e] >= 0.f ? rstd : ar, -mr);
+                    const float da = fmaf(-xh, rc2, fmaf(rg, dv[e], -rc1));
+                    const bool valid = (k + e) < K;
+                    if (valid && yv[e] < 0.f) dal += da * yv[e];
+                    o[e] = valid ? (yv[e] >= 0.f ? da : al * da) : 0.f;
+                }
+                amax = fmaxf(fmaxf(amax, fmaxf(fabsf(o[0]), fabsf(o[1]))), fmaxf(fabsf(o[2]), fabsf(o[3])));
+                *reinterpret_cast<float4*>(dY + row + k) = make_float4(o[0], o[1], o[2], o[3]);
+            }
+            if (full) issue(i, k + CHUNK * NB);              // (past the row: offset out of range, reads 0, never used)
         }
-        amax = fmaxf(fmaxf(amax, fmaxf(fabsf(o[0]), fabsf(o[1]))), fmaxf(fabsf(o[2]), fabsf(o[3])));
-        *reinterpret_cast<float4*>(dY + row + k) = make_float4(o[0], o[1], o[2], o[3]);
+    };
+    if (live) {
+#pragma unroll
+        for (int i = 0; i < NB; ++i) issue(i, CHUNK * i + lane * 4);
+        int kq = 0;
+        for (; kq + CHUNK * NB <= Kp; kq += CHUNK * NB) batch(kq, true);
+        if (kq < Kp) batch(kq, false);                      // the ragged tail: chunks past the row hold 0 and store nothing
     }
     dal = wave_sum(dal);
     if (live && lane == 0) dalpha_part[(size_t)m * H + c] = dal;
