@@ -476,8 +476,6 @@ ClnBwdWs cln_bwd_ws(int M, int B, int H, int Kp, int P, int nblocks) {
 }
 }  // namespace
 
-extern "C" int ctn_cln_fuse(void);       // csrc/ctn_tcn.hip
-
 extern "C" {
 
 // forward weight-operand form of ctn_pw_gemm_cln after prepare_weights(forward): 3 h3 pieces, 2 b6 pieces, 1 the [I, O] fp32 copy

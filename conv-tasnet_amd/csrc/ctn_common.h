@@ -54,6 +54,21 @@ int ctn_pw_wgrad_h3_chained(const float* dOut, const float* X, float* dW, int M,
                             void* workspace, size_t workspace_bytes, void* stream, CtnWgradChain* chain);
 int ctn_wgrad_chain_flush(CtnWgradChain* chain, void* stream);
 
+// ---- library-internal names that cross translation units: declared here only, each with the linkage of its definition ----
+extern "C" {
+extern int g_ctn_cln_fr;        // csrc/ctn_cln.hip: frames per workgroup of the channel-wise LayerNorm v4 kernels
+extern int g_ctn_cln_lean;      // csrc/ctn_cln.hip: the specialised cLN backward kernel for the stacks' form
+extern int g_ctn_cln_fuse;      // csrc/ctn_cln.hip: cLN stacks with the norms fused into their neighbours; read it through ctn_cln_fuse()
+extern int g_ctn_gln_fuse;      // csrc/ctn_dw.hip: gLN stacks without the gLN-1' / PReLU-1' pass; read it through ctn_gln_fuse()
+int ctn_cln_fuse(void);
+int ctn_gln_fuse(void);
+int ctn_absmax_rows(const float* x, int M, long long n, unsigned* amax, void* stream);      // csrc/ctn_gemm.hip (the cLN fallbacks' h3 maxima)
+}
+extern int g_ctn_bwd_events;    // csrc/ctn_block.hip: cross-stream forks per block of the composite backward passes
+#ifdef CTN_EXP_SKIP
+extern int g_ctn_exp_skip;      // csrc/ctn_block.hip: timing-experiment switch of lab builds
+#endif
+
 #ifdef __HIPCC__
 // ---- wave64 / block reductions ---------------------------------------------
 __device__ __forceinline__ float wave_sum(float v) {

@@ -428,14 +428,6 @@ __global__ __launch_bounds__(NT) void pw_wgrad4_kernel(WgArgs a) {
 #include "ctn_gemm_ws.h"            // the wave-specialised h3 forward / input-gradient kernel
 
 int g_ctn_tile_override = -2;
-extern int g_ctn_cln_lean;
-extern int g_ctn_bwd_events;                // csrc/ctn_block.hip: cross-stream forks per block of the composite backward passes
-#ifdef CTN_EXP_SKIP
-extern int g_ctn_exp_skip;                  // csrc/ctn_block.hip: timing-experiment switch of lab builds
-#endif
-extern int g_ctn_gln_fuse;                  // csrc/ctn_tcn.hip: gLN stacks without the gLN-1' / PReLU-1' pass
-extern int g_ctn_cln_fuse;                  // csrc/ctn_tcn.hip: cLN stacks with the second norm's backward fused into its neighbours
-extern int g_ctn_cln_fr;                    // csrc/ctn_tcn.hip: frames per workgroup of the channel-wise LayerNorm backward kernel
 
 // GEMM arithmetic (ctn_gemm_b3.h): 3 = "h3" (default: the composite stacks run their GEMMs on two fp16 pieces per operand under
 // tracked power-of-two scales, three f16 MFMAs -- the ctn_*_h3 entry points; every other GEMM as b6), 2 = "b6" (three bf16 pieces

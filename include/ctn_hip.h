@@ -197,7 +197,9 @@ int ctn_dw_fwd(const float* Y, float* Z, const float* D, int M, int H, int K, in
  *        pc [F, M, H] per-(utterance, channel) partials, F = ctn_dw_bwd_rows(P, fused):
  *        rows 0..P-1 dD taps; fused adds P: dgamma2, P+1: dbeta2, P+2: dgamma1, P+3: dbeta1, P+4: dalpha2.
  * fused = 0: dN2 = dZ, Y1 = the forward input; outputs dN1 = dY and pc rows 0..P-1.
- * (fused = 2 is the channel-wise LayerNorm form behind ctn_dw_bwd_cln below: call that.) */
+ * fused takes 0 and 1 only.  The other two forms have entry points of their own, and this one refuses their numbers with
+ * CTN_ERR_ARG and a message that names the one to call: 2 = the channel-wise LayerNorm form, ctn_dw_bwd_cln; 3 = the gLN form
+ * with the first norm's backward applied, ctn_dw_bwd_gln2 (both below).  ctn_dw_bwd_rows still answers for 0..3. */
 int ctn_dw_bwd(const float* dN2, const float* Dz, const float* Y1, float* dN1, const float* D,
                int M, int H, int K, int Kp, int P, int dilation, int causal, int fused,
                const float* g1, const float* b1, const float* a1, const float* ms1,

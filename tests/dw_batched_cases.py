@@ -1,5 +1,5 @@
 """What tests/test_gpu_depthwise_batched.py and tests/test_dw_batched_oracle_cpu.py share: the cases at which a batched or
-pipelined load of dw_fwd_kernel / dw_bwd_kernel / gln_prelu_bwd_kernel (csrc/ctn_tcn.hip) can go wrong, the guard-row layout
+pipelined load of dw_fwd_kernel / dw_bwd_kernel / gln_prelu_bwd_kernel (csrc/ctn_dw.hip) can go wrong, the guard-row layout
 of the operands, a model of a kernel that reads past its row, and the fp64 definition of ctn_gln_prelu_bwd.
 
 The kernels fill a segment's LDS image in batches of 256-frame chunks (one float4 per lane), all loads of a batch before the

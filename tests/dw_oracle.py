@@ -1,4 +1,4 @@
-"""Closed forms of the depthwise-conv kernels of csrc/ctn_tcn.hip (dw_fwd_kernel / dw_bwd_kernel), in plain torch on the CPU.
+"""Closed forms of the depthwise-conv kernels of csrc/ctn_dw.hip (dw_fwd_kernel / dw_bwd_kernel), in plain torch on the CPU.
 
 The functions take what the C entry points take (include/ctn_hip.h: ctn_dw_fwd, ctn_dw_fwd_cln, ctn_dw_bwd, ctn_dw_bwd_gln2,
 ctn_dw_bwd_cln), already rounded to fp32 where the kernel receives fp32, without the K..Kp pad frames, and evaluate the
@@ -22,7 +22,7 @@ import torch.nn.functional as F
 F64 = torch.float64
 EPS = 1e-8                    # CTN_EPS
 
-# ---- mirror of csrc/ctn_tcn.hip (test_dw_oracle_cpu.py::test_constants_match_the_source reads the source) ------------------
+# ---- mirror of csrc/ctn_dw.hip (test_dw_oracle_cpu.py::test_constants_match_the_source reads the source) ------------------
 MAXP = 8
 FWD_BUF_S, FWD_BUF_L = 1024, 3584
 BWD_BUF_S, BWD_BUF_M, BWD_BUF_L = 768, 1280, 1792

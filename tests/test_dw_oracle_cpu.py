@@ -1,6 +1,6 @@
 """tests/dw_oracle.py itself, on the CPU: the fp64 closed forms of the depthwise kernels against autograd, the limits of
 tests/test_gpu_depthwise.py against what fp32 arithmetic can reach and against four deliberately wrong models, and the mirror of
-the kernels' patch constants against csrc/ctn_tcn.hip."""
+the kernels' patch constants against csrc/ctn_dw.hip."""
 import os
 import re
 
@@ -12,7 +12,7 @@ from conftest import ROOT
 from oracle import ctn_oracle as O
 
 F64 = torch.float64
-SOURCE = os.path.join(ROOT, "conv-tasnet_amd", "csrc", "ctn_tcn.hip")
+SOURCE = os.path.join(ROOT, "conv-tasnet_amd", "csrc", "ctn_dw.hip")
 
 
 # ---- the constants mirror ------------------------------------------------------------------------------------------------------
@@ -22,13 +22,16 @@ def test_constants_match_the_source():
         m = re.search(r"constexpr int [^;]*\b%s = (\d+)[,;]" % name, src)
         assert m, name
         assert int(m.group(1)) == getattr(DO, name), name
-    # the patch is chosen from the halo: forward small <= 192 (both forward entry points), backward small <= 128, medium <= 256
-    t = [str(v) for v in (DO.FWD_SMALL_HALO,) * 3 + (DO.BWD_SMALL_HALO, DO.BWD_MEDIUM_HALO)]
+    # the patch is chosen from the halo, in the one geometry helper that every depthwise entry point goes through:
+    # forward small <= 192, backward small <= 128, medium <= 256
+    t = [str(v) for v in (DO.FWD_SMALL_HALO, DO.BWD_SMALL_HALO, DO.BWD_MEDIUM_HALO)]
     assert re.findall(r"halo <= (\d+)", src) == t       # (no further threshold that the mirror does not know)
-    assert "const bool small = halo <= %s, medium = !small && halo <= %s;" % (t[3], t[4]) in src
-    # seg = ((BUF - halo - 8) / 64) * 64
-    assert src.count("const int seg = (((small ? FWD_BUF_S : FWD_BUF_L) - halo - 8) / 64) * 64;") == 2
-    assert src.count("const int seg = (((small ? BWD_BUF_S : (medium ? BWD_BUF_M : BWD_BUF_L)) - halo - 8) / 64) * 64;") == 1
+    assert "const bool small = halo <= %s;" % t[0] in src
+    assert "const bool small = halo <= %s, medium = !small && halo <= %s;" % (t[1], t[2]) in src
+    # seg = ((BUF - halo - 8) / 64) * 64, once per direction and nowhere else
+    assert len(re.findall(r"(?<![.\w])seg = ", src)) == 2 and len(re.findall(r"\bdw_geometry\(\"ctn_dw_\w+\", (?:true|false),", src)) == 5
+    assert src.count("seg = (((small ? FWD_BUF_S : FWD_BUF_L) - halo - 8) / 64) * 64;") == 1
+    assert src.count("seg = (((small ? BWD_BUF_S : (medium ? BWD_BUF_M : BWD_BUF_L)) - halo - 8) / 64) * 64;") == 1
     assert src.count("const bool vec4 = (a.dil % 4 == 0) && (a.padl % 4 == 0);") == 2
     assert DO.seg_of(1024, 2) == 960 and DO.seg_of(1792, 512) == 1216
 

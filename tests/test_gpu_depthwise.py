@@ -1,4 +1,4 @@
-"""Every variant of dw_fwd_kernel / dw_bwd_kernel (csrc/ctn_tcn.hip) through the C ABI against tests/dw_oracle.py in fp64, at the
+"""Every variant of dw_fwd_kernel / dw_bwd_kernel (csrc/ctn_dw.hip) through the C ABI against tests/dw_oracle.py in fp64, at the
 kernels' seams.
 
 The launchers pick a variant from halo = (P-1) dilation (the LDS patch: forward S / L, backward S / M / L), from the alignment

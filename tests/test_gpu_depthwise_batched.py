@@ -1,4 +1,4 @@
-"""The batched and early loads of dw_fwd_kernel, dw_bwd_kernel and gln_prelu_bwd_kernel (csrc/ctn_tcn.hip) through the C ABI
+"""The batched and early loads of dw_fwd_kernel, dw_bwd_kernel and gln_prelu_bwd_kernel (csrc/ctn_dw.hip) through the C ABI
 against tests/dw_oracle.py in fp64, at the frame counts of tests/dw_batched_cases.py and between guard rows.
 
 Every tensor and per-frame operand is rows 1..n of a buffer with one more row in front and one behind.  The guard rows hold NaN

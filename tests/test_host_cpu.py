@@ -44,6 +44,36 @@ def test_bad_arguments_return_error_codes_not_crashes():
         ctn.lib.call("ctn_im2col", 0, 0, 1, 100, 20, 20, 9, 64, 0)
 
 
+def _dw_call(name, **kw):
+    """A depthwise entry point on fake 16-byte-aligned pointers with complete, valid arguments except for `kw` (by the header's
+    parameter names): such a call must be refused before any HIP call.  -> (status, message)"""
+    dflt = {"M": 1, "H": 4, "K": 8, "Kp": 8, "P": 3, "dilation": 1, "causal": 0, "fused": 1, "sums2_nparts": 1, "stream": 0}
+    names = ctn.lib.protos[name][2]
+    assert set(kw) <= set(names), (name, kw)
+    rc = getattr(ctn.lib.load(), name)(*[kw[nm] if nm in kw else dflt.get(nm, 16) for nm in names])
+    return rc, ctn.lib.ctn_last_error().decode()
+
+
+@pytest.mark.parametrize("name,kw", [
+    ("ctn_dw_fwd_cln", {"P": 99}),
+    ("ctn_dw_bwd_gln2", {"P": 99}),
+    ("ctn_dw_bwd_gln2", {"ms1": 0}),
+    ("ctn_dw_bwd_cln", {"P": 2, "dilation": 3, "causal": 0}),
+    ("ctn_dw_bwd_cln", {"mean1": 0}),
+    ("ctn_dw_bwd", {"fused": 4}),
+    ("ctn_dw_bwd", {"fused": -1}),
+])
+def test_depthwise_entry_points_name_themselves_when_they_refuse(name, kw):
+    rc, msg = _dw_call(name, **kw)
+    assert rc == -1 and msg.startswith(name + ":"), (rc, msg)
+
+
+@pytest.mark.parametrize("fused,other", [(2, "ctn_dw_bwd_cln"), (3, "ctn_dw_bwd_gln2")])
+def test_dw_bwd_refuses_the_forms_that_have_their_own_entry_point(fused, other):
+    rc, msg = _dw_call("ctn_dw_bwd", fused=fused)
+    assert rc == -1 and msg.startswith("ctn_dw_bwd:") and other in msg, (rc, msg)
+
+
 @pytest.mark.parametrize("tag,nt,causal", [("gLN", "gLN", False), ("cLN", "cLN", True)])
 def test_constructor_is_bitwise_the_reference_constructor(tag, nt, causal):
     g = load_golden("init_seed11_" + tag)
