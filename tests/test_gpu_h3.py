@@ -267,7 +267,8 @@ def test_h3_producers_track_exact_maxima():
     ctn.lib.call("ctn_gln_prelu_bwd", dn.data_ptr(), y.data_ptr(), dY.data_ptr(), M, H, K, Kp, gam.data_ptr(), a.data_ptr(), ms.data_ptr(),
                  s1p.data_ptr(), H, dap.data_ptr(), am.data_ptr(), ops._stream())
     assert torch.equal(amax_f(am), dY.abs().amax((1, 2)))
-    # channel-wise LayerNorm (the causal config's norm): forward output and input gradient, fast (v4) and fallback kernels
+    # channel-wise LayerNorm (the causal config's norm): forward output and input gradient, the v4 kernels at CPT 4 and CPT 1 (Kp = 704
+    # and 256 are multiples of 32: no fallback here; tests/test_gpu_norm_forms.py tracks the maxima of the fallback kernels)
     for Ch, Kc in ((H, 700), (36, 203)):
         Kpc = ops.padded_frames(Kc)
         yc = pad(torch.randn(M, Ch, Kc, generator=g(7)) * torch.tensor([1e-6, 1.0, 3e4]).view(M, 1, 1), Kpc).to(DEV)

@@ -866,8 +866,9 @@ def test_pw_wgrad_every_plan(fp32_only, blocks):
 @pytest.mark.parametrize("Ch,K", [(8, 50), (40, 333), (300, 95), (520, 70), (1100, 40)])
 @pytest.mark.parametrize("with_prelu", [True, False])
 def test_cln_kernels_every_width(Ch, K, with_prelu):
-    """Channel-wise LayerNorm (+PReLU) forward / backward across the register-resident configurations (2..32 channels
-    per thread, 512- and 1024-thread workgroups) and the generic fallback for very wide layers, against fp64 torch."""
+    """Channel-wise LayerNorm (+PReLU) forward / backward against fp64 torch at five widths.  Kp is a multiple of 64 here, so the
+    widths 8, 40 and 300 run the v4 kernels (CPT 1, 1 and 8); 520 runs cln_fwd_reg_kernel<32, 32>, 1100 the generic forward, and both
+    the generic backward.  tests/test_gpu_norm_forms.py reaches the register-resident fallbacks."""
     M = 2
     Kp = ops.padded_frames(K)
     y = (torch.randn(M, Ch, K, generator=g(21)) * 1.5 + 0.2).double().requires_grad_(True)
