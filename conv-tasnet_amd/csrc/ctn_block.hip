@@ -116,12 +116,32 @@ inline bool use_h3(int B, int H) { return ctn_gemm_arith() == 3 && B >= 64 && H 
 // rows, slot 1 for the one with B output rows.  fwd: (w1 -> H rows, w2 -> B rows) as stored; bwd: (w2 -> H rows, w1 -> B rows)
 // transposed.  tw_h / tw_b receive the trans_w code of ctn_pw_gemm for the prepared operand (2 pieces, 1 fp32 [I, O] copy;
 // backward without pieces uses the stored matrices: no copy, code 1).
-// h3: pieces from ctn_split_h3_batch (code 3), and gb [nblocks][2] receives {max |gamma2|, max |beta2|} of every block.
+// h3: pieces as from ctn_split_h3_batch (code 3), and gb [nblocks][2] receives {max |gamma2|, max |beta2|} of every block, all from
+// the one launch of ctn_prep_h3_fused.
 int prepare_weights(const void* const* params, int nblocks, int B, int H, bool backward, char* region, size_t slot,
                     int* tw_h, int* tw_b, bool h3, float* gb, void* stream) {
     std::vector<const void*> src(nblocks);
     std::vector<void*> dst(nblocks);
     int rc;
+    if (h3) {       // both operands of every block and the norm-parameter maxima: one launch ahead of the chain
+        std::vector<const void*> srcb(nblocks), gsrc;
+        std::vector<void*> dstb(nblocks), gdst;
+        for (int i = 0; i < nblocks; ++i) {
+            const void* const* p = (const void* const*)(params + (size_t)i * NPARAM);
+            src[i] = p[backward ? P_W2 : P_W1];         // the H-row GEMM
+            srcb[i] = p[backward ? P_W1 : P_W2];        // the B-row GEMM
+            dst[i] = region + ((size_t)2 * i) * slot;
+            dstb[i] = region + ((size_t)2 * i + 1) * slot;
+            if (gb != nullptr) {        // (the cLN stacks have no operand prologue)
+                gsrc.push_back(p[P_G2]); gsrc.push_back(p[P_B2]);
+                gdst.push_back(gb + 2 * i); gdst.push_back(gb + 2 * i + 1);
+            }
+        }
+        if ((rc = PROBED(F_PREP, stream, ctn_prep_h3_fused(src.data(), dst.data(), H, B, srcb.data(), dstb.data(), B, H, nblocks, backward ? 1 : 0,
+                                                           gb != nullptr ? gsrc.data() : nullptr, gb != nullptr ? gdst.data() : nullptr, H, stream)))) return rc;
+        *tw_h = *tw_b = 3;
+        return CTN_OK;
+    }
     for (int half = 0; half < 2; ++half) {              // 0: the H-row GEMM, 1: the B-row GEMM
         const int R = half == 0 ? H : B, Cn = half == 0 ? B : H;
         const int pidx = (half == 0) != backward ? P_W1 : P_W2;      // fwd: H rows <- w1, B rows <- w2; bwd: H rows <- w2, B rows <- w1
@@ -130,10 +150,7 @@ int prepare_weights(const void* const* params, int nblocks, int B, int H, bool b
             dst[i] = region + ((size_t)2 * i + half) * slot;
         }
         int* const tw = half == 0 ? tw_h : tw_b;
-        if (h3) {
-            if ((rc = PROBED(F_PREP, stream, ctn_split_h3_batch(src.data(), dst.data(), nblocks, R, Cn, backward ? 1 : 0, stream)))) return rc;
-            *tw = 3;
-        } else if (pieces(R)) {
+        if (pieces(R)) {
             if ((rc = PROBED(F_PREP, stream, ctn_split_b3_batch(src.data(), dst.data(), nblocks, R, Cn, backward ? 1 : 0, stream)))) return rc;
             *tw = 2;
         } else if (!backward) {
@@ -142,17 +159,6 @@ int prepare_weights(const void* const* params, int nblocks, int B, int H, bool b
         } else {
             *tw = -1;       // use the stored matrix (trans_w = 1)
         }
-    }
-    if (h3 && gb != nullptr) {      // (the cLN stacks have no operand prologue)
-        std::vector<const void*> gsrc(2 * (size_t)nblocks);
-        std::vector<void*> gdst(2 * (size_t)nblocks);
-        for (int i = 0; i < nblocks; ++i) {
-            gsrc[2 * i] = ((const void* const*)(params + (size_t)i * NPARAM))[P_G2];
-            gsrc[2 * i + 1] = ((const void* const*)(params + (size_t)i * NPARAM))[P_B2];
-            gdst[2 * i] = gb + 2 * i;
-            gdst[2 * i + 1] = gb + 2 * i + 1;
-        }
-        if ((rc = PROBED(F_PREP, stream, ctn_absmax_batch(gsrc.data(), gdst.data(), 2 * nblocks, H, stream)))) return rc;
     }
     return CTN_OK;
 }

@@ -516,7 +516,14 @@ __global__ __launch_bounds__(NT) void cln_bwd_finalize_kernel(const float* __res
     if (c < Ch) {
         const float* __restrict__ p = pc + (size_t)f * rows * Ch + c;
         int r = wave;
-        for (; r + 28 < rows; r += 32) {                 // eight independent loads in flight per lane
+        for (; r + 252 < rows; r += 256) {               // 64 independent loads in flight per lane: the kernel is load latency, a
+            float v[64];                                 // few MB over nine workgroups; the adds keep their row order
+#pragma unroll
+            for (int j = 0; j < 64; ++j) v[j] = p[(size_t)(r + 4 * j) * Ch];
+#pragma unroll
+            for (int j = 0; j < 64; ++j) s += v[j];
+        }
+        for (; r + 28 < rows; r += 32) {                 // eight
             float v[8];
 #pragma unroll
             for (int j = 0; j < 8; ++j) v[j] = p[(size_t)(r + 4 * j) * Ch];

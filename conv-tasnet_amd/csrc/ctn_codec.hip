@@ -198,6 +198,98 @@ __global__ __launch_bounds__(NT) void mask_apply_bwd_kernel(const float* __restr
     }
 }
 
+// The same for C = 2 and 3 (the training configs), closer to its bytes: a thread takes TWO element groups per trip and issues all
+// 2 (2C + 1) 16-byte loads before the first use; the grid is sized for one trip where that fits.  Per element the arithmetic and
+// the order over c are those of mask_apply_bwd_kernel: bitwise its results.  dscore may alias dsw: a thread reads its groups
+// before it writes them.
+template <int C>
+struct MaskGroup {
+    float4 w, s[C], g[C];
+};
+template <int C>
+__device__ __forceinline__ void mask_group_load(MaskGroup<C>& q, const float* __restrict__ dsw, const float* __restrict__ score,
+                                                const float* __restrict__ w, long long e, long long NK) {
+    const size_t base = (size_t)(e / NK) * C * NK + (size_t)(e % NK);
+    q.w = ld4(w + e);
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+        q.s[c] = ld4(score + base + (size_t)c * NK);
+        q.g[c] = ld4(dsw + base + (size_t)c * NK);
+    }
+}
+template <int C>
+__device__ __forceinline__ void mask_group_bwd(const MaskGroup<C>& q, float* __restrict__ dscore, float* __restrict__ dw, long long e,
+                                               long long NK, int mode) {
+    const size_t base = (size_t)(e / NK) * C * NK + (size_t)(e % NK);
+    const float ww[4] = {q.w.x, q.w.y, q.w.z, q.w.w};
+    float acc[4] = {0.f, 0.f, 0.f, 0.f};
+    if (mode == 0) {
+#pragma unroll
+        for (int c = 0; c < C; ++c) {
+            const float sv[4] = {q.s[c].x, q.s[c].y, q.s[c].z, q.s[c].w}, gv[4] = {q.g[c].x, q.g[c].y, q.g[c].z, q.g[c].w};
+            float o[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                acc[k] += gv[k] * fmaxf(sv[k], 0.f);
+                o[k] = sv[k] > 0.f ? gv[k] * ww[k] : 0.f;
+            }
+            *reinterpret_cast<float4*>(dscore + base + (size_t)c * NK) = make_float4(o[0], o[1], o[2], o[3]);
+        }
+    } else if (mode == 2) {
+#pragma unroll
+        for (int c = 0; c < C; ++c) {
+            const float4 s = q.s[c], g = q.g[c];
+            acc[0] += g.x * s.x; acc[1] += g.y * s.y; acc[2] += g.z * s.z; acc[3] += g.w * s.w;
+            *reinterpret_cast<float4*>(dscore + base + (size_t)c * NK) = make_float4(g.x * ww[0], g.y * ww[1], g.z * ww[2], g.w * ww[3]);
+        }
+    } else {
+        float pr[C][4], gm[C][4];
+        float mx[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY}, den[4] = {0.f, 0.f, 0.f, 0.f}, dotv[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int c = 0; c < C; ++c) {
+            pr[c][0] = q.s[c].x; pr[c][1] = q.s[c].y; pr[c][2] = q.s[c].z; pr[c][3] = q.s[c].w;
+            gm[c][0] = q.g[c].x; gm[c][1] = q.g[c].y; gm[c][2] = q.g[c].z; gm[c][3] = q.g[c].w;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) mx[k] = fmaxf(mx[k], pr[c][k]);
+        }
+#pragma unroll
+        for (int c = 0; c < C; ++c) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) { pr[c][k] = expf(pr[c][k] - mx[k]); den[k] += pr[c][k]; }
+        }
+#pragma unroll
+        for (int c = 0; c < C; ++c) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                pr[c][k] /= den[k];
+                acc[k] += gm[c][k] * pr[c][k];          // dw
+                gm[c][k] *= ww[k];                      // dmask
+                dotv[k] += gm[c][k] * pr[c][k];
+            }
+        }
+#pragma unroll
+        for (int c = 0; c < C; ++c)
+            *reinterpret_cast<float4*>(dscore + base + (size_t)c * NK) =
+                make_float4(pr[c][0] * (gm[c][0] - dotv[0]), pr[c][1] * (gm[c][1] - dotv[1]),
+                            pr[c][2] * (gm[c][2] - dotv[2]), pr[c][3] * (gm[c][3] - dotv[3]));
+    }
+    *reinterpret_cast<float4*>(dw + e) = make_float4(acc[0], acc[1], acc[2], acc[3]);
+}
+template <int C>
+__global__ __launch_bounds__(NT) void mask_apply_bwd2_kernel(const float* __restrict__ dsw, const float* __restrict__ score,
+                                                             const float* __restrict__ w, float* __restrict__ dscore,
+                                                             float* __restrict__ dw, int M, long long NK, int mode) {
+    const long long n4 = (long long)M * NK / 4, stride = (long long)gridDim.x * NT;
+    for (long long i = (long long)blockIdx.x * NT + threadIdx.x; i < n4; i += 2 * stride) {
+        const long long j = i + stride;
+        MaskGroup<C> a, b;
+        mask_group_load<C>(a, dsw, score, w, i * 4, NK);
+        if (j < n4) mask_group_load<C>(b, dsw, score, w, j * 4, NK);
+        mask_group_bwd<C>(a, dscore, dw, i * 4, NK, mode);
+        if (j < n4) mask_group_bwd<C>(b, dscore, dw, j * 4, NK, mode);
+    }
+}
+
 // est[b][t] = sum_{k,l: k*S+l = t} fr[b][l][k],  b over M*C rows; est is [B, T], zero for t >= (K-1)S+L
 __global__ __launch_bounds__(NT) void ola_kernel(const float* __restrict__ fr, float* __restrict__ est,
                                                  int Bn, int T, int L, int Lp, int S, int K, int Kp) {
@@ -324,8 +416,11 @@ int ctn_mask_apply_bwd(const float* dsw, const float* score, const float* w, flo
     CTN_REQUIRE(softmax != 1 || C <= MAXC, "ctn_mask_apply_bwd: softmax mask supports at most %d speakers", MAXC);
     CTN_REQUIRE(ctn_aligned16(dsw) && ctn_aligned16(score) && ctn_aligned16(w) && ctn_aligned16(dscore) && ctn_aligned16(dw), "ctn_mask_apply_bwd: alignment");
     const long long NK = (long long)N * Kp;
-    hipLaunchKernelGGL(mask_apply_bwd_kernel, dim3(grid_for((long long)M * NK / 4)), dim3(NT), 0, (hipStream_t)stream,
-                       dsw, score, w, dscore, dw, M, C, NK, softmax);
+    const unsigned grid2 = grid_for(ctn_cdivll((long long)M * NK / 4, 2));      // two element groups per thread and trip
+    if (C == 2) hipLaunchKernelGGL(mask_apply_bwd2_kernel<2>, dim3(grid2), dim3(NT), 0, (hipStream_t)stream, dsw, score, w, dscore, dw, M, NK, softmax);
+    else if (C == 3) hipLaunchKernelGGL(mask_apply_bwd2_kernel<3>, dim3(grid2), dim3(NT), 0, (hipStream_t)stream, dsw, score, w, dscore, dw, M, NK, softmax);
+    else hipLaunchKernelGGL(mask_apply_bwd_kernel, dim3(grid_for((long long)M * NK / 4)), dim3(NT), 0, (hipStream_t)stream,
+                            dsw, score, w, dscore, dw, M, C, NK, softmax);
     CTN_CHECK_LAUNCH("ctn_mask_apply_bwd");
     return CTN_OK;
 }

@@ -54,6 +54,12 @@ int ctn_pw_wgrad_h3_chained(const float* dOut, const float* X, float* dW, int M,
                             void* workspace, size_t workspace_bytes, void* stream, CtnWgradChain* chain);
 int ctn_wgrad_chain_flush(CtnWgradChain* chain, void* stream);
 
+// ---- h3 weight operands of a composite stack call in one launch (library-internal: ctn_block.hip calls, ctn_gemm.hip defines) ----
+// What ctn_split_h3_batch(src_h -> dst_h, [Rh, Cnh]) + ctn_split_h3_batch(src_b -> dst_b, [Rb, Cnb]) + ctn_absmax_batch(gsrc -> gdst,
+// 2 * nblocks vectors of glen floats; gsrc may be null) write, bit for bit.
+int ctn_prep_h3_fused(const void* const* src_h, void* const* dst_h, int Rh, int Cnh, const void* const* src_b, void* const* dst_b,
+                      int Rb, int Cnb, int nblocks, int k_major, const void* const* gsrc, void* const* gdst, int glen, void* stream);
+
 // ---- library-internal names that cross translation units: declared here only, each with the linkage of its definition ----
 extern "C" {
 extern int g_ctn_cln_fr;        // csrc/ctn_cln.hip: frames per workgroup of the channel-wise LayerNorm v4 kernels

@@ -762,7 +762,11 @@ int ctn_pw_wgrad_chained(const float* dOut, const float* X, float* dW, int M, in
     if ((rc = ctn_wgrad_chain_flush(chain, stream))) return rc;        // the fp32-MFMA kernels do not chain
     int wt;
     wgrad_plan(M, R, Cn, Kp, &wt, &a.chunk, &a.chunks_per_m);
-    a.tiles_r = ctn_cdiv(R, wt); a.tiles_c = ctn_cdiv(Cn, wt);
+    // Skinny layers (encoder / decoder bases: 20 live columns or rows): the 128-tile kernel on a 64-wide tile along the short side(s).
+    // The split-K partition above, the k-tiles and the MFMA chain of every output element are those of the 128 x 128 tile -- bitwise
+    // its gradients -- but a wave issues half (a quarter) of the MFMAs on zeros and the workgroup stages half the LDS rows.
+    const int wtr = (wt == 128 && R <= 64) ? 64 : wt, wtc = (wt == 128 && Cn <= 64) ? 64 : wt;
+    a.tiles_r = ctn_cdiv(R, wtr); a.tiles_c = ctn_cdiv(Cn, wtc);
     const int nsplit = M * a.chunks_per_m;
     if (workspace == nullptr || workspace_bytes < (size_t)nsplit * R * Cn * sizeof(float)) {
         ctn_set_error("ctn_pw_wgrad: workspace too small (%zu < %zu)", workspace_bytes, (size_t)nsplit * R * Cn * sizeof(float));
@@ -775,13 +779,33 @@ int ctn_pw_wgrad_chained(const float* dOut, const float* X, float* dW, int M, in
         if (pro_ms) hipLaunchKernelGGL((pw_wgrad4_kernel<PRO_PRELU_NORM>), grid, block, 0, st, a);
         else hipLaunchKernelGGL((pw_wgrad4_kernel<PRO_NONE>), grid, block, 0, st, a);
     } else {
-        if (pro_ms) hipLaunchKernelGGL((pw_wgrad_kernel<PRO_PRELU_NORM, 128, 128>), grid, block, 0, st, a);
-        else hipLaunchKernelGGL((pw_wgrad_kernel<PRO_NONE, 128, 128>), grid, block, 0, st, a);
+#define CTN_WGRAD_TILE(TM_, TN_) do { if (pro_ms) hipLaunchKernelGGL((pw_wgrad_kernel<PRO_PRELU_NORM, TM_, TN_>), grid, block, 0, st, a); \
+                                      else hipLaunchKernelGGL((pw_wgrad_kernel<PRO_NONE, TM_, TN_>), grid, block, 0, st, a); } while (0)
+        if (wtr == 64 && wtc == 64) CTN_WGRAD_TILE(64, 64);
+        else if (wtc == 64) CTN_WGRAD_TILE(128, 64);
+        else if (wtr == 64) CTN_WGRAD_TILE(64, 128);
+        else CTN_WGRAD_TILE(128, 128);
+#undef CTN_WGRAD_TILE
     }
     CTN_CHECK_LAUNCH("ctn_pw_wgrad");
     const long long n = (long long)R * Cn;
     hipLaunchKernelGGL(slab_reduce_kernel, dim3((unsigned)ctn_cdivll(n / 4, NT)), block, 0, st, a.slab, nsplit, n, dW);   // R, Cn multiples of 4
     CTN_CHECK_LAUNCH("ctn_pw_wgrad/reduce");
+    return CTN_OK;
+}
+
+// library-internal (ctn_common.h): the h3 weight operands of a composite stack call and its norm-parameter maxima in one launch
+int ctn_prep_h3_fused(const void* const* src_h, void* const* dst_h, int Rh, int Cnh, const void* const* src_b, void* const* dst_b,
+                      int Rb, int Cnb, int nblocks, int k_major, const void* const* gsrc, void* const* gdst, int glen, void* stream) {
+    CTN_REQUIRE(src_h && dst_h && src_b && dst_b && nblocks > 0 && Rh > 0 && Cnh > 0 && Rb > 0 && Cnb > 0 && (Rh * Cnh) % 4 == 0 &&
+                (Rb * Cnb) % 4 == 0 && (!gsrc || (gdst && glen > 0)), "ctn_prep_h3_fused: bad arguments");
+    for (int i = 0; i < nblocks; ++i)
+        CTN_REQUIRE(src_h[i] && dst_h[i] && src_b[i] && dst_b[i] && ctn_aligned16(src_h[i]) && ctn_aligned16(dst_h[i]) &&
+                    ctn_aligned16(src_b[i]) && ctn_aligned16(dst_b[i]), "ctn_prep_h3_fused: block %d: null or unaligned pointer", i);
+    for (int i = 0; gsrc && i < 2 * nblocks; ++i)
+        CTN_REQUIRE(gsrc[i] && gdst[i] && ctn_aligned16(gsrc[i]), "ctn_prep_h3_fused: vector %d: null or unaligned pointer", i);
+    ctn_b3_launch_prep_h3(src_h, dst_h, Rh, Cnh, src_b, dst_b, Rb, Cnb, nblocks, k_major, gsrc, gdst, 2, glen, (hipStream_t)stream);
+    CTN_CHECK_LAUNCH("ctn_prep_h3_fused");
     return CTN_OK;
 }
 

@@ -843,6 +843,30 @@ struct SplitArgs {
     __bf16* dst[SPLIT_MAX];
     int R, Cn, sr, sk, nkt;        // nkt = Cnp / 16
 };
+// one (rt, kt) fragment block of one weight, on one wave: 64 lanes x 8 values -> NP pieces of 1 KiB (load and split apart, so that
+// a caller can have the loads of several blocks in flight)
+__device__ __forceinline__ void split_b3_load(float (&v)[8], const float* __restrict__ W, int R, int Cn, int sr, int sk, int rt, int kt, int lane) {
+    const int r = rt * 32 + (lane & 31), k0 = kt * 16 + (lane >> 5) * 8;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) v[e] = (r < R && k0 + e < Cn) ? W[(size_t)r * sr + (size_t)(k0 + e) * sk] : 0.f;
+}
+template <int AR>
+__device__ __forceinline__ void split_b3_store(const float (&v)[8], __bf16* __restrict__ D, int nkt, int rt, int kt, int lane, float sc) {
+    constexpr int NP = Ar<AR>::NP;
+    bf16x4 q0[NP], q1[NP];
+    split_x4<AR>(make_float4(v[0], v[1], v[2], v[3]), q0, sc);
+    split_x4<AR>(make_float4(v[4], v[5], v[6], v[7]), q1, sc);
+    __bf16* const blk = D + ((size_t)(rt * nkt + kt) * NP) * 512 + lane * 8;     // 512 bf16 = 1 KiB per block
+#pragma unroll
+    for (int p = 0; p < NP; ++p) *reinterpret_cast<bf16x8*>(blk + p * 512) = __builtin_shufflevector(q0[p], q1[p], 0, 1, 2, 3, 4, 5, 6, 7);
+}
+template <int AR>
+__device__ __forceinline__ void split_b3_block(const float* __restrict__ W, __bf16* __restrict__ D, int R, int Cn, int sr, int sk,
+                                               int nkt, int rt, int kt, int lane, float sc) {
+    float v[8];
+    split_b3_load(v, W, R, Cn, sr, sk, rt, kt, lane);
+    split_b3_store<AR>(v, D, nkt, rt, kt, lane, sc);
+}
 template <int AR>
 __global__ __launch_bounds__(256) void split_b3_kernel(SplitArgs a) {
     constexpr int NP = Ar<AR>::NP;
@@ -856,16 +880,7 @@ __global__ __launch_bounds__(256) void split_b3_kernel(SplitArgs a) {
         const size_t pieces = (size_t)gridDim.y * 32 * (size_t)a.nkt * 16 * (2 * NP);
         sc = h3_pow2(h3_exp(__uint_as_float(*reinterpret_cast<const unsigned*>(reinterpret_cast<const char*>(D) + pieces))));
     }
-    const int r = rt * 32 + (lane & 31), k0 = kt * 16 + (lane >> 5) * 8;
-    float v[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) v[e] = (r < a.R && k0 + e < a.Cn) ? W[(size_t)r * a.sr + (size_t)(k0 + e) * a.sk] : 0.f;
-    bf16x4 q0[NP], q1[NP];
-    split_x4<AR>(make_float4(v[0], v[1], v[2], v[3]), q0, sc);
-    split_x4<AR>(make_float4(v[4], v[5], v[6], v[7]), q1, sc);
-    __bf16* const blk = D + ((size_t)(rt * a.nkt + kt) * NP) * 512 + lane * 8;     // 512 bf16 = 1 KiB per block
-#pragma unroll
-    for (int p = 0; p < NP; ++p) *reinterpret_cast<bf16x8*>(blk + p * 512) = __builtin_shufflevector(q0[p], q1[p], 0, 1, 2, 3, 4, 5, 6, 7);
+    split_b3_block<AR>(W, D, a.R, a.Cn, a.sr, a.sk, a.nkt, rt, kt, lane, sc);
 }
 
 // ---- range tracking for the h3 arithmetic -----------------------------------------------------------------------------
@@ -875,11 +890,13 @@ struct AbsmaxArgs {
     unsigned* dst[SPLIT_MAX];
     int n;
 };
-__global__ __launch_bounds__(1024) void absmax_batch_kernel(AbsmaxArgs a) {
-    __shared__ unsigned sc[16];
-    const float* __restrict__ S = a.src[blockIdx.x];
+// bit pattern of max |S[0 .. n)| over a workgroup of 1024 threads, returned to every thread; sc: 16 words of LDS.  DEEP: also a loop
+// with eight 16-byte loads in flight per thread (prep_h3_kernel, whose split phase needs the registers anyway; the exported
+// absmax_batch_kernel stays at four: 44 VGPRs)
+template <bool DEEP>
+__device__ __forceinline__ unsigned block_absmax_bits(const float* __restrict__ S, int n, unsigned* sc) {
     unsigned b = 0u;
-    const int n4 = a.n & ~3;
+    const int n4 = n & ~3;
     auto upd = [&](const float4& v) {
         const unsigned t0 = __float_as_uint(fabsf(v.x)), t1 = __float_as_uint(fabsf(v.y));
         const unsigned t2 = __float_as_uint(fabsf(v.z)), t3 = __float_as_uint(fabsf(v.w));
@@ -888,21 +905,77 @@ __global__ __launch_bounds__(1024) void absmax_batch_kernel(AbsmaxArgs a) {
         b = b > w ? b : w;
     };
     int i = threadIdx.x * 4;
-    for (; i + 3 * 4096 < n4; i += 4 * 4096) {       // four 16-byte loads in flight per thread
+    if constexpr (DEEP) {
+        for (; i + 7 * 4096 < n4; i += 8 * 4096) {   // eight 16-byte loads in flight per thread (sixteen spill under the 128 VGPRs of 1024 threads)
+            float4 v[8];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) v[j] = *reinterpret_cast<const float4*>(S + i + j * 4096);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) upd(v[j]);
+        }
+    }
+    for (; i + 3 * 4096 < n4; i += 4 * 4096) {       // four
         const float4 v0 = *reinterpret_cast<const float4*>(S + i), v1 = *reinterpret_cast<const float4*>(S + i + 4096);
         const float4 v2 = *reinterpret_cast<const float4*>(S + i + 2 * 4096), v3 = *reinterpret_cast<const float4*>(S + i + 3 * 4096);
         upd(v0); upd(v1); upd(v2); upd(v3);
     }
     for (; i < n4; i += 4096) upd(*reinterpret_cast<const float4*>(S + i));
-    for (int j = n4 + threadIdx.x; j < a.n; j += 1024) { const unsigned t = __float_as_uint(fabsf(S[j])); b = b > t ? b : t; }
+    for (int j = n4 + threadIdx.x; j < n; j += 1024) { const unsigned t = __float_as_uint(fabsf(S[j])); b = b > t ? b : t; }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) { const unsigned t = (unsigned)__shfl_xor((int)b, o, 64); b = b > t ? b : t; }
     if ((threadIdx.x & 63) == 0) sc[threadIdx.x >> 6] = b;
     __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned r = sc[0];
-        for (int w = 1; w < 16; ++w) r = r > sc[w] ? r : sc[w];
-        a.dst[blockIdx.x][0] = r;
+    unsigned r = sc[0];
+    for (int w = 1; w < 16; ++w) r = r > sc[w] ? r : sc[w];
+    return r;
+}
+__global__ __launch_bounds__(1024) void absmax_batch_kernel(AbsmaxArgs a) {
+    __shared__ unsigned sc[16];
+    const unsigned r = block_absmax_bits<false>(a.src[blockIdx.x], a.n, sc);
+    if (threadIdx.x == 0) a.dst[blockIdx.x][0] = r;
+}
+
+// All h3 weight operands of a composite stack call in ONE launch (prepare_weights of ctn_block.hip): what absmax_batch_kernel +
+// split_b3_kernel<H3AR> per operand shape and one more absmax_batch_kernel for the norm parameters write, bit for bit.  Weights
+// [0, nw0) have shape 0, [nw0, nw) shape 1.  pw workgroups serve each weight: each takes max |W| over the WHOLE matrix itself
+// (exact and order-free; the re-reads hit the caches) -- so nothing waits on another workgroup --, the first writes it behind the
+// pieces, and each splits every pw-th group of 16 fragment blocks with the scale derived from it.  The last ng workgroups take
+// max |.| of the ng norm-parameter vectors.
+struct PrepH3Args {
+    const float* src[SPLIT_MAX];
+    __bf16* dst[SPLIT_MAX];
+    const float* gsrc[SPLIT_MAX];
+    unsigned* gdst[SPLIT_MAX];
+    int R[2], Cn[2], sr[2], sk[2], nkt[2];
+    int nw, nw0, pw, ng, glen;
+};
+__global__ __launch_bounds__(1024) void prep_h3_kernel(PrepH3Args a) {
+    constexpr int NP = Ar<H3AR>::NP;
+    __shared__ unsigned sc[16];
+    const int bx = (int)blockIdx.x;
+    if (bx >= a.nw * a.pw) {
+        const int g = bx - a.nw * a.pw;
+        const unsigned r = block_absmax_bits<true>(a.gsrc[g], a.glen, sc);
+        if (threadIdx.x == 0) a.gdst[g][0] = r;
+        return;
+    }
+    const int w = bx / a.pw, part = bx % a.pw, h = w >= a.nw0 ? 1 : 0;
+    const int R = a.R[h], Cn = a.Cn[h], sr = a.sr[h], sk = a.sk[h], nkt = a.nkt[h], nrt = (R + 31) / 32;
+    const float* __restrict__ W = a.src[w];
+    __bf16* __restrict__ D = a.dst[w];
+    const unsigned mb = block_absmax_bits<true>(W, R * Cn, sc);
+    if (part == 0 && threadIdx.x == 0)
+        *reinterpret_cast<unsigned*>(reinterpret_cast<char*>(D) + (size_t)nrt * 32 * (size_t)nkt * 16 * (2 * NP)) = mb;
+    const float scl = h3_pow2(h3_exp(__uint_as_float(mb)));
+    const int lane = threadIdx.x & 63;
+    const int nwi = nrt * nkt, step = a.pw * 16;
+    for (int wi = part * 16 + (int)(threadIdx.x >> 6); wi < nwi; wi += 2 * step) {       // two fragment blocks per trip: 16 loads in flight
+        const int wj = wi + step;
+        float va[8], vb[8];
+        split_b3_load(va, W, R, Cn, sr, sk, wi / nkt, wi % nkt, lane);
+        if (wj < nwi) split_b3_load(vb, W, R, Cn, sr, sk, wj / nkt, wj % nkt, lane);
+        split_b3_store<H3AR>(va, D, nkt, wi / nkt, wi % nkt, lane, scl);
+        if (wj < nwi) split_b3_store<H3AR>(vb, D, nkt, wj / nkt, wj % nkt, lane, scl);
     }
 }
 // slots of amax[m] <- max |x[m][0 .. n)| : activations entering a stack (the caller zeroes amax); n % 4 == 0, 16-byte rows
@@ -1042,6 +1115,39 @@ static void ctn_b3_launch_split(int ar, const void* const* src, void* const* dst
         const dim3 grid(ctn_cdiv(sa.nkt, 4), (R + 31) / 32, cnt);
         if (ar == 4) hipLaunchKernelGGL(split_b3_kernel<H3AR>, grid, dim3(256), 0, st, sa);
         else hipLaunchKernelGGL(split_b3_kernel<3>, grid, dim3(256), 0, st, sa);
+    }
+}
+
+// prepare_weights (h3): operands of shape 0 (src0 -> dst0) and shape 1 (src1 -> dst1) of nblocks blocks plus max |.| of gper
+// vectors of glen floats per block (gsrc / gdst [nblocks * gper], may be null), SPLIT_MAX / 2 blocks per launch
+static void ctn_b3_launch_prep_h3(const void* const* src0, void* const* dst0, int R0, int Cn0, const void* const* src1, void* const* dst1,
+                                  int R1, int Cn1, int nblocks, int k_major, const void* const* gsrc, void* const* gdst, int gper,
+                                  int glen, hipStream_t st) {
+    constexpr int NB = SPLIT_MAX / 2;
+    for (int o = 0; o < nblocks; o += NB) {
+        PrepH3Args pa{};
+        const int cnt = nblocks - o < NB ? nblocks - o : NB;
+        for (int i = 0; i < cnt; ++i) {
+            pa.src[i] = (const float*)src0[o + i]; pa.dst[i] = (__bf16*)dst0[o + i];
+            pa.src[cnt + i] = (const float*)src1[o + i]; pa.dst[cnt + i] = (__bf16*)dst1[o + i];
+        }
+        pa.ng = gsrc != nullptr ? cnt * gper : 0;
+        for (int i = 0; i < pa.ng; ++i) { pa.gsrc[i] = (const float*)gsrc[o * gper + i]; pa.gdst[i] = (unsigned*)gdst[o * gper + i]; }
+        int items = 0;
+        for (int h = 0; h < 2; ++h) {
+            const int R = h ? R1 : R0, Cn = h ? Cn1 : Cn0;
+            pa.R[h] = R; pa.Cn[h] = Cn;
+            pa.sr[h] = k_major ? 1 : Cn; pa.sk[h] = k_major ? R : 1;
+            pa.nkt[h] = (Cn + XK - 1) / XK * 2;
+            const int it = (R + 31) / 32 * pa.nkt[h];
+            if (it > items) items = it;
+        }
+        pa.nw = 2 * cnt; pa.nw0 = cnt; pa.glen = glen;
+        pa.pw = 256 / pa.nw;        // about one workgroup per CU
+        if (pa.pw > 8) pa.pw = 8;
+        if (pa.pw > ctn_cdiv(items, 16)) pa.pw = ctn_cdiv(items, 16);       // (a workgroup splits 16 fragment blocks at a time)
+        if (pa.pw < 1) pa.pw = 1;
+        hipLaunchKernelGGL(prep_h3_kernel, dim3((unsigned)(pa.nw * pa.pw + pa.ng)), dim3(1024), 0, st, pa);
     }
 }
 

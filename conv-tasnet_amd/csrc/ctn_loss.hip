@@ -76,21 +76,42 @@ __global__ __launch_bounds__(NT) void sisnr_moments_kernel(const float* __restri
 }
 
 // coef[b][i][4] = {A, Bc, mean_e_i, mean_s_j}; jsel[b][i] = j
+// One workgroup.  The nchunk-long sums of the nmom(C) moments are latency, not bytes: a pass of PIT_UB utterances puts one
+// (utterance, moment) pair on every lane, issues its chunk loads eight at a time and adds them in chunk order into LDS; then
+// thread b % NT does utterance b's algebra and permutation search, so every thread's share of the batch mean is summed in the
+// order of one thread per utterance.
+constexpr int PIT_UB = 32;      // utterances per pass (divides NT)
 __global__ __launch_bounds__(NT) void sisnr_pit_kernel(const double* __restrict__ partial, const long long* __restrict__ lens,
                                                        const int* __restrict__ perms, int nperm, int B, int C, int T,
                                                        int nchunk, float* __restrict__ max_snr, long long* __restrict__ idx_out,
                                                        float* __restrict__ loss, float* __restrict__ snr_out,
                                                        float* __restrict__ coef, int* __restrict__ jsel) {
     __shared__ double red[NT / 64];
+    __shared__ double mom[PIT_UB * (4 * MAXC + MAXC * MAXC)];
     double local = 0.0;
     const int nm = nmom(C);
-    for (int b = threadIdx.x; b < B; b += NT) {
-        double mo[4 * MAXC + MAXC * MAXC];
-        for (int q = 0; q < nm; ++q) {
+    for (int b0 = 0; b0 < B; b0 += PIT_UB) {
+        const int nb = min(PIT_UB, B - b0);
+        __syncthreads();        // the previous pass has read mom
+        for (int it = threadIdx.x; it < nb * nm; it += NT) {
+            const double* __restrict__ p = partial + ((size_t)(b0 + it / nm) * nchunk) * nm + it % nm;
             double s = 0.0;
-            for (int ch = 0; ch < nchunk; ++ch) s += partial[((size_t)b * nchunk + ch) * nm + q];
-            mo[q] = s;
+            int ch = 0;
+            for (; ch + 8 <= nchunk; ch += 8) {
+                double v[8];
+#pragma unroll
+                for (int j = 0; j < 8; ++j) v[j] = p[(size_t)(ch + j) * nm];
+#pragma unroll
+                for (int j = 0; j < 8; ++j) s += v[j];
+            }
+            for (; ch < nchunk; ++ch) s += p[(size_t)ch * nm];
+            mom[it] = s;
         }
+        __syncthreads();
+        const int off = (int)threadIdx.x - b0 % NT;
+        if (off < 0 || off >= nb) continue;
+        const int b = b0 + off;
+        const double* mo = mom + off * nm;
         long long len = lens[b];
         if (len > T) len = T;
         const double n = (double)len;
