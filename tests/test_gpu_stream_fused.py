@@ -1,5 +1,6 @@
 """GPU: FusedStreamingSeparator (csrc/ctn_stream.hip) -- the reference's recorded output, bitwise chunk / batch invariance, the fp64
-oracle as yardstick against the full forward and against the eager StreamingSeparator, reset / graph replay / refresh."""
+oracle as yardstick against the full forward and against the eager StreamingSeparator, reset / graph replay / refresh.
+(Kernel by kernel, at the seams of the tiling and against an fp64 oracle of each entry point: tests/test_gpu_stream_seams.py.)"""
 import pytest
 import torch
 
