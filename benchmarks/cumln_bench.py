@@ -1,0 +1,97 @@
+#!/usr/bin/env python
+"""Time the cumulative LayerNorm against the per-frame channel-wise one of the same build, at the causal paper shape [8, 512, 3199]:
+the two norms with passes of their own (ctn_cumln_fwd / _bwd vs ctn_cln_fwd / _bwd), the two per-frame kernels (the scans vs
+ctn_cln_stats_frame / ctn_cln_bwd_frame), and the causal paper-config training step with norm_type cumLN vs cLN, both block by block
+(CTN_COMPOSITE=0: cumLN has no composite stack).  Pairs alternate inside one process; every figure is the median of `reps` windows.
+
+usage: python benchmarks/cumln_bench.py [--no-step] [--json OUT]      (prints a table and, with --json, writes the figures)"""
+import json
+import os
+import statistics
+import sys
+
+os.environ.setdefault("CTN_COMPOSITE", "0")
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch  # noqa: E402
+import conv_tasnet_amd as ctn  # noqa: E402
+from conv_tasnet_amd import ops  # noqa: E402
+from conv_tasnet_amd.optim import FlatAdam  # noqa: E402
+from conv_tasnet_amd.train import SyntheticLoader  # noqa: E402
+
+M, H, K = 8, 512, 3199
+Kp = ops.padded_frames(K)
+dev = "cuda:0"
+res = {"shape": [M, H, K], "Kp": Kp}
+
+
+def window(fn, iters):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(iters):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / iters * 1e3            # us per call
+
+
+def pair(name, a, b, iters=50, reps=7):
+    """Median us of a (cumLN) and b (cLN), measured in alternating windows."""
+    for _ in range(5):
+        a(); b()
+    torch.cuda.synchronize()
+    ta, tb = [], []
+    for _ in range(reps):
+        ta.append(window(a, iters))
+        tb.append(window(b, iters))
+    x, y = statistics.median(ta), statistics.median(tb)
+    res[name] = {"cumln_us": round(x, 2), "cln_us": round(y, 2), "ratio": round(x / y, 3), "cumln_spread_us": [round(min(ta), 2), round(max(ta), 2)],
+                 "cln_spread_us": [round(min(tb), 2), round(max(tb), 2)]}
+    print("%-12s cumLN %8.1f us [%6.1f .. %6.1f]   cLN %8.1f us [%6.1f .. %6.1f]   ratio %.2f" % (name, x, min(ta), max(ta), y, min(tb), max(tb), x / y), flush=True)
+
+
+torch.manual_seed(0)
+y = torch.randn(M, H, Kp, device=dev) + 0.3
+y[..., K:] = 0
+dout = torch.randn(M, H, Kp, device=dev)
+dout[..., K:] = 0
+g, b = 1 + 0.3 * torch.randn(H, device=dev), 0.3 * torch.randn(H, device=dev)
+a = torch.full((1,), 0.25, device=dev)
+nbytes = M * H * Kp * 4
+
+_, mean_c, rstd_c = ops.cumln_fwd(y, g, b, a, K)
+_, mean_f, rstd_f = ops.cln_fwd(y, g, b, a, K)
+pair("fwd", lambda: ops.cumln_fwd(y, g, b, a, K), lambda: ops.cln_fwd(y, g, b, a, K))
+pair("bwd", lambda: ops.cumln_bwd(dout, y, mean_c, rstd_c, g, a, K), lambda: ops.cln_bwd(dout, y, mean_f, rstd_f, g, a, K))
+for k, passes in (("fwd", (3, 2)), ("bwd", (5, 3))):
+    res[k]["cumln_TBps"] = round(passes[0] * nbytes / res[k]["cumln_us"] / 1e6, 2)
+    res[k]["cln_TBps"] = round(passes[1] * nbytes / res[k]["cln_us"] / 1e6, 2)
+    res[k]["byte_ratio"] = round(passes[0] / passes[1], 2)
+nparts = ctn.lib.ctn_pw_col_parts(M, H, Kp, 3)                 # the row tiles of the h3 GEMM that feeds the frame kernels in the step
+colp = torch.rand(M, nparts, Kp, 2, dtype=torch.float64, device=dev)
+res["frame_nparts"] = nparts
+pair("stats_frame", lambda: ops.cumln_stats_frame(colp, H, K), lambda: ops.cln_stats_frame(colp, H), iters=100)
+pair("bwd_frame", lambda: ops.cumln_bwd_frame(colp, mean_c, rstd_c, H, K), lambda: ops.cln_bwd_frame(colp, mean_f, rstd_f, H), iters=100)
+
+if "--no-step" not in sys.argv:
+    assert not ops.composite_enabled()
+    mix, lens, src = next(iter(SyntheticLoader(1, 8, samples=32000, C=2, sample_rate=8000)))
+    mix, lens, src = mix.to(dev), lens.to(dev), src.to(dev)
+    steps = {}
+    for norm in ("cumLN", "cLN"):
+        torch.manual_seed(0)
+        m = ctn.ConvTasNet(256, 20, 256, 512, 3, 8, 4, 2, norm_type=norm, causal=True).to(dev)
+        opt = FlatAdam(m.parameters(), lr=1e-3)
+
+        def step(m=m, opt=opt):
+            opt.zero_grad()
+            ctn.cal_loss(src, m(mix), lens)[0].backward()
+            opt.step(max_grad_norm=5.0)
+        steps[norm] = step
+    pair("step", steps["cumLN"], steps["cLN"], iters=5, reps=5)
+    for k in ("cumln_us", "cln_us"):
+        res["step"][k.replace("_us", "_ms")] = round(res["step"].pop(k) / 1e3, 3)
+
+if "--json" in sys.argv:
+    with open(sys.argv[sys.argv.index("--json") + 1], "w") as f:
+        json.dump(res, f, indent=1)
+print(json.dumps(res))

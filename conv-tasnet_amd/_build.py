@@ -7,7 +7,7 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libctn_hip.so")
-SOURCES = ["ctn_api.hip", "ctn_gemm.hip", "ctn_dw.hip", "ctn_cln.hip", "ctn_bn.hip", "ctn_codec.hip", "ctn_loss.hip", "ctn_optim.hip",
+SOURCES = ["ctn_api.hip", "ctn_gemm.hip", "ctn_dw.hip", "ctn_cln.hip", "ctn_cumln.hip", "ctn_bn.hip", "ctn_codec.hip", "ctn_loss.hip", "ctn_optim.hip",
            "ctn_block.hip", "ctn_bss.hip", "ctn_stream.hip", "ctn_dynmix.hip", "ctn_resample.hip", "ctn_dynmix_aug.hip",
            "ctn_longform.hip", "ctn_stoi.hip", "ctn_mixit.hip", "ctn_varpit.hip", "ctn_dynmix_active.hip"]
 # -amdgpu-mfma-vgpr-form: MFMA results stay in VGPRs (unified file on gfx950), so the epilogues read them without

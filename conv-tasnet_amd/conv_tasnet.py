@@ -28,6 +28,8 @@ class ConvTasNet(nn.Module):
     def __init__(self, N, L, B, H, P, X, R, C, norm_type="gLN", causal=False, mask_nonlinear='relu'):
         super().__init__()
         self.N, self.L, self.B, self.H, self.P, self.X, self.R, self.C = N, L, B, H, P, X, R, C
+        if norm_type == "cumLN" and not causal:
+            raise ValueError('norm_type="cumLN" (the cumulative layer norm) needs causal=True: a non-causal model looks ahead anyway')
         self.norm_type = norm_type
         self.causal = causal
         self.mask_nonlinear = mask_nonlinear
@@ -323,6 +325,8 @@ class TemporalBlock(nn.Module):
             fn = ops.GlnBlock
         elif self.norm_type == "cLN":
             fn = ops.ClnBlock
+        elif self.norm_type == "cumLN":
+            fn = ops.CumLnBlock
         else:       # chose_norm's else-branch: BatchNorm1d (src/conv_tasnet.py:305-309)
             return ops.BnBlock.apply(x, self.net[0].weight, self.net[1].weight, norm1.weight, norm1.bias,
                                      ds.net[0].weight, ds.prelu().weight, norm2.weight, norm2.bias,
@@ -380,6 +384,8 @@ def chose_norm(norm_type, channel_size):
         return GlobalLayerNorm(channel_size)
     elif norm_type == "cLN":
         return ChannelwiseLayerNorm(channel_size)
+    elif norm_type == "cumLN":
+        return CumulativeLayerNorm(channel_size)
     else:
         return BatchNorm1d(channel_size)
 
@@ -446,6 +452,36 @@ class ChannelwiseLayerNorm(_NormParams):
     def forward(self, y):
         K = y.size(-1)
         return _ClnOnly.apply(_pad_frames(y, K), self.gamma, self.beta, K)[..., :K]
+
+
+class _CumLnOnly(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, y, gamma, beta, K):
+        y = y.contiguous()
+        out, mean, rstd = ops.cumln_fwd(y, gamma, beta, None, K)
+        ctx.save_for_backward(y, mean, rstd, gamma)
+        ctx.K = K
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        y, mean, rstd, gamma = ctx.saved_tensors
+        dy, dg, db, _ = ops.cumln_bwd(dout.contiguous(), y, mean, rstd, gamma, None, ctx.K)
+        return dy, dg.view_as(gamma), db.view_as(gamma), None
+
+
+class CumulativeLayerNorm(_NormParams):
+    """cumLN: the cumulative layer norm of the paper's causal model (Luo & Mesgarani 2019, eq. 12-14; not in src/conv_tasnet.py, whose
+    causal "cLN" is per frame).  Frame k of [M, Ch, K] is normalised by the mean and the biased variance of all channels of
+    frames 0..k, then scaled by gamma / beta [1, Ch, 1] -- the parameters, state-dict keys and init of ChannelwiseLayerNorm.
+
+    ``ConvTasNet(..., norm_type="cumLN", causal=True)`` puts it at both norms of every TemporalBlock (ops.CumLnBlock); the norm of the
+    encoder output stays channel-wise per frame, as with every norm_type.  Called on its own it is an ordinary
+    differentiable module (_CumLnOnly)."""
+
+    def forward(self, y):
+        K = y.size(-1)
+        return _CumLnOnly.apply(_pad_frames(y.to(torch.float32), K), self.gamma, self.beta, K)[..., :K]
 
 
 class _GlnOnly(torch.autograd.Function):

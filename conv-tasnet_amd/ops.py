@@ -12,6 +12,8 @@ autograd node:
   GlnBlock : TemporalBlock with gLN, fully fused                  (src/conv_tasnet.py:218-278)
   ClnBlock : TemporalBlock with cLN (causal variant)              (same, norm_type='cLN'; the first norm's forward and the second
              norm's backward ride in the neighbouring GEMM epilogues / depthwise kernels: ctn_tune("cln_fuse"), include/ctn_hip.h)
+  CumLnBlock: TemporalBlock with the cumulative LayerNorm of the paper's causal model (norm_type='cumLN'; ClnBlock's fused chain
+             with the per-frame statistics / backward constants from prefix and suffix scans, csrc/ctn_cumln.hip)
   Backend  : mask 1x1 -> relu|softmax -> mask*w -> basis -> OLA   (src/conv_tasnet.py:191,206-215,131-146)
   SiSnrPit : PIT SI-SNR loss                                      (src/pit_criterion.py:12-77)
 """
@@ -510,6 +512,74 @@ def cln_bwd(dOut, Y, mean, rstd, gamma, alpha, K, add=None, relu_ref=None, sinks
     return dY, dg, db, da
 
 
+# ---- cumulative LayerNorm (csrc/ctn_cumln.hip): frame k normalised by the statistics of frames 0..k ----
+def cumln_state(M, device):
+    """(carry [M,4] f64, count [M] i64), zeroed: the device-side record that carries a cumulative norm's prefix sums from one chunk
+    of a stream to the next (cumln_fwd / cumln_stats_frame advance it in place; zero it to start a new stream)."""
+    return (torch.zeros((M, 4), dtype=F64, device=device), torch.zeros((M,), dtype=torch.int64, device=device))
+
+
+def cumln_stats_frame(col_part, Ch, K, state=None):
+    """ctn_cumln_stats_frame: cumulative (mean, rstd) [M, Kp] from ctn_pw_gemm_cln's column partials.  state: cumln_state() or None."""
+    M, nparts, Kp, _ = col_part.shape
+    mean = torch.empty((M, Kp), dtype=F32, device=col_part.device)
+    rstd = torch.empty((M, Kp), dtype=F32, device=col_part.device)
+    carry, count = state or (None, None)
+    _chk_aux(col_part, carry, count)
+    lib.call("ctn_cumln_stats_frame", _p(col_part), nparts, _p(mean), _p(rstd), _p(carry), _p(count), M, Ch, K, Kp, _stream())
+    return mean, rstd
+
+
+def cumln_bwd_frame(col_part, mean, rstd, Ch, K):
+    """ctn_cumln_bwd_frame: fc [M, 4, Kp] = (rstd, mean rstd, U - W + mean V, V / rstd) per frame (suffix sums over the valid frames)
+    from ctn_pw_dgrad_cln's partials: what ctn_dw_bwd_cln needs to apply a cumulative norm's backward."""
+    M, nparts, Kp, _ = col_part.shape
+    fc = torch.empty((M, 4, Kp), dtype=F32, device=mean.device)
+    _chk(mean, rstd)
+    _chk_aux(col_part)
+    lib.call("ctn_cumln_bwd_frame", _p(col_part), nparts, _p(mean), _p(rstd), _p(fc), M, Ch, K, Kp, _stream())
+    return fc
+
+
+def cumln_fwd(Y, gamma, beta, alpha, K, state=None):
+    """ctn_cumln_fwd -> (out, mean [M,Kp], rstd [M,Kp]).  state: cumln_state() of a stream (advanced in place) or None."""
+    M, Ch, Kp = Y.shape
+    out = torch.empty_like(Y)
+    mean = torch.empty((M, Kp), dtype=F32, device=Y.device)
+    rstd = torch.empty((M, Kp), dtype=F32, device=Y.device)
+    work = torch.empty((lib.ctn_cumln_work_bytes(M, Kp),), dtype=torch.uint8, device=Y.device)
+    carry, count = state or (None, None)
+    _chk(Y, gamma, beta, alpha)
+    _chk_aux(carry, count)
+    lib.call("ctn_cumln_fwd", _p(Y), _p(out), _p(mean), _p(rstd), M, Ch, K, Kp, _p(gamma), _p(beta), _p(alpha), _p(carry), _p(count),
+             _p(work), _stream())
+    return out, mean, rstd
+
+
+def cumln_bwd(dOut, Y, mean, rstd, gamma, alpha, K, sinks=None):
+    """ctn_cumln_bwd + ctn_cln_bwd_finalize -> dY, dgamma[Ch], dbeta[Ch], dalpha[1]|None; sinks as for cln_bwd."""
+    M, Ch, Kp = Y.shape
+    dev = Y.device
+    dY = torch.empty_like(Y)
+    pc = torch.empty((lib.ctn_cln_bwd_pc_floats(M, Ch, Kp),), dtype=F32, device=dev)
+    dap = None if alpha is None else torch.empty((lib.ctn_cln_bwd_blocks(M, Kp),), dtype=F32, device=dev)
+    work = torch.empty((lib.ctn_cumln_work_bytes(M, Kp),), dtype=torch.uint8, device=dev)
+    _chk(dOut, Y, mean, rstd, gamma, alpha)
+    lib.call("ctn_cumln_bwd", _p(dOut), _p(Y), _p(dY), _p(mean), _p(rstd), M, Ch, K, Kp, _p(gamma), _p(alpha), _p(dap), _p(pc),
+             _p(work), _stream())
+    if sinks is not None:
+        dg, db, da = sinks
+    else:
+        dg = torch.empty((Ch,), dtype=F32, device=dev)
+        db = torch.empty((Ch,), dtype=F32, device=dev)
+        da = None if dap is None else torch.empty((1,), dtype=F32, device=dev)
+    _chk(dg, db, da)
+    lib.call("ctn_cln_bwd_finalize", _p(pc), _p(dap), M, Ch, Kp, _p(dg), _p(db), _p(da if dap is not None else None), _stream())
+    if sinks is not None:
+        return dY, None, None, None
+    return dY, dg, db, da
+
+
 def dw_fwd(Y, D, K, dilation, causal, pro=None, epi_alpha=None, ms_out=None):
     M, H, Kp = Y.shape
     P = D.shape[-1]
@@ -1000,6 +1070,63 @@ class ClnBlock(torch.autograd.Function):
         if direct:
             if not fuse:
                 sk[4].copy_(dD)
+            return (dx,) + (None,) * 12
+        return (dx, dW1.view(H, B, 1), da1, dg1.view(1, H, 1), db1.view(1, H, 1), dD, da2, dg2.view(1, H, 1),
+                db2.view(1, H, 1), dW2.view(B, H, 1), None, None, None)
+
+
+class CumLnBlock(torch.autograd.Function):
+    """TemporalBlock with the cumulative LayerNorm (norm_type="cumLN", causal): ClnBlock's fused chain, always -- per frame a cumulative
+    norm is the channel-wise norm's affine form with other constants, so the GEMMs, ctn_dw_fwd_cln, ctn_pw_dgrad_cln, ctn_dw_bwd_cln,
+    the weight gradients, the h3 maxima and the gradient sinks are ClnBlock's, and four calls differ: the first norm's statistics and
+    the second norm's backward constants come from the scans (cumln_stats_frame, cumln_bwd_frame), and the two norms that have passes
+    of their own run cumln_fwd / cumln_bwd.  ctn_tune("cln_fuse") does not apply; there is no composite stack."""
+
+    @staticmethod
+    def forward(ctx, x, w1, a1, g1, b1, D, a2, g2, b2, w2, K, dilation, causal):
+        x = _c(x)
+        M, B, Kp = x.shape
+        H = w1.shape[0]
+        if H % 4 or B % 4:
+            raise ValueError("HIP path needs B and H to be multiples of 4")
+        h3 = _h3_block(B, H)
+        ax = absmax_rows(x) if h3 else None
+        h1, colp = pw_gemm_cln(w1, x, H, B, K, a1, x_amax=ax)
+        mean1, rstd1 = cumln_stats_frame(colp, H, K)
+        d = dw_fwd_cln(h1, D, K, dilation, causal, mean1, rstd1, g1, b1, a1)
+        n2, mean2, rstd2 = cumln_fwd(d, g2, b2, a2, K)
+        an = absmax_rows(n2) if h3 else None
+        out, _ = _gemm(w2, n2, B, H, K, an, residual=x)
+        ctx.h3 = (ax, an) if h3 else None
+        ctx.save_for_backward(x, h1, d, n2, mean1, rstd1, mean2, rstd2, w1, a1, g1, D, a2, g2, w2, b1)
+        ctx.cfg = (K, dilation, causal)
+        ctx.sinks = tuple(_sink(p) for p in (w1, a1, g1, b1, D, a2, g2, b2, w2))
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        x, h1, d, n2, mean1, rstd1, mean2, rstd2, w1, a1, g1, D, a2, g2, w2, b1 = ctx.saved_tensors
+        K, dilation, causal = ctx.cfg
+        dout = _c(dout)
+        M, B, Kp = x.shape
+        H = w1.shape[0]
+        sk = ctx.sinks
+        direct = all(t is not None for t in sk)
+        if direct:
+            _claim_sinks(w1)
+        side = direct and _SIDE_ENABLED and _CLN_SIDE
+        ax, an = ctx.h3 or (None, None)
+        h3 = ax is not None
+        ady = absmax_rows(dout) if h3 else None
+        dn2, colp = pw_dgrad_cln(w2, dout, H, B, K, d, g2, a2, mean2, rstd2, g_amax=ady)
+        dW2 = _wgrad(side, direct, dout, n2, B, H, K, sk[8], h3=(ady, an, None) if h3 else None)
+        fc = cumln_bwd_frame(colp, mean2, rstd2, H, K)
+        dn1, dD, dg2, db2, da2 = dw_bwd_cln(dn2, d, h1, D, K, dilation, causal, g2, a2, fc,
+                                            sinks=(sk[4], sk[6], sk[7], sk[5]) if direct else None,
+                                            norm1=(g1, b1, a1, mean1, rstd1))
+        dh1, dg1, db1, da1 = cumln_bwd(dn1, h1, mean1, rstd1, g1, a1, K, sinks=(sk[2], sk[3], sk[1]) if direct else None)
+        dx, dW1 = _first_conv_bwd(side, direct, w1, dh1, x, dout, K, sk[0], ax)
+        if direct:
             return (dx,) + (None,) * 12
         return (dx, dW1.view(H, B, 1), da1, dg1.view(1, H, 1), db1.view(1, H, 1), dD, da2, dg2.view(1, H, 1),
                 db2.view(1, H, 1), dW2.view(B, H, 1), None, None, None)

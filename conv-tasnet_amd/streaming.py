@@ -7,6 +7,11 @@ separated chunk by chunk, exactly, by carrying per block the last (P-1)*dilation
 plus the encoder's L-S input samples and the decoder's L-S overlap-add samples.  Total left context is
 R*(P-1)*(2^X-1) frames (2040 at the paper config) -- but it is state, not recomputation.
 
+``norm_type='cumLN'`` (the paper's cumulative layer norm, csrc/ctn_cumln.hip) adds one more kind of state: per norm the prefix sums
+of the frames so far and their count, kept in device memory and advanced by the scan kernel itself (so a captured graph replays
+it); the order of the prefix sums is fixed by the absolute frame index, so the statistics do not depend on the chunking.
+`StreamingSeparator` serves such models; the fused classes below do not.
+
 All arithmetic runs through the same HIP entry points as training (ops.py); torch only slices / concatenates.
 """
 import torch
@@ -25,7 +30,7 @@ def _padded(t, K):
 
 
 class StreamingSeparator:
-    """Stateful chunk-wise separation with a causal ConvTasNet.
+    """Stateful chunk-wise separation with a causal ConvTasNet (norm_type 'cLN' or 'cumLN').
 
         s = StreamingSeparator(model, batch=1)
         for chunk in stream:            # chunk: [M, n*S] samples, S = L//2, n >= 1
@@ -40,8 +45,9 @@ class StreamingSeparator:
     """
 
     def __init__(self, model, batch=1, graph=False):
-        if not model.causal or model.norm_type != "cLN":
-            raise ValueError("streaming needs the causal cLN variant (gLN statistics span the whole utterance)")
+        if not model.causal or model.norm_type not in ("cLN", "cumLN"):
+            raise ValueError("streaming needs the causal cLN or cumLN variant (gLN statistics span the whole utterance)")
+        self.cum = model.norm_type == "cumLN"
         self.m = model
         self.M = batch
         self.L, self.S = model.L, model.L // 2
@@ -60,6 +66,8 @@ class StreamingSeparator:
                 for blk in rep:
                     halo = (m.P - 1) * blk.dilation
                     self.hist.append(torch.zeros((M, m.H, halo), device=dev))
+            # cumLN: per norm the prefix sums and the frame count so far, on the device (the scan kernel advances them: graph replay)
+            self.cum_state = [ops.cumln_state(M, dev) for _ in range(2 * len(self.hist))] if self.cum else []
             self._graphs = {}            # chunk length -> (graph, static chunk, static output)
             self._seen = {}              # chunk length -> eager steady-state chunks so far
         else:
@@ -67,6 +75,9 @@ class StreamingSeparator:
             self.ola_tail.zero_()
             for h in self.hist:
                 h.zero_()
+            for carry, count in self.cum_state:
+                carry.zero_()
+                count.zero_()
         self.first = True
 
     @torch.no_grad()
@@ -118,13 +129,19 @@ class StreamingSeparator:
                 ds = blk.net[3]
                 halo = (m.P - 1) * blk.dilation
                 h, _ = ops.pw_gemm(blk.net[0].weight, y, m.H, m.B, K)
-                n1, _, _ = ops.cln_fwd(h, blk.net[2].gamma, blk.net[2].beta, blk.net[1].weight, K)
+                if self.cum:
+                    n1, _, _ = ops.cumln_fwd(h, blk.net[2].gamma, blk.net[2].beta, blk.net[1].weight, K, self.cum_state[2 * i])
+                else:
+                    n1, _, _ = ops.cln_fwd(h, blk.net[2].gamma, blk.net[2].beta, blk.net[1].weight, K)
                 cat = torch.cat([self.hist[i], n1[..., :K]], dim=2)          # [M, H, halo + K]
                 self.hist[i].copy_(cat[..., cat.shape[2] - halo:])
                 Kc = halo + K
                 z, _ = ops.dw_fwd(_padded(cat, Kc), ds.net[0].weight, Kc, blk.dilation, True)
                 z = _padded(z[..., halo:Kc], K)
-                n2, _, _ = ops.cln_fwd(z, ds.norm().gamma, ds.norm().beta, ds.prelu().weight, K)
+                if self.cum:
+                    n2, _, _ = ops.cumln_fwd(z, ds.norm().gamma, ds.norm().beta, ds.prelu().weight, K, self.cum_state[2 * i + 1])
+                else:
+                    n2, _, _ = ops.cln_fwd(z, ds.norm().gamma, ds.norm().beta, ds.prelu().weight, K)
                 y, _ = ops.pw_gemm(ds.pointwise().weight, n2, m.B, m.H, K, residual=y)
                 i += 1
         # mask -> decoder frames -> overlap-add with carry
@@ -152,7 +169,8 @@ class _FusedBase:
     def _setup(self, model, batch, max_chunk_frames, graph):
         import ctypes
         if not model.causal or model.norm_type != "cLN":
-            raise ValueError("streaming needs the causal cLN variant (gLN statistics span the whole utterance)")
+            raise ValueError("the fused streaming kernels need the causal cLN variant (gLN statistics span the whole utterance; "
+                             "cumLN is not supported here: use StreamingSeparator)")
         if max_chunk_frames < 1 or batch < 1:
             raise ValueError("batch and max_chunk_frames must be positive")
         m = self.m = model

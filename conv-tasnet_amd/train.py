@@ -114,6 +114,9 @@ def build_parser():
     ap.add_argument("--segment-len", type=int, default=32000, help="samples per segment of the dynamic-mixing loaders")
     ap.add_argument("--tiny", action="store_true", help="a tiny model (N=64 L=20 B=32 H=64 P=3 X=2 R=2) instead of the paper's: a "
                     "quick end-to-end check of a data path")
+    ap.add_argument("--norm", choices=("gLN", "cLN", "cumLN", "BN"), default=None, help="norm of the TemporalBlocks (default: the "
+                    "configuration's, gLN); cumLN: the paper's cumulative layer norm, with --causal")
+    ap.add_argument("--causal", action="store_true", help="the causal model (left-padded depthwise convs)")
     ap.add_argument("--speed-perturb", default=None, metavar="LO:HI", help="--dynamic-mix only: replay every source at a drawn "
                     "integer percent of its speed in [LO, HI], e.g. 95:105 (resampled on the device); validation never perturbs")
     ap.add_argument("--corpus-rate", default="8000", choices=["8000", "auto"], help="rate of the --dynamic-mix files: 8000 (any "
@@ -177,6 +180,8 @@ TINY = dict(N=64, L=20, B=32, H=64, P=3, X=2, R=2, C=2)
 def main(argv=None):
     import os
     a = build_parser().parse_args(argv)
+    if a.norm == "cumLN" and not a.causal:
+        raise SystemExit("--norm cumLN needs --causal")
     if a.speed_perturb and not a.dynamic_mix:
         raise SystemExit("--speed-perturb applies to --dynamic-mix only")
     if (a.noise or a.rirs) and not a.dynamic_mix:
@@ -248,6 +253,12 @@ def main(argv=None):
         config = dict(TINY if a.tiny else PAPER, C=speakers)
         extra = dict(loss="varpit", snr_max=None if a.snr_max.lower() == "none" else float(a.snr_max),
                      inactive_snr_max=None if a.inactive_snr_max.lower() == "none" else float(a.inactive_snr_max))
+    if a.norm is not None or a.causal:          # (untouched otherwise: the configurations above as they are)
+        config = dict(config if config is not None else PAPER)
+        if a.norm is not None:
+            config['norm_type'] = a.norm
+        if a.causal:
+            config['causal'] = 1
     return train({'tr_loader': tr, 'cv_loader': cv}, a.epochs, a.model_path, save_folder=a.save_folder, lr=a.lr,
                  optimizer_type=a.optimizer, momentum=a.momentum, l2=a.l2, config=config,
                  enable_checkpoint=int(a.checkpoint), continue_from=a.continue_from, **extra)

@@ -385,6 +385,38 @@ int ctn_cln_bwd_frame(const double* col_part, int nparts, const float* mean, con
 int ctn_cln_bwd_finalize(const float* pc, const float* dalpha_part, int M, int Ch, int Kp, float* dgamma, float* dbeta,
                          float* dalpha, void* stream);
 
+/* ---- cumulative LayerNorm (the causal norm of Luo & Mesgarani 2019, eq. 12-14; not in src/conv_tasnet.py) -----
+ * Frame k is normalised by the statistics of all channels of all frames 0..k of its utterance (a = prelu(Y, alpha) or Y):
+ *     mean_k = sum_{j<=k} sum_c a[c,j] / n_k,  n_k = Ch (k + 1),  rstd_k = 1 / sqrt(max(E_k[a^2] - mean_k^2, 0) + eps),
+ *     Out = gamma (a - mean_k) rstd_k + beta.
+ * Per frame that is the channel-wise norm's affine form, so ctn_pw_gemm_cln / ctn_dw_fwd_cln and ctn_pw_dgrad_cln / ctn_dw_bwd_cln
+ * serve it unchanged; only the per-frame kernels between them differ:
+ *   ctn_cumln_stats_frame: col_part as for ctn_cln_stats_frame -> mean, rstd [M,Kp]; frames k >= K get (0, 1/sqrt(eps)).
+ *   ctn_cumln_bwd_frame  : col_part as for ctn_cln_bwd_frame (the sums taken with the cumulative mean / rstd) ->
+ *       fc [M][4][Kp] = (rstd, mean rstd, U - W + mean V, V / rstd)[k] with the suffix sums over the valid frames
+ *       (U, V, W)_j = sum_{j<=k<K} (rstd_k S1_k, rstd_k^2 S2_k, rstd_k^2 S2_k mean_k) / n_k, which ctn_dw_bwd_cln turns into
+ *       da = rstd gamma dN - U + W - a V.
+ * The prefix sums run in fp64 in ONE order fixed by the absolute frame index (64-frame blocks sequentially inside, block prefixes
+ * sequentially), so a stream cut into calls anywhere gives the bits of one call.  carry [M][4] fp64 + count [M] long long hold
+ * the state across calls IN DEVICE MEMORY (zero both to start a stream; the kernel advances them, so a captured graph replays it);
+ * NULL for both: whole utterances starting at frame 0.  The backward has no chunked form.
+ *   ctn_cumln_fwd: the norm as passes of its own (per-frame sums in fp64 -> scan -> apply: three tensor passes); any alignment and
+ *       any Kp (16-byte accesses when the rows allow).  work: ctn_cumln_work_bytes(M, Kp) bytes, 16-byte aligned.
+ *   ctn_cumln_bwd: dY = cumLN/PReLU backward of dOut (sums + parameter partials -> suffix scans -> apply: five tensor passes).
+ *       Frames k >= K of dOut may hold anything; those of dY are written as zeros.  dY may alias dOut.  pc and dalpha_part
+ *       (required with alpha) have ctn_cln_bwd's layout and sizes: finish them with ctn_cln_bwd_finalize. */
+int ctn_cumln_stats_frame(const double* col_part, int nparts, float* mean, float* rstd, double* carry, long long* count,
+                          int M, int Ch, int K, int Kp, void* stream);
+int ctn_cumln_bwd_frame(const double* col_part, int nparts, const float* mean, const float* rstd, float* fc,
+                        int M, int Ch, int K, int Kp, void* stream);
+size_t ctn_cumln_work_bytes(int M, int Kp);
+int ctn_cumln_fwd(const float* Y, float* Out, float* mean, float* rstd, int M, int Ch, int K, int Kp,
+                  const float* gamma, const float* beta, const float* alpha, double* carry, long long* count,
+                  void* work, void* stream);
+int ctn_cumln_bwd(const float* dOut, const float* Y, float* dY, const float* mean, const float* rstd,
+                  int M, int Ch, int K, int Kp, const float* gamma, const float* alpha,
+                  float* dalpha_part, float* pc, void* work, void* stream);
+
 /* ---- BatchNorm1d over (utterances, frames) per channel, optionally behind PReLU ------------------
  * replaces nn.BatchNorm1d as returned by chose_norm's else-branch, src/conv_tasnet.py:305-309, at its two uses
  * (:225 after PReLU :224, :260 after PReLU :259).  gamma/beta are nn.BatchNorm1d's weight/bias [Ch].
