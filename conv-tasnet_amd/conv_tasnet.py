@@ -282,19 +282,28 @@ def _pad_zero_tail(t, K):
     return t
 
 
+def _frame_norm_forward(norm, ctx, y, gamma, beta, K):
+    """A stand-alone norm per frame, `norm` = ops.NORM_CLN | ops.NORM_CUMLN (no PReLU in front)."""
+    out, mean, rstd = norm.fwd(y, gamma, beta, None, K)
+    ctx.save_for_backward(y, mean, rstd, gamma)
+    ctx.K = K
+    return out
+
+
+def _frame_norm_backward(norm, ctx, dout):
+    y, mean, rstd, gamma = ctx.saved_tensors
+    dy, dg, db, _ = norm.bwd(dout.contiguous(), y, mean, rstd, gamma, None, ctx.K)
+    return dy, dg.view_as(gamma), db.view_as(gamma), None
+
+
 class _ClnOnly(torch.autograd.Function):
     @staticmethod
     def forward(ctx, y, gamma, beta, K):
-        out, mean, rstd = ops.cln_fwd(y, gamma, beta, None, K)
-        ctx.save_for_backward(y, mean, rstd, gamma)
-        ctx.K = K
-        return out
+        return _frame_norm_forward(ops.NORM_CLN, ctx, y, gamma, beta, K)
 
     @staticmethod
     def backward(ctx, dout):
-        y, mean, rstd, gamma = ctx.saved_tensors
-        dy, dg, db, _ = ops.cln_bwd(dout.contiguous(), y, mean, rstd, gamma, None, ctx.K)
-        return dy, dg.view_as(gamma), db.view_as(gamma), None
+        return _frame_norm_backward(ops.NORM_CLN, ctx, dout)
 
 
 class TemporalBlock(nn.Module):
@@ -318,16 +327,13 @@ class TemporalBlock(nn.Module):
         return (self.net[0].weight, self.net[1].weight, norm1.gamma, norm1.beta, ds.net[0].weight, ds.prelu().weight,
                 norm2.gamma, norm2.beta, ds.pointwise().weight)
 
+    _NODES = {"gLN": ops.GlnBlock, "cLN": ops.ClnBlock, "cumLN": ops.CumLnBlock}      # every other norm_type: ops.BnBlock
+
     def fused(self, x, K):
         ds = self.net[3]
         norm1, norm2 = self.net[2], ds.norm()
-        if self.norm_type == "gLN":
-            fn = ops.GlnBlock
-        elif self.norm_type == "cLN":
-            fn = ops.ClnBlock
-        elif self.norm_type == "cumLN":
-            fn = ops.CumLnBlock
-        else:       # chose_norm's else-branch: BatchNorm1d (src/conv_tasnet.py:305-309)
+        fn = self._NODES.get(self.norm_type)
+        if fn is None:      # chose_norm's else-branch: BatchNorm1d (src/conv_tasnet.py:305-309)
             return ops.BnBlock.apply(x, self.net[0].weight, self.net[1].weight, norm1.weight, norm1.bias,
                                      ds.net[0].weight, ds.prelu().weight, norm2.weight, norm2.bias,
                                      ds.pointwise().weight, K, self.dilation, self.causal,
@@ -457,17 +463,11 @@ class ChannelwiseLayerNorm(_NormParams):
 class _CumLnOnly(torch.autograd.Function):
     @staticmethod
     def forward(ctx, y, gamma, beta, K):
-        y = y.contiguous()
-        out, mean, rstd = ops.cumln_fwd(y, gamma, beta, None, K)
-        ctx.save_for_backward(y, mean, rstd, gamma)
-        ctx.K = K
-        return out
+        return _frame_norm_forward(ops.NORM_CUMLN, ctx, y.contiguous(), gamma, beta, K)
 
     @staticmethod
     def backward(ctx, dout):
-        y, mean, rstd, gamma = ctx.saved_tensors
-        dy, dg, db, _ = ops.cumln_bwd(dout.contiguous(), y, mean, rstd, gamma, None, ctx.K)
-        return dy, dg.view_as(gamma), db.view_as(gamma), None
+        return _frame_norm_backward(ops.NORM_CUMLN, ctx, dout)
 
 
 class CumulativeLayerNorm(_NormParams):

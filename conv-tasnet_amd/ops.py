@@ -10,10 +10,10 @@ autograd node:
 
   Frontend : encoder conv + ReLU -> input cLN -> bottleneck 1x1   (src/conv_tasnet.py:108-121,172-174)
   GlnBlock : TemporalBlock with gLN, fully fused                  (src/conv_tasnet.py:218-278)
-  ClnBlock : TemporalBlock with cLN (causal variant)              (same, norm_type='cLN'; the first norm's forward and the second
-             norm's backward ride in the neighbouring GEMM epilogues / depthwise kernels: ctn_tune("cln_fuse"), include/ctn_hip.h)
-  CumLnBlock: TemporalBlock with the cumulative LayerNorm of the paper's causal model (norm_type='cumLN'; ClnBlock's fused chain
-             with the per-frame statistics / backward constants from prefix and suffix scans, csrc/ctn_cumln.hip)
+  ClnBlock, CumLnBlock : TemporalBlock with a norm per frame -- cLN (causal variant; same, norm_type='cLN') or the cumulative LayerNorm
+             of the paper's causal model (norm_type='cumLN', csrc/ctn_cumln.hip).  ONE node (_frame_block_forward / _backward) over
+             a _FrameNorm record of the four calls that differ; the first norm's forward and the second norm's backward ride in the
+             neighbouring GEMM epilogues / depthwise kernels (cLN: by ctn_tune("cln_fuse"), include/ctn_hip.h; cumLN: always)
   Backend  : mask 1x1 -> relu|softmax -> mask*w -> basis -> OLA   (src/conv_tasnet.py:191,206-215,131-146)
   SiSnrPit : PIT SI-SNR loss                                      (src/pit_criterion.py:12-77)
 """
@@ -313,11 +313,22 @@ def pw_gemm_cln(W, X, R, Cn, K, alpha, x_amax=None):
     return out, part
 
 
+def _mean_rstd(M, Kp, dev):
+    """(mean, rstd) [M, Kp] of a norm per frame, to be filled by a kernel."""
+    return torch.empty((M, Kp), dtype=F32, device=dev), torch.empty((M, Kp), dtype=F32, device=dev)
+
+
+def _frame_consts(col_part, mean, rstd):
+    """fc [M, 4, Kp]: the four per-frame constants with which ctn_dw_bwd_cln applies a norm's backward (operands checked)."""
+    _chk(mean, rstd)
+    _chk_aux(col_part)
+    return torch.empty((col_part.shape[0], 4, col_part.shape[2]), dtype=F32, device=mean.device)
+
+
 def cln_stats_frame(col_part, Ch):
     """ctn_cln_stats_frame: (mean, rstd) [M, Kp] of a channel-wise LayerNorm from ctn_pw_gemm_cln's column partials."""
     M, nparts, Kp, _ = col_part.shape
-    mean = torch.empty((M, Kp), dtype=F32, device=col_part.device)
-    rstd = torch.empty((M, Kp), dtype=F32, device=col_part.device)
+    mean, rstd = _mean_rstd(M, Kp, col_part.device)
     _chk_aux(col_part)
     lib.call("ctn_cln_stats_frame", _p(col_part), nparts, _p(mean), _p(rstd), M, Ch, Kp, _stream())
     return mean, rstd
@@ -336,9 +347,7 @@ def dw_fwd_cln(Y, D, K, dilation, causal, mean, rstd, gamma, beta, alpha):
 def cln_bwd_frame(col_part, mean, rstd, Ch):
     """ctn_cln_bwd_frame: fc [M, 4, Kp] = (rstd, mean rstd, rstd S1/Ch, rstd S2/Ch) per frame from ctn_pw_dgrad_cln's partials."""
     M, nparts, Kp, _ = col_part.shape
-    fc = torch.empty((M, 4, Kp), dtype=F32, device=mean.device)
-    _chk(mean, rstd)
-    _chk_aux(col_part)
+    fc = _frame_consts(col_part, mean, rstd)
     lib.call("ctn_cln_bwd_frame", _p(col_part), nparts, _p(mean), _p(rstd), _p(fc), M, Ch, Kp, _stream())
     return fc
 
@@ -476,97 +485,32 @@ def reduce_mid(x, F, Mid, Inner, out=None):
     return out
 
 
+def _norm_out(Y):
+    """(out, mean [M,Kp], rstd [M,Kp]) of a norm per frame over Y [M,Ch,Kp], to be filled by a kernel."""
+    return (torch.empty_like(Y),) + _mean_rstd(Y.shape[0], Y.shape[2], Y.device)
+
+
 def cln_fwd(Y, gamma, beta, alpha, K):
     M, Ch, Kp = Y.shape
-    out = torch.empty_like(Y)
-    mean = torch.empty((M, Kp), dtype=F32, device=Y.device)
-    rstd = torch.empty((M, Kp), dtype=F32, device=Y.device)
+    out, mean, rstd = _norm_out(Y)
     _chk(Y, gamma, beta, alpha)
     lib.call("ctn_cln_fwd", _p(Y), _p(out), _p(mean), _p(rstd), M, Ch, K, Kp, _p(gamma), _p(beta), _p(alpha), 0, _stream())
     return out, mean, rstd
 
 
-def cln_bwd(dOut, Y, mean, rstd, gamma, alpha, K, add=None, relu_ref=None, sinks=None):
-    """-> dY, dgamma[Ch], dbeta[Ch], dalpha[1]|None.  sinks = (dgamma, dbeta, dalpha) destinations (a flat
-    optimiser's gradient views): the fixed-order finishing reductions then write there directly and None is returned for them."""
-    M, Ch, Kp = Y.shape
-    dY = torch.empty_like(Y)
-    pc = torch.empty((lib.ctn_cln_bwd_pc_floats(M, Ch, Kp),), dtype=F32, device=Y.device)
-    dap = None
-    if alpha is not None:
-        dap = torch.empty((lib.ctn_cln_bwd_blocks(M, Kp),), dtype=F32, device=Y.device)
-    _chk(dOut, Y, mean, rstd, gamma, alpha, add, relu_ref)
-    lib.call("ctn_cln_bwd", _p(dOut), _p(Y), _p(dY), _p(mean), _p(rstd), M, Ch, K, Kp, _p(gamma), _p(alpha),
-             _p(add), _p(relu_ref), _p(dap), _p(pc), 0, _stream())
-    if sinks is not None:
-        dg, db, da = sinks
-    else:
-        dg = torch.empty((Ch,), dtype=F32, device=Y.device)
-        db = torch.empty((Ch,), dtype=F32, device=Y.device)
-        da = None if dap is None else torch.empty((1,), dtype=F32, device=Y.device)
-    _chk(dg, db, da)
-    lib.call("ctn_cln_bwd_finalize", _p(pc), _p(dap), M, Ch, Kp, _p(dg), _p(db), _p(da if dap is not None else None),
-             _stream())
-    if sinks is not None:
-        return dY, None, None, None
-    return dY, dg, db, da
-
-
-# ---- cumulative LayerNorm (csrc/ctn_cumln.hip): frame k normalised by the statistics of frames 0..k ----
-def cumln_state(M, device):
-    """(carry [M,4] f64, count [M] i64), zeroed: the device-side record that carries a cumulative norm's prefix sums from one chunk
-    of a stream to the next (cumln_fwd / cumln_stats_frame advance it in place; zero it to start a new stream)."""
-    return (torch.zeros((M, 4), dtype=F64, device=device), torch.zeros((M,), dtype=torch.int64, device=device))
-
-
-def cumln_stats_frame(col_part, Ch, K, state=None):
-    """ctn_cumln_stats_frame: cumulative (mean, rstd) [M, Kp] from ctn_pw_gemm_cln's column partials.  state: cumln_state() or None."""
-    M, nparts, Kp, _ = col_part.shape
-    mean = torch.empty((M, Kp), dtype=F32, device=col_part.device)
-    rstd = torch.empty((M, Kp), dtype=F32, device=col_part.device)
-    carry, count = state or (None, None)
-    _chk_aux(col_part, carry, count)
-    lib.call("ctn_cumln_stats_frame", _p(col_part), nparts, _p(mean), _p(rstd), _p(carry), _p(count), M, Ch, K, Kp, _stream())
-    return mean, rstd
-
-
-def cumln_bwd_frame(col_part, mean, rstd, Ch, K):
-    """ctn_cumln_bwd_frame: fc [M, 4, Kp] = (rstd, mean rstd, U - W + mean V, V / rstd) per frame (suffix sums over the valid frames)
-    from ctn_pw_dgrad_cln's partials: what ctn_dw_bwd_cln needs to apply a cumulative norm's backward."""
-    M, nparts, Kp, _ = col_part.shape
-    fc = torch.empty((M, 4, Kp), dtype=F32, device=mean.device)
-    _chk(mean, rstd)
-    _chk_aux(col_part)
-    lib.call("ctn_cumln_bwd_frame", _p(col_part), nparts, _p(mean), _p(rstd), _p(fc), M, Ch, K, Kp, _stream())
-    return fc
-
-
-def cumln_fwd(Y, gamma, beta, alpha, K, state=None):
-    """ctn_cumln_fwd -> (out, mean [M,Kp], rstd [M,Kp]).  state: cumln_state() of a stream (advanced in place) or None."""
-    M, Ch, Kp = Y.shape
-    out = torch.empty_like(Y)
-    mean = torch.empty((M, Kp), dtype=F32, device=Y.device)
-    rstd = torch.empty((M, Kp), dtype=F32, device=Y.device)
-    work = torch.empty((lib.ctn_cumln_work_bytes(M, Kp),), dtype=torch.uint8, device=Y.device)
-    carry, count = state or (None, None)
-    _chk(Y, gamma, beta, alpha)
-    _chk_aux(carry, count)
-    lib.call("ctn_cumln_fwd", _p(Y), _p(out), _p(mean), _p(rstd), M, Ch, K, Kp, _p(gamma), _p(beta), _p(alpha), _p(carry), _p(count),
-             _p(work), _stream())
-    return out, mean, rstd
-
-
-def cumln_bwd(dOut, Y, mean, rstd, gamma, alpha, K, sinks=None):
-    """ctn_cumln_bwd + ctn_cln_bwd_finalize -> dY, dgamma[Ch], dbeta[Ch], dalpha[1]|None; sinks as for cln_bwd."""
+def _norm_bwd(entry, dOut, Y, mean, rstd, gamma, alpha, K, sinks, mid, tail):
+    """What the backward passes of both norms per frame do around their entry point (`entry`, whose arguments between alpha and the
+    partials are `mid` and after them `tail`): dY, the partials pc / dap sized by the library, then the fixed-order finishing
+    reductions of ctn_cln_bwd_finalize into sinks = (dgamma, dbeta, dalpha) (-> dY, None, None, None) or into fresh tensors
+    (-> dY, dgamma[Ch], dbeta[Ch], dalpha[1]|None)."""
     M, Ch, Kp = Y.shape
     dev = Y.device
     dY = torch.empty_like(Y)
     pc = torch.empty((lib.ctn_cln_bwd_pc_floats(M, Ch, Kp),), dtype=F32, device=dev)
     dap = None if alpha is None else torch.empty((lib.ctn_cln_bwd_blocks(M, Kp),), dtype=F32, device=dev)
-    work = torch.empty((lib.ctn_cumln_work_bytes(M, Kp),), dtype=torch.uint8, device=dev)
     _chk(dOut, Y, mean, rstd, gamma, alpha)
-    lib.call("ctn_cumln_bwd", _p(dOut), _p(Y), _p(dY), _p(mean), _p(rstd), M, Ch, K, Kp, _p(gamma), _p(alpha), _p(dap), _p(pc),
-             _p(work), _stream())
+    lib.call(entry, _p(dOut), _p(Y), _p(dY), _p(mean), _p(rstd), M, Ch, K, Kp, _p(gamma), _p(alpha), *mid, _p(dap), _p(pc), *tail,
+             _stream())
     if sinks is not None:
         dg, db, da = sinks
     else:
@@ -580,6 +524,70 @@ def cumln_bwd(dOut, Y, mean, rstd, gamma, alpha, K, sinks=None):
     return dY, dg, db, da
 
 
+def cln_bwd(dOut, Y, mean, rstd, gamma, alpha, K, add=None, relu_ref=None, sinks=None):
+    """-> dY, dgamma[Ch], dbeta[Ch], dalpha[1]|None.  sinks = (dgamma, dbeta, dalpha) destinations (a flat
+    optimiser's gradient views): the fixed-order finishing reductions then write there directly and None is returned for them."""
+    _chk(add, relu_ref)
+    return _norm_bwd("ctn_cln_bwd", dOut, Y, mean, rstd, gamma, alpha, K, sinks, (_p(add), _p(relu_ref)), (0,))
+
+
+# ---- cumulative LayerNorm (csrc/ctn_cumln.hip): frame k normalised by the statistics of frames 0..k ----
+def cumln_state(M, device):
+    """(carry [M,4] f64, count [M] i64), zeroed: the device-side record that carries a cumulative norm's prefix sums from one chunk
+    of a stream to the next (cumln_fwd / cumln_stats_frame advance it in place; zero it to start a new stream)."""
+    return (torch.zeros((M, 4), dtype=F64, device=device), torch.zeros((M,), dtype=torch.int64, device=device))
+
+
+def cumln_stats_frame(col_part, Ch, K, state=None):
+    """ctn_cumln_stats_frame: cumulative (mean, rstd) [M, Kp] from ctn_pw_gemm_cln's column partials.  state: cumln_state() or None."""
+    M, nparts, Kp, _ = col_part.shape
+    mean, rstd = _mean_rstd(M, Kp, col_part.device)
+    carry, count = state or (None, None)
+    _chk_aux(col_part, carry, count)
+    lib.call("ctn_cumln_stats_frame", _p(col_part), nparts, _p(mean), _p(rstd), _p(carry), _p(count), M, Ch, K, Kp, _stream())
+    return mean, rstd
+
+
+def cumln_bwd_frame(col_part, mean, rstd, Ch, K):
+    """ctn_cumln_bwd_frame: fc [M, 4, Kp] = (rstd, mean rstd, U - W + mean V, V / rstd) per frame (suffix sums over the valid frames)
+    from ctn_pw_dgrad_cln's partials: what ctn_dw_bwd_cln needs to apply a cumulative norm's backward."""
+    M, nparts, Kp, _ = col_part.shape
+    fc = _frame_consts(col_part, mean, rstd)
+    lib.call("ctn_cumln_bwd_frame", _p(col_part), nparts, _p(mean), _p(rstd), _p(fc), M, Ch, K, Kp, _stream())
+    return fc
+
+
+def cumln_fwd(Y, gamma, beta, alpha, K, state=None):
+    """ctn_cumln_fwd -> (out, mean [M,Kp], rstd [M,Kp]).  state: cumln_state() of a stream (advanced in place) or None."""
+    M, Ch, Kp = Y.shape
+    out, mean, rstd = _norm_out(Y)
+    work = torch.empty((lib.ctn_cumln_work_bytes(M, Kp),), dtype=torch.uint8, device=Y.device)
+    carry, count = state or (None, None)
+    _chk(Y, gamma, beta, alpha)
+    _chk_aux(carry, count)
+    lib.call("ctn_cumln_fwd", _p(Y), _p(out), _p(mean), _p(rstd), M, Ch, K, Kp, _p(gamma), _p(beta), _p(alpha), _p(carry), _p(count),
+             _p(work), _stream())
+    return out, mean, rstd
+
+
+def cumln_bwd(dOut, Y, mean, rstd, gamma, alpha, K, sinks=None):
+    """ctn_cumln_bwd + ctn_cln_bwd_finalize -> dY, dgamma[Ch], dbeta[Ch], dalpha[1]|None; sinks as for cln_bwd."""
+    work = torch.empty((lib.ctn_cumln_work_bytes(Y.shape[0], Y.shape[2]),), dtype=torch.uint8, device=Y.device)
+    return _norm_bwd("ctn_cumln_bwd", dOut, Y, mean, rstd, gamma, alpha, K, sinks, (), (_p(work),))
+
+
+# ---- the two norms per frame as the block node (_frame_block_forward / _backward) and conv_tasnet's stand-alone norm modules see
+# them.  Per frame a cumulative norm is the channel-wise norm's affine form with other constants, so the four calls listed here are
+# all that differs: stats_frame(col_part, Ch, K) -> (mean, rstd): the first norm's statistics from ctn_pw_gemm_cln's column partials;
+# bwd_frame(col_part, mean, rstd, Ch, K) -> fc: the second norm's backward constants from ctn_pw_dgrad_cln's; fwd(Y, gamma, beta,
+# alpha, K) and bwd(dOut, Y, mean, rstd, gamma, alpha, K, sinks=): the norm passes.  fused: the block runs the fused chain whatever
+# ctn_tune("cln_fuse") says (the cumulative norm has no other; there is no composite stack for it either).
+_FrameNorm = collections.namedtuple("_FrameNorm", "name stats_frame bwd_frame fwd bwd fused")
+NORM_CLN = _FrameNorm("cLN", lambda col_part, Ch, K: cln_stats_frame(col_part, Ch),
+                      lambda col_part, mean, rstd, Ch, K: cln_bwd_frame(col_part, mean, rstd, Ch), cln_fwd, cln_bwd, False)
+NORM_CUMLN = _FrameNorm("cumLN", cumln_stats_frame, cumln_bwd_frame, cumln_fwd, cumln_bwd, True)
+
+
 def dw_fwd(Y, D, K, dilation, causal, pro=None, epi_alpha=None, ms_out=None):
     M, H, Kp = Y.shape
     P = D.shape[-1]
@@ -590,6 +598,19 @@ def dw_fwd(Y, D, K, dilation, causal, pro=None, epi_alpha=None, ms_out=None):
     lib.call("ctn_dw_fwd", _p(Y), _p(Z), _p(D), M, H, K, Kp, P, dilation, int(causal),
              _p(pp), npart, _p(pg), _p(pb), _p(pa), _p(ms_out), _p(epi_alpha), _p(epi_part), 0, _stream())
     return Z, epi_part
+
+
+def dw_bwd_plain(dd, n1, D, K, dilation, causal):
+    """ctn_dw_bwd without a norm folded in (no prologue, no statistics) + the fixed-order sum of its per-utterance partials:
+    -> dn1 [M,H,Kp], dD [H,1,P] from the gradient dd at the depthwise output and the depthwise input n1."""
+    M, H, Kp = n1.shape
+    P = D.shape[-1]
+    pc = torch.empty((P, M, H), dtype=F32, device=n1.device)
+    dn1 = torch.empty((M, H, Kp), dtype=F32, device=n1.device)
+    _chk(dd, n1)
+    lib.call("ctn_dw_bwd", _p(dd), 0, _p(n1), _p(dn1), _p(D), M, H, K, Kp, P, dilation, int(causal), 0,
+             0, 0, 0, 0, 0, 0, 0, 0, 0, _p(pc), 0, _stream())
+    return dn1, reduce_mid(pc, P, M, H).t().contiguous().view(H, 1, P)
 
 
 # ---------------------------------------------------------------------------------------
@@ -656,9 +677,19 @@ class Frontend(torch.autograd.Function):
 
 
 # ---------------------------------------------------------------------------------------
-# What GlnBlock and ClnBlock share: which GEMM / weight-gradient entry point runs, where, and in which order (the composite stacks'
-# rules, kernel by kernel)
+# What the block nodes share: the checks, the gradient sinks, and which GEMM / weight-gradient entry point runs, where, and in which
+# order (the composite stacks' rules, kernel by kernel)
 # ---------------------------------------------------------------------------------------
+def _check_block_dims(B, H):
+    if H % 4 or B % 4:
+        raise ValueError("HIP path needs B and H to be multiples of 4")
+
+
+def _block_sinks(w1, a1, g1, b1, D, a2, g2, b2, w2):
+    """The gradient sinks of a block's nine parameters (NPARAM order), None where none is registered."""
+    return (_sink(w1), _sink(a1), _sink(g1), _sink(b1), _sink(D), _sink(a2), _sink(g2), _sink(b2), _sink(w2))
+
+
 def _gemm(W, X, R, Cn, K, amax, k_major=False, gb=None, **kw):
     """Out = op(W) . f(X): on h3 pieces when X's tracked maximum `amax` is passed (gb = the prologue's (gamma, beta), whose maxima the
     kernel needs), through pw_gemm otherwise.  k_major: W is stored [Cn, R].  kw: pro, residual, epi_alpha, ms_out."""
@@ -702,8 +733,7 @@ class GlnBlock(torch.autograd.Function):
         x = _c(x)
         M, B, Kp = x.shape
         H = w1.shape[0]
-        if H % 4 or B % 4:
-            raise ValueError("HIP path needs B and H to be multiples of 4")
+        _check_block_dims(B, H)
         dev = x.device
         ms1 = torch.empty((M, 2), dtype=F32, device=dev)
         ms2 = torch.empty((M, 2), dtype=F32, device=dev)
@@ -718,7 +748,7 @@ class GlnBlock(torch.autograd.Function):
         ctx.h3 = (ax, ad) if h3 else None
         ctx.save_for_backward(x, h1, d, ms1, ms2, w1, a1, g1, b1, D, a2, g2, b2, w2)
         ctx.cfg = (K, dilation, causal)
-        ctx.sinks = tuple(_sink(p) for p in (w1, a1, g1, b1, D, a2, g2, b2, w2))
+        ctx.sinks = _block_sinks(w1, a1, g1, b1, D, a2, g2, b2, w2)
         return out
 
     @staticmethod
@@ -882,8 +912,8 @@ def _stack_forward(S, ctx, x0, K, dilations, causal, params):
         x0 = _c(x0)
     M, B, Kp = x0.shape
     H, P = params[0].shape[0], params[4].shape[-1]
-    if save and (H % 4 or B % 4):
-        raise ValueError("HIP path needs B and H to be multiples of 4")
+    if save:
+        _check_block_dims(B, H)
     dev = x0.device
     _chk(x0, *params)
     xs = torch.empty((nb if save else 2, M, B, Kp), dtype=F32, device=dev)
@@ -994,142 +1024,102 @@ def tcn_cln_infer(x0, K, dilations, causal, params):
 
 
 # ---------------------------------------------------------------------------------------
-# TemporalBlock, cLN (causal config): unfused norm kernels around the same GEMMs / depthwise
+# TemporalBlock with a norm per frame (causal configs), cLN or cumLN: one node over a _FrameNorm record
 # ---------------------------------------------------------------------------------------
+def _frame_block_forward(norm, ctx, x, w1, a1, g1, b1, D, a2, g2, b2, w2, K, dilation, causal):
+    """One TemporalBlock with `norm` (NORM_CLN | NORM_CUMLN) at both places; the GEMMs, the depthwise kernels, the weight gradients,
+    the h3 maxima and the gradient sinks do not depend on which."""
+    x = _c(x)
+    M, B, Kp = x.shape
+    H = w1.shape[0]
+    _check_block_dims(B, H)
+    h3 = _h3_block(B, H)       # the composite stack's arithmetic, kernel by kernel (maxima measured here: exact, so the same bits)
+    fuse1 = norm.fused or lib.ctn_cln_fuse() >= 2     # the first norm without a pass (the composite's rule): statistics from K1's epilogue, applied in K2's prologue
+    ax = absmax_rows(x) if h3 else None
+    if fuse1:
+        h1, colp = pw_gemm_cln(w1, x, H, B, K, a1, x_amax=ax)
+        mean1, rstd1 = norm.stats_frame(colp, H, K)
+        d = dw_fwd_cln(h1, D, K, dilation, causal, mean1, rstd1, g1, b1, a1)
+        n1 = None                               # never stored
+    else:
+        h1, _ = _gemm(w1, x, H, B, K, ax)
+        n1, mean1, rstd1 = norm.fwd(h1, g1, b1, a1, K)
+        d, _ = dw_fwd(n1, D, K, dilation, causal)
+    n2, mean2, rstd2 = norm.fwd(d, g2, b2, a2, K)
+    an = absmax_rows(n2) if h3 else None
+    out, _ = _gemm(w2, n2, B, H, K, an, residual=x)
+    ctx.h3 = (ax, an) if h3 else None
+    ctx.save_for_backward(x, h1, n1, d, n2, mean1, rstd1, mean2, rstd2, w1, a1, g1, D, a2, g2, w2, b1)
+    ctx.cfg = (K, dilation, causal)
+    ctx.fuse1 = fuse1
+    ctx.sinks = _block_sinks(w1, a1, g1, b1, D, a2, g2, b2, w2)
+    return out
+
+
+def _frame_block_backward(norm, ctx, dout):
+    x, h1, n1, d, n2, mean1, rstd1, mean2, rstd2, w1, a1, g1, D, a2, g2, w2, b1 = ctx.saved_tensors
+    K, dilation, causal = ctx.cfg
+    dout = _c(dout)
+    B, H = x.shape[1], w1.shape[0]
+    sk = ctx.sinks
+    direct = all(t is not None for t in sk)       # flat optimiser: gradients go straight into the flat buffer
+    if direct:
+        _claim_sinks(w1)
+    # Weight gradients on the second stream: with the round-1 weight-gradient kernel this lost (22.7 vs 22.3 ms/step: the
+    # 1024-thread cLN kernels fill every wave slot); with the w4 kernel and the 5 us slab reduce it wins, 20.07 vs
+    # 21.7 ms/step at paper size (CONFIG=causal benchmarks/ab_step.py).  CTN_CLN_SIDE=0 turns it off.
+    side = direct and _SIDE_ENABLED and _CLN_SIDE
+    ax, an = ctx.h3 or (None, None)                 # h3 arithmetic: the operand maxima the forward pass measured
+    h3 = ax is not None
+    # the second norm's backward inside the GEMM epilogue + the depthwise backward (the composite's rule)
+    fuse = norm.fused or lib.ctn_cln_fuse() != 0 or ctx.fuse1
+    ady = absmax_rows(dout) if h3 else None
+    if fuse:
+        dn2, colp = pw_dgrad_cln(w2, dout, H, B, K, d, g2, a2, mean2, rstd2, g_amax=ady)
+    else:
+        dn2, _ = _gemm(w2, dout, H, B, K, ady, k_major=True)
+    dW2 = _wgrad(side, direct, dout, n2, B, H, K, sk[8], h3=(ady, an, None) if h3 else None)
+    if fuse:
+        fc = norm.bwd_frame(colp, mean2, rstd2, H, K)
+        dn1, dD, dg2, db2, da2 = dw_bwd_cln(dn2, d, h1 if ctx.fuse1 else n1, D, K, dilation, causal, g2, a2, fc,
+                                            sinks=(sk[4], sk[6], sk[7], sk[5]) if direct else None,
+                                            norm1=(g1, b1, a1, mean1, rstd1) if ctx.fuse1 else None)
+    else:
+        dd, dg2, db2, da2 = norm.bwd(dn2, d, mean2, rstd2, g2, a2, K, sinks=(sk[6], sk[7], sk[5]) if direct else None)
+        dn1, dD = dw_bwd_plain(dd, n1, D, K, dilation, causal)
+    dh1, dg1, db1, da1 = norm.bwd(dn1, h1, mean1, rstd1, g1, a1, K, sinks=(sk[2], sk[3], sk[1]) if direct else None)
+    dx, dW1 = _first_conv_bwd(side, direct, w1, dh1, x, dout, K, sk[0], ax)
+    if direct:
+        if not fuse:
+            sk[4].copy_(dD)
+        return (dx,) + (None,) * 12
+    return (dx, dW1.view(H, B, 1), da1, dg1.view(1, H, 1), db1.view(1, H, 1), dD, da2, dg2.view(1, H, 1),
+            db2.view(1, H, 1), dW2.view(B, H, 1), None, None, None)
+
+
 class ClnBlock(torch.autograd.Function):
+    """TemporalBlock with cLN (norm_type="cLN"): ctn_tune("cln_fuse") decides which of the two norms have passes of their own."""
+
     @staticmethod
     def forward(ctx, x, w1, a1, g1, b1, D, a2, g2, b2, w2, K, dilation, causal):
-        x = _c(x)
-        M, B, Kp = x.shape
-        H = w1.shape[0]
-        if H % 4 or B % 4:
-            raise ValueError("HIP path needs B and H to be multiples of 4")
-        h3 = _h3_block(B, H)       # the composite stack's arithmetic, kernel by kernel (maxima measured here: exact, so the same bits)
-        fuse1 = lib.ctn_cln_fuse() >= 2     # the first norm without a pass (the composite's rule): statistics from K1's epilogue, applied in K2's prologue
-        ax = absmax_rows(x) if h3 else None
-        if fuse1:
-            h1, colp = pw_gemm_cln(w1, x, H, B, K, a1, x_amax=ax)
-            mean1, rstd1 = cln_stats_frame(colp, H)
-            d = dw_fwd_cln(h1, D, K, dilation, causal, mean1, rstd1, g1, b1, a1)
-            n1 = h1.new_empty(0)                    # never stored
-        else:
-            h1, _ = _gemm(w1, x, H, B, K, ax)
-            n1, mean1, rstd1 = cln_fwd(h1, g1, b1, a1, K)
-            d, _ = dw_fwd(n1, D, K, dilation, causal)
-        n2, mean2, rstd2 = cln_fwd(d, g2, b2, a2, K)
-        an = absmax_rows(n2) if h3 else None
-        out, _ = _gemm(w2, n2, B, H, K, an, residual=x)
-        ctx.h3 = (ax, an) if h3 else None
-        ctx.save_for_backward(x, h1, n1, d, n2, mean1, rstd1, mean2, rstd2, w1, a1, g1, D, a2, g2, w2, b1)
-        ctx.cfg = (K, dilation, causal)
-        ctx.fuse1 = fuse1
-        ctx.sinks = tuple(_sink(p) for p in (w1, a1, g1, b1, D, a2, g2, b2, w2))
-        return out
+        return _frame_block_forward(NORM_CLN, ctx, x, w1, a1, g1, b1, D, a2, g2, b2, w2, K, dilation, causal)
 
     @staticmethod
     def backward(ctx, dout):
-        x, h1, n1, d, n2, mean1, rstd1, mean2, rstd2, w1, a1, g1, D, a2, g2, w2, b1 = ctx.saved_tensors
-        K, dilation, causal = ctx.cfg
-        dout = _c(dout)
-        M, B, Kp = x.shape
-        H = w1.shape[0]
-        P = D.shape[-1]
-        dev = x.device
-        sk = ctx.sinks
-        direct = all(t is not None for t in sk)       # flat optimiser: gradients go straight into the flat buffer
-        if direct:
-            _claim_sinks(w1)
-        # Weight gradients on the second stream: with the round-1 weight-gradient kernel this lost (22.7 vs 22.3 ms/step: the
-        # 1024-thread cLN kernels fill every wave slot); with the w4 kernel and the 5 us slab reduce it wins, 20.07 vs
-        # 21.7 ms/step at paper size (CONFIG=causal benchmarks/ab_step.py).  CTN_CLN_SIDE=0 turns it off.
-        side = direct and _SIDE_ENABLED and _CLN_SIDE
-        ax, an = ctx.h3 or (None, None)                 # h3 arithmetic: the operand maxima the forward pass measured
-        h3 = ax is not None
-        fuse = lib.ctn_cln_fuse() != 0 or ctx.fuse1     # the second norm's backward inside the GEMM epilogue + the depthwise backward (the composite's rule)
-        ady = absmax_rows(dout) if h3 else None
-        if fuse:
-            dn2, colp = pw_dgrad_cln(w2, dout, H, B, K, d, g2, a2, mean2, rstd2, g_amax=ady)
-        else:
-            dn2, _ = _gemm(w2, dout, H, B, K, ady, k_major=True)
-        dW2 = _wgrad(side, direct, dout, n2, B, H, K, sk[8], h3=(ady, an, None) if h3 else None)
-        if fuse:
-            fc = cln_bwd_frame(colp, mean2, rstd2, H)
-            dn1, dD, dg2, db2, da2 = dw_bwd_cln(dn2, d, h1 if ctx.fuse1 else n1, D, K, dilation, causal, g2, a2, fc,
-                                                sinks=(sk[4], sk[6], sk[7], sk[5]) if direct else None,
-                                                norm1=(g1, b1, a1, mean1, rstd1) if ctx.fuse1 else None)
-        else:
-            dd, dg2, db2, da2 = cln_bwd(dn2, d, mean2, rstd2, g2, a2, K, sinks=(sk[6], sk[7], sk[5]) if direct else None)
-            pc = torch.empty((P, M, H), dtype=F32, device=dev)
-            dn1 = torch.empty((M, H, Kp), dtype=F32, device=dev)
-            _chk(dd, n1)
-            lib.call("ctn_dw_bwd", _p(dd), 0, _p(n1), _p(dn1), _p(D), M, H, K, Kp, P, dilation, int(causal), 0,
-                     0, 0, 0, 0, 0, 0, 0, 0, 0, _p(pc), 0, _stream())
-            dD = reduce_mid(pc, P, M, H).t().contiguous().view(H, 1, P)
-        dh1, dg1, db1, da1 = cln_bwd(dn1, h1, mean1, rstd1, g1, a1, K, sinks=(sk[2], sk[3], sk[1]) if direct else None)
-        dx, dW1 = _first_conv_bwd(side, direct, w1, dh1, x, dout, K, sk[0], ax)
-        if direct:
-            if not fuse:
-                sk[4].copy_(dD)
-            return (dx,) + (None,) * 12
-        return (dx, dW1.view(H, B, 1), da1, dg1.view(1, H, 1), db1.view(1, H, 1), dD, da2, dg2.view(1, H, 1),
-                db2.view(1, H, 1), dW2.view(B, H, 1), None, None, None)
+        return _frame_block_backward(NORM_CLN, ctx, dout)
 
 
 class CumLnBlock(torch.autograd.Function):
-    """TemporalBlock with the cumulative LayerNorm (norm_type="cumLN", causal): ClnBlock's fused chain, always -- per frame a cumulative
-    norm is the channel-wise norm's affine form with other constants, so the GEMMs, ctn_dw_fwd_cln, ctn_pw_dgrad_cln, ctn_dw_bwd_cln,
-    the weight gradients, the h3 maxima and the gradient sinks are ClnBlock's, and four calls differ: the first norm's statistics and
-    the second norm's backward constants come from the scans (cumln_stats_frame, cumln_bwd_frame), and the two norms that have passes
-    of their own run cumln_fwd / cumln_bwd.  ctn_tune("cln_fuse") does not apply; there is no composite stack."""
+    """TemporalBlock with the cumulative LayerNorm (norm_type="cumLN", causal): the fused chain always, with the first norm's statistics
+    and the second norm's backward constants from the scans of csrc/ctn_cumln.hip; ctn_tune("cln_fuse") does not reach it."""
 
     @staticmethod
     def forward(ctx, x, w1, a1, g1, b1, D, a2, g2, b2, w2, K, dilation, causal):
-        x = _c(x)
-        M, B, Kp = x.shape
-        H = w1.shape[0]
-        if H % 4 or B % 4:
-            raise ValueError("HIP path needs B and H to be multiples of 4")
-        h3 = _h3_block(B, H)
-        ax = absmax_rows(x) if h3 else None
-        h1, colp = pw_gemm_cln(w1, x, H, B, K, a1, x_amax=ax)
-        mean1, rstd1 = cumln_stats_frame(colp, H, K)
-        d = dw_fwd_cln(h1, D, K, dilation, causal, mean1, rstd1, g1, b1, a1)
-        n2, mean2, rstd2 = cumln_fwd(d, g2, b2, a2, K)
-        an = absmax_rows(n2) if h3 else None
-        out, _ = _gemm(w2, n2, B, H, K, an, residual=x)
-        ctx.h3 = (ax, an) if h3 else None
-        ctx.save_for_backward(x, h1, d, n2, mean1, rstd1, mean2, rstd2, w1, a1, g1, D, a2, g2, w2, b1)
-        ctx.cfg = (K, dilation, causal)
-        ctx.sinks = tuple(_sink(p) for p in (w1, a1, g1, b1, D, a2, g2, b2, w2))
-        return out
+        return _frame_block_forward(NORM_CUMLN, ctx, x, w1, a1, g1, b1, D, a2, g2, b2, w2, K, dilation, causal)
 
     @staticmethod
     def backward(ctx, dout):
-        x, h1, d, n2, mean1, rstd1, mean2, rstd2, w1, a1, g1, D, a2, g2, w2, b1 = ctx.saved_tensors
-        K, dilation, causal = ctx.cfg
-        dout = _c(dout)
-        M, B, Kp = x.shape
-        H = w1.shape[0]
-        sk = ctx.sinks
-        direct = all(t is not None for t in sk)
-        if direct:
-            _claim_sinks(w1)
-        side = direct and _SIDE_ENABLED and _CLN_SIDE
-        ax, an = ctx.h3 or (None, None)
-        h3 = ax is not None
-        ady = absmax_rows(dout) if h3 else None
-        dn2, colp = pw_dgrad_cln(w2, dout, H, B, K, d, g2, a2, mean2, rstd2, g_amax=ady)
-        dW2 = _wgrad(side, direct, dout, n2, B, H, K, sk[8], h3=(ady, an, None) if h3 else None)
-        fc = cumln_bwd_frame(colp, mean2, rstd2, H, K)
-        dn1, dD, dg2, db2, da2 = dw_bwd_cln(dn2, d, h1, D, K, dilation, causal, g2, a2, fc,
-                                            sinks=(sk[4], sk[6], sk[7], sk[5]) if direct else None,
-                                            norm1=(g1, b1, a1, mean1, rstd1))
-        dh1, dg1, db1, da1 = cumln_bwd(dn1, h1, mean1, rstd1, g1, a1, K, sinks=(sk[2], sk[3], sk[1]) if direct else None)
-        dx, dW1 = _first_conv_bwd(side, direct, w1, dh1, x, dout, K, sk[0], ax)
-        if direct:
-            return (dx,) + (None,) * 12
-        return (dx, dW1.view(H, B, 1), da1, dg1.view(1, H, 1), db1.view(1, H, 1), dD, da2, dg2.view(1, H, 1),
-                db2.view(1, H, 1), dW2.view(B, H, 1), None, None, None)
+        return _frame_block_backward(NORM_CUMLN, ctx, dout)
 
 
 def bn_fwd(Y, alpha, weight, bias, running_mean, running_var, training, eps, momentum, K):
@@ -1170,8 +1160,7 @@ class BnBlock(torch.autograd.Function):
         x = _c(x)
         M, B, Kp = x.shape
         H = w1.shape[0]
-        if H % 4 or B % 4:
-            raise ValueError("HIP path needs B and H to be multiples of 4")
+        _check_block_dims(B, H)
         h1, _ = pw_gemm(w1, x, H, B, K)
         n1, mr1 = bn_fwd(h1, a1, g1, b1, bn1[0], bn1[1], bn1[2], bn1[3], bn1[4], K)
         d, _ = dw_fwd(n1, D, K, dilation, causal)
@@ -1179,7 +1168,7 @@ class BnBlock(torch.autograd.Function):
         out, _ = pw_gemm(w2, n2, B, H, K, residual=x)
         ctx.save_for_backward(x, h1, n1, d, n2, mr1, mr2, w1, a1, g1, D, a2, g2, w2)
         ctx.cfg = (K, dilation, causal, bool(bn1[2]), bool(bn2[2]))
-        ctx.sinks = tuple(_sink(p) for p in (w1, a1, g1, b1, D, a2, g2, b2, w2))
+        ctx.sinks = _block_sinks(w1, a1, g1, b1, D, a2, g2, b2, w2)
         return out
 
     @staticmethod
@@ -1187,19 +1176,11 @@ class BnBlock(torch.autograd.Function):
         x, h1, n1, d, n2, mr1, mr2, w1, a1, g1, D, a2, g2, w2 = ctx.saved_tensors
         K, dilation, causal, tr1, tr2 = ctx.cfg
         dout = _c(dout)
-        M, B, Kp = x.shape
-        H = w1.shape[0]
-        P = D.shape[-1]
-        dev = x.device
+        B, H = x.shape[1], w1.shape[0]
         dn2, _ = pw_gemm(w2, dout, H, B, K, trans_w=True)
         dW2 = pw_wgrad(dout, n2, B, H, K)
         dd, dg2, db2, da2 = bn_bwd(dn2, d, a2, g2, mr2, tr2, K)
-        pc = torch.empty((P, M, H), dtype=F32, device=dev)
-        dn1 = torch.empty((M, H, Kp), dtype=F32, device=dev)
-        _chk(dd, n1)
-        lib.call("ctn_dw_bwd", _p(dd), 0, _p(n1), _p(dn1), _p(D), M, H, K, Kp, P, dilation, int(causal), 0,
-                 0, 0, 0, 0, 0, 0, 0, 0, 0, _p(pc), 0, _stream())
-        dD = reduce_mid(pc, P, M, H).t().contiguous().view(H, 1, P)
+        dn1, dD = dw_bwd_plain(dd, n1, D, K, dilation, causal)
         dh1, dg1, db1, da1 = bn_bwd(dn1, h1, a1, g1, mr1, tr1, K)
         dx, _ = pw_gemm(w1, dh1, B, H, K, trans_w=True, residual=dout)
         dW1 = pw_wgrad(dh1, x, H, B, K)

@@ -14,6 +14,8 @@ it); the order of the prefix sums is fixed by the absolute frame index, so the s
 
 All arithmetic runs through the same HIP entry points as training (ops.py); torch only slices / concatenates.
 """
+import functools
+
 import torch
 
 from . import ops
@@ -68,6 +70,8 @@ class StreamingSeparator:
                     self.hist.append(torch.zeros((M, m.H, halo), device=dev))
             # cumLN: per norm the prefix sums and the frame count so far, on the device (the scan kernel advances them: graph replay)
             self.cum_state = [ops.cumln_state(M, dev) for _ in range(2 * len(self.hist))] if self.cum else []
+            # the norm pass of norm j (block i: 2i and 2i + 1): cln_fwd, or cumln_fwd bound to that norm's state
+            self.norms = [functools.partial(ops.cumln_fwd, state=st) for st in self.cum_state] or [ops.cln_fwd] * (2 * len(self.hist))
             self._graphs = {}            # chunk length -> (graph, static chunk, static output)
             self._seen = {}              # chunk length -> eager steady-state chunks so far
         else:
@@ -129,19 +133,13 @@ class StreamingSeparator:
                 ds = blk.net[3]
                 halo = (m.P - 1) * blk.dilation
                 h, _ = ops.pw_gemm(blk.net[0].weight, y, m.H, m.B, K)
-                if self.cum:
-                    n1, _, _ = ops.cumln_fwd(h, blk.net[2].gamma, blk.net[2].beta, blk.net[1].weight, K, self.cum_state[2 * i])
-                else:
-                    n1, _, _ = ops.cln_fwd(h, blk.net[2].gamma, blk.net[2].beta, blk.net[1].weight, K)
+                n1, _, _ = self.norms[2 * i](h, blk.net[2].gamma, blk.net[2].beta, blk.net[1].weight, K)
                 cat = torch.cat([self.hist[i], n1[..., :K]], dim=2)          # [M, H, halo + K]
                 self.hist[i].copy_(cat[..., cat.shape[2] - halo:])
                 Kc = halo + K
                 z, _ = ops.dw_fwd(_padded(cat, Kc), ds.net[0].weight, Kc, blk.dilation, True)
                 z = _padded(z[..., halo:Kc], K)
-                if self.cum:
-                    n2, _, _ = ops.cumln_fwd(z, ds.norm().gamma, ds.norm().beta, ds.prelu().weight, K, self.cum_state[2 * i + 1])
-                else:
-                    n2, _, _ = ops.cln_fwd(z, ds.norm().gamma, ds.norm().beta, ds.prelu().weight, K)
+                n2, _, _ = self.norms[2 * i + 1](z, ds.norm().gamma, ds.norm().beta, ds.prelu().weight, K)
                 y, _ = ops.pw_gemm(ds.pointwise().weight, n2, m.B, m.H, K, residual=y)
                 i += 1
         # mask -> decoder frames -> overlap-add with carry

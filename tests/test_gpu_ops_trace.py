@@ -5,12 +5,14 @@ tests (tests/test_gpu_train.py, tests/test_gpu_h3.py) pin WHAT is computed and i
 themselves: the name of every ``lib.call`` of one forward / loss / backward / join_side_stream(), in order, with every scalar
 argument (byte counts included), every pointer as null or non-null, every pointer table as its length, every integer table as
 its values, every ``bytes`` argument, and every ``stream`` / ``side_stream`` argument as "main", "side" or "null" (compared, at
-the time of the call, with ops._side_stream() and torch's current stream).  Addresses are not compared.
+the time of the call, with ops._side_stream() and torch's current stream).  Addresses are not compared.  The cases of
+``mode="stream"`` pin chunked inference the same way: the calls of a streaming.StreamingSeparator over two pushes and the flush.
 
 The fixture pins ONE machine: workspace sizes and partial counts follow the CU count, so it stores torch.version.hip, the device
 name and the CU count, and a run anywhere else FAILS with the instruction below (it does not skip).  To re-record, check out the
-parent of the commit under review (the fixture in the tree was recorded from the commit before ops.py's stack nodes and GEMM
-dispatch were merged into one routine each), build it, and run there
+parent of the commit under review (the fixture in the tree was recorded from the commit before ClnBlock and CumLnBlock became one
+node over a record of the norm's calls; its older cases expand to what the fixture before it held), build it, copy this module over
+its own, and run there
     python tests/test_gpu_ops_trace.py --record tests/golden/ops_call_trace.json
 never from a tree whose ops.py is the one under review.
 """
@@ -30,12 +32,13 @@ pytestmark = pytest.mark.gpu
 import conv_tasnet_amd as ctn  # noqa: E402
 from conv_tasnet_amd import ops  # noqa: E402
 from conv_tasnet_amd.optim import FlatAdam  # noqa: E402
+from conv_tasnet_amd.streaming import StreamingSeparator  # noqa: E402
 
 DEV = "cuda:0"
 FIXTURE = os.path.join(conftest.GOLDEN, "ops_call_trace.json")
 NARROW = (32, 20, 16, 32, 3, 4, 2, 2)
 WIDE = (64, 20, 64, 128, 3, 3, 2, 2)          # >= 64 rows everywhere: reaches the b6 / h3 piece forms
-NORMS = {"gln": ("gLN", False), "cln": ("cLN", True), "bn": ("BN", False)}
+NORMS = {"gln": ("gLN", False), "cln": ("cLN", True), "bn": ("BN", False), "cumln": ("cumLN", True)}
 BASE = dict(dims=WIDE, flat=True, arith="h3", cln_fuse=2, gln_fuse=0, side=True, buckets=False, no_grad=False)
 
 
@@ -61,6 +64,20 @@ def _cases():
         for level in (0, 1):
             add("gln_fuse%d" % level, "gln", composite, gln_fuse=level)
     add("narrow_sinks", "bn", False, dims=NARROW)
+    # cumLN has no composite stack: per kernel only; ctn_tune("cln_fuse") must not reach it
+    for dims, dname in ((NARROW, "narrow"), (WIDE, "wide")):
+        for flat in (True, False):
+            add("%s_%s" % (dname, "sinks" if flat else "autograd"), "cumln", False, dims=dims, flat=flat)
+    for arith in ("fp32", "b6", "h3"):
+        add("arith_" + arith, "cumln", False, arith=arith)
+    add("side_off", "cumln", False, side=False)
+    add("no_grad", "cumln", False, no_grad=True)
+    add("cln_fuse0", "cumln", False, cln_fuse=0)
+    add("wide_sinks", "bn", False)
+    add("narrow_autograd", "bn", False, dims=NARROW, flat=False)
+    # chunked inference: StreamingSeparator on the narrow model, eager
+    for norm in ("cln", "cumln"):
+        cases["%s_stream" % norm] = dict(BASE, norm=norm, composite=False, dims=NARROW, flat=False, mode="stream")
     return cases
 
 
@@ -128,8 +145,15 @@ def _trace(case, mp):
         if opt is not None:
             opt.zero_grad()
         torch.cuda.synchronize()
+        stream = case.get("mode") == "stream"
+        if stream:
+            sep, hop = StreamingSeparator(m, batch=2), case["dims"][1] // 2
         mp.setattr(ctn.lib, "call", recorder)
-        if case["no_grad"]:
+        if stream:                                  # a push of 40 hops, one of 7, the flush
+            sep.push(mix[:2, :40 * hop])
+            sep.push(mix[:2, 40 * hop:47 * hop])
+            sep.flush()
+        elif case["no_grad"]:
             with torch.no_grad():
                 m(mix)
         else:
