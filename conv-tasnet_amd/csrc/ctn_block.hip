@@ -20,7 +20,7 @@
 // ---- measurement hook (bench.py's roofline leg): HIP events around every launch group of the composite stacks, on the stream
 // the group is launched to.  Off by default (no events, no overhead); ctn_probe_enable(1) starts a recording, ctn_probe_read
 // waits for the recorded events, returns (family id, microseconds) per launch group in issue order and ends the recording.
-enum { F_K1 = 0, F_K2, F_K3, F_B1, F_B2, F_B3, F_B4, F_B5, F_B6, F_FIN, F_PREP, F_CLN_FWD, F_CLN_BWD, F_TAPS, F_WFLUSH, F_FRAME, F_COUNT };
+enum { F_K1 = 0, F_K2, F_K3, F_B1, F_B2, F_B3, F_B4, F_B5, F_B6, F_FIN, F_PREP, F_CLN_FWD, F_CLN_BWD, F_TAPS, F_UNUSED_14, F_FRAME, F_COUNT };     // (14: the removed chained weight gradients' flush; the ids are fixed)
 namespace {
 struct ProbeRec { int fam; hipEvent_t e0, e1; };
 std::vector<ProbeRec> g_probe;          // guarded by g_probe_mu: a second host thread that drives the library while a recording is
@@ -198,7 +198,7 @@ BwdWs bwd_ws(int M, int B, int H, int Kp, int P, int nblocks) {
     w.da1p = o; o += (size_t)nblocks * w.da1p_slot;
     const size_t s1 = ctn_pw_wgrad_workspace(M, H, B, Kp), s2 = ctn_pw_wgrad_workspace(M, B, H, Kp);
     w.slab_bytes = s1 > s2 ? s1 : s2;
-    w.slab = o; o += 2 * align256(w.slab_bytes);          // two: a chained weight gradient writes one while the next launch sums the other
+    w.slab = o; o += align256(w.slab_bytes);
     w.wp = o; o += (size_t)nblocks * 2 * wslot_bytes(B, H);         // [nblocks][w2 operand (H rows) | w1 operand (B rows)], b3 pieces
     w.gb = o; o += align256((size_t)nblocks * 2 * sizeof(float));   // h3: {max |gamma2|, max |beta2|} per block
     w.amax = o; o += align256((size_t)nblocks * 2 * M * CTN_AMAX_SLOTS * sizeof(unsigned));     // h3: tracked maxima of (dy, dh1) per block and utterance
@@ -320,10 +320,7 @@ int ctn_tcn_gln_bwd(const void* const* params, void* const* grads, const int* di
     char* const ws = (char*)workspace;
     float* const dn2 = (float*)(ws + w.dn2);
     double* const s2p = (double*)(ws + w.s2p);
-    // chained weight gradients (ctn_common.h): each launch's slabs are summed inside the next launch of the weight-gradient stream
-    void* const slabs[2] = {ws + w.slab, ws + w.slab + align256(w.slab_bytes)};
-    CtnWgradChain chain;
-    int nwg = 0;
+    void* const slab = ws + w.slab;         // split-K slabs of the weight gradients: all on one stream, each followed by its reduce
     const size_t xsz = (size_t)M * B * Kp, hsz = (size_t)M * H * Kp;
     void* const wst = side_stream ? side_stream : stream;       // where the weight gradients (and parameter-gradient sums) go
     int rc;
@@ -355,8 +352,8 @@ int ctn_tcn_gln_bwd(const void* const* params, void* const* grads, const int* di
         const float* const ms2j = ms + ((size_t)j * 2 + 1) * M * 2;
         const unsigned* const adj = h3 ? amax + (size_t)(2 * j + 1) * M * CTN_AMAX_SLOTS : nullptr;
         unsigned* const adyj = amax_b + (size_t)(2 * j) * M * CTN_AMAX_SLOTS;
-        if (h3) return PROBED(F_B2, wst, ctn_pw_wgrad_h3_chained(dyj, dj, gj[P_W2], M, B, H, K, Kp, pj[P_G2], pj[P_B2], pj[P_A2], ms2j, adyj, adj, gb + 2 * j, slabs[nwg++ & 1], w.slab_bytes, wst, &chain));
-        return PROBED(F_B2, wst, ctn_pw_wgrad_chained(dyj, dj, gj[P_W2], M, B, H, K, Kp, pj[P_G2], pj[P_B2], pj[P_A2], ms2j, slabs[nwg++ & 1], w.slab_bytes, wst, &chain));
+        if (h3) return PROBED(F_B2, wst, ctn_pw_wgrad_h3(dyj, dj, gj[P_W2], M, B, H, K, Kp, pj[P_G2], pj[P_B2], pj[P_A2], ms2j, adyj, adj, gb + 2 * j, slab, w.slab_bytes, wst));
+        return PROBED(F_B2, wst, ctn_pw_wgrad(dyj, dj, gj[P_W2], M, B, H, K, Kp, pj[P_G2], pj[P_B2], pj[P_A2], ms2j, slab, w.slab_bytes, wst));
     };
     if (one_event) {        // dout, its maximum and the norm parameters' maxima are ready in stream order: the last block's dW2 can start
         if ((rc = ctn_stream_order(stream, side_stream))) return rc;
@@ -408,8 +405,8 @@ int ctn_tcn_gln_bwd(const void* const* params, void* const* grads, const int* di
         // optimiser: second stream
         if (side_stream && !one_event && (rc = ctn_stream_order(stream, side_stream))) return rc;
         auto wgrad1 = [&]() -> int {
-            if (h3) return PROBED(F_B6, wst, ctn_pw_wgrad_h3_chained(dn1, x, g[P_W1], M, H, B, K, Kp, nullptr, nullptr, nullptr, nullptr, adh, ax, nullptr, slabs[nwg++ & 1], w.slab_bytes, wst, &chain));
-            return PROBED(F_B6, wst, ctn_pw_wgrad_chained(dn1, x, g[P_W1], M, H, B, K, Kp, nullptr, nullptr, nullptr, nullptr, slabs[nwg++ & 1], w.slab_bytes, wst, &chain));
+            if (h3) return PROBED(F_B6, wst, ctn_pw_wgrad_h3(dn1, x, g[P_W1], M, H, B, K, Kp, nullptr, nullptr, nullptr, nullptr, adh, ax, nullptr, slab, w.slab_bytes, wst));
+            return PROBED(F_B6, wst, ctn_pw_wgrad(dn1, x, g[P_W1], M, H, B, K, Kp, nullptr, nullptr, nullptr, nullptr, slab, w.slab_bytes, wst));
         };
         auto finalize = [&](void* st) -> int {
             return PROBED(F_FIN, st, ctn_dw_bwd_finalize(pc, P, M, H, g[P_D], g[P_G2], g[P_B2], g[P_G1], g[P_B1], g[P_A2],
@@ -435,7 +432,6 @@ int ctn_tcn_gln_bwd(const void* const* params, void* const* grads, const int* di
             if ((rc = finalize(stream))) return rc;
         }
     }
-    if (chain.slab && (rc = PROBED(F_WFLUSH, wst, ctn_wgrad_chain_flush(&chain, wst)))) return rc;     // the last weight gradient's slabs
     // flags bit 0: leave the second stream un-joined (the caller issues more work behind it -- e.g. this bucket's gradient
     // all-reduce -- and joins later; it must then give every un-joined call a workspace of its own)
     if (side_stream && !(flags & 1) && (rc = ctn_stream_order(side_stream, stream))) return rc;
@@ -469,7 +465,7 @@ ClnBwdWs cln_bwd_ws(int M, int B, int H, int Kp, int P, int nblocks) {
     w.dap = o; o += (size_t)nblocks * 2 * w.dap_slot;
     const size_t s1 = ctn_pw_wgrad_workspace(M, H, B, Kp), s2 = ctn_pw_wgrad_workspace(M, B, H, Kp);
     w.slab_bytes = s1 > s2 ? s1 : s2;
-    w.slab = o; o += 2 * align256(w.slab_bytes);          // two: a chained weight gradient writes one while the next launch sums the other
+    w.slab = o; o += align256(w.slab_bytes);
     w.wp = o; o += (size_t)nblocks * 2 * wslot_bytes(B, H);
     w.amax = o; o += align256((size_t)nblocks * 2 * M * CTN_AMAX_SLOTS * sizeof(unsigned));     // h3: tracked maxima of (dy, dh1) per block
     // fused second norm (ctn_tune("cln_fuse")): per-frame column partials of the input-gradient GEMM and the per-frame constants
@@ -600,10 +596,7 @@ int ctn_tcn_cln_bwd(const void* const* params, void* const* grads, const int* di
     double* const colp = (double*)(ws + w.colp);
     float* const fc = (float*)(ws + w.fc);
     const bool fuse = ctn_cln_fuse() != 0, fuse1 = ctn_cln_fuse() >= 2;      // fuse1: n1 was never stored (forward under the same setting)
-    // chained weight gradients (ctn_common.h): each launch's slabs are summed inside the next launch of the weight-gradient stream
-    void* const slabs[2] = {ws + w.slab, ws + w.slab + align256(w.slab_bytes)};
-    CtnWgradChain chain;
-    int nwg = 0;
+    void* const slab = ws + w.slab;         // split-K slabs of the weight gradients: all on one stream, each followed by its reduce
     const size_t xsz = (size_t)M * B * Kp, hsz = (size_t)M * H * Kp, ssz = (size_t)M * Kp;
     void* const wst = side_stream ? side_stream : stream;
     int rc;
@@ -629,8 +622,8 @@ int ctn_tcn_cln_bwd(const void* const* params, void* const* grads, const int* di
         const float* const dyj = j == nblocks - 1 ? dout : dxs + (size_t)(j + 1) * xsz;
         const unsigned* const anj = h3 ? amax + (size_t)(2 * j + 1) * M * CTN_AMAX_SLOTS : nullptr;
         unsigned* const adyj = amax_b + (size_t)(2 * j) * M * CTN_AMAX_SLOTS;
-        if (h3) return PROBED(F_B2, wst, ctn_pw_wgrad_h3_chained(dyj, n2j, gj[P_W2], M, B, H, K, Kp, nullptr, nullptr, nullptr, nullptr, adyj, anj, nullptr, slabs[nwg++ & 1], w.slab_bytes, wst, &chain));
-        return PROBED(F_B2, wst, ctn_pw_wgrad_chained(dyj, n2j, gj[P_W2], M, B, H, K, Kp, nullptr, nullptr, nullptr, nullptr, slabs[nwg++ & 1], w.slab_bytes, wst, &chain));
+        if (h3) return PROBED(F_B2, wst, ctn_pw_wgrad_h3(dyj, n2j, gj[P_W2], M, B, H, K, Kp, nullptr, nullptr, nullptr, nullptr, adyj, anj, nullptr, slab, w.slab_bytes, wst));
+        return PROBED(F_B2, wst, ctn_pw_wgrad(dyj, n2j, gj[P_W2], M, B, H, K, Kp, nullptr, nullptr, nullptr, nullptr, slab, w.slab_bytes, wst));
     };
     if (one_event) {
         if ((rc = ctn_stream_order(stream, side_stream))) return rc;
@@ -692,8 +685,8 @@ int ctn_tcn_cln_bwd(const void* const* params, void* const* grads, const int* di
             return PROBED(F_FIN, fst, ctn_cln_bwd_finalize(pcn1, dap1, M, H, Kp, g[P_G1], g[P_B1], g[P_A1], fst));
         };
         auto wgrad1 = [&]() -> int {
-            if (h3) return PROBED(F_B6, wst, ctn_pw_wgrad_h3_chained(dh1, x, g[P_W1], M, H, B, K, Kp, nullptr, nullptr, nullptr, nullptr, adh, ax, nullptr, slabs[nwg++ & 1], w.slab_bytes, wst, &chain));
-            return PROBED(F_B6, wst, ctn_pw_wgrad_chained(dh1, x, g[P_W1], M, H, B, K, Kp, nullptr, nullptr, nullptr, nullptr, slabs[nwg++ & 1], w.slab_bytes, wst, &chain));
+            if (h3) return PROBED(F_B6, wst, ctn_pw_wgrad_h3(dh1, x, g[P_W1], M, H, B, K, Kp, nullptr, nullptr, nullptr, nullptr, adh, ax, nullptr, slab, w.slab_bytes, wst));
+            return PROBED(F_B6, wst, ctn_pw_wgrad(dh1, x, g[P_W1], M, H, B, K, Kp, nullptr, nullptr, nullptr, nullptr, slab, w.slab_bytes, wst));
         };
         if (!one_event) {
             if (side_stream && (rc = ctn_stream_order(stream, side_stream))) return rc;
@@ -712,7 +705,6 @@ int ctn_tcn_cln_bwd(const void* const* params, void* const* grads, const int* di
             if (i > 0 && (rc = wgrad2(i - 1))) return rc;       // (ahead of the sums instead: 12.09 vs 11.97 ms; two forks: 11.60)
         } else if (!side_stream && (rc = wgrad1())) return rc;
     }
-    if (chain.slab && (rc = PROBED(F_WFLUSH, wst, ctn_wgrad_chain_flush(&chain, wst)))) return rc;     // the last weight gradient's slabs
     // flags bit 0: leave the second stream un-joined (the caller issues more work behind it -- e.g. this bucket's gradient
     // all-reduce -- and joins later; it must then give every un-joined call a workspace of its own)
     if (side_stream && !(flags & 1) && (rc = ctn_stream_order(side_stream, stream))) return rc;

@@ -359,7 +359,6 @@ __global__ __launch_bounds__(WNT, 2) void pw_wgrad_b3_kernel(WgArgs a) {
     __shared__ __attribute__((aligned(16))) __bf16 smem[4 * STAGE];        // (h3: 80 KiB, b6: 120 KiB)
     __bf16* const Ap = smem;                                               // [stage][piece][BM][XPA]
     __bf16* const Bp = smem + 2 * STAGE;
-    static_assert(sizeof(smem) >= 32 * 128 * sizeof(float4), "the chained slab reduction stages 32 x 128 float4 in this buffer");
     __shared__ double red[WNT / 64];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave >> 2, wn = wave & 3;
@@ -492,50 +491,10 @@ __global__ __launch_bounds__(WNT, 2) void pw_wgrad_b3_kernel(WgArgs a) {
     // (Round 3, b6: running the two halves of each barrier interval -- MFMAs of tile kt, split of tile kt + 1 -- in opposite
     // order on waves 4-7, so that each wave's VALU half sits beside its SIMD partner's MFMA half, measured SLOWER: 48.7 vs
     // 44.9 us alone, 13.71 vs 13.43 ms per step; profiles/README.md.)
-    // Chained launches: this grid also sums the slabs of the previous weight gradient of its stream (complete: stream order).
-    // Workgroup b owns float4s [b * per, (b + 1) * per) of that gradient; per batch of 32 slabs four thread groups load eight
-    // slabs each (loads in flight beside this launch's first three k-tiles), exchange them through LDS, and threads 0-127 add
-    // them in slab order -- the sum sequence of slab_reduce_kernel, bit for bit.
-    const bool chained = a.prev_slab != nullptr;
-    const long long pn4 = a.prev_n >> 2;
-    const long long pper = chained ? (pn4 + gridDim.x - 1) / gridDim.x : 0;
-    const long long plo = (long long)blockIdx.x * pper, phi = plo + pper < pn4 ? plo + pper : pn4;
-    const int pf = tid & 127, pg = tid >> 7;
-    float4 pv[8];
-    auto prev_load = [&](long long base, int k0) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const int sl = k0 + 8 * pg + j;
-            pv[j] = (base + pf < phi && sl < a.prev_nsplit) ? *reinterpret_cast<const float4*>(a.prev_slab + ((size_t)sl * pn4 + base + pf) * 4)
-                                                            : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-    };
-    auto prev_sum = [&](float4& s) {
-        float4* const L = reinterpret_cast<float4*>(smem);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) L[(8 * pg + j) * 128 + pf] = pv[j];
-        __syncthreads();
-        if (pg == 0) {
-#pragma unroll 8
-            for (int sl = 0; sl < 32; ++sl) { const float4 v = L[sl * 128 + pf]; s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w; }
-        }
-        __syncthreads();
-    };
-    if (chained && plo < phi) prev_load(plo, 0);
     if (nk > 0) {
         load_regs(0, ra[0], rb[0]);
         if (nk > 1) load_regs(1, ra[1], rb[1]);
         if (nk > 2) load_regs(2, ra[2], rb[2]);
-    }
-    if (chained) {
-        for (long long base = plo; base < phi; base += 128) {
-            float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
-            for (int k0 = 0; k0 < a.prev_nsplit; k0 += 32) {
-                if (base != plo || k0 != 0) prev_load(base, k0);
-                prev_sum(s);
-            }
-            if (pg == 0 && base + pf < phi) *reinterpret_cast<float4*>(a.prev_out + (base + pf) * 4) = s;
-        }
     }
     if (nk > 0) {
         write_lds(0, 0, ra[0], rb[0]);

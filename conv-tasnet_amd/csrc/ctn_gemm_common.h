@@ -292,8 +292,9 @@ __device__ __forceinline__ void gemm_epilogue(const PwArgs& a, f32x16 (&acc)[TL:
                 // store with a REGISTER soffset to need no wait state before a VALU write of its data registers and may schedule
                 // one right behind it (40 such pairs in the round-3 listings of these epilogues, e.g. buffer_store_dwordx4 v[2:5]
                 // .. s4 offen ; v_cvt_f64_f32 v[2:3]); on gfx950 the store can then pick up the NEW value in part of its lanes when
-                // the CU is busy (observed in round 4 on pw_gemm_ws_kernel: 16 of 8192 outputs of a tile, profiles/README.md
-                // r04_a).  With a zero soffset the compiler's hazard recogniser inserts the wait states itself.
+                // the CU is busy (observed in round 4 on a persistent GEMM kernel, since removed: 16 of 8192 outputs of a tile,
+                // profiles/r04_a_store_hazard_evidence.txt).  With a zero soffset the compiler's hazard recogniser inserts the
+                // wait states itself.
                 __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4s, f32x4v{v.x, v.y, v.z, v.w}), rsOut, vo0 + so, 0, 0);
             }
         }
@@ -380,9 +381,6 @@ struct WgArgs {
     const float* pro_gamma; const float* pro_beta; const float* pro_alpha; const float* pro_ms;  // [M,2]
     // h3 arithmetic: [M][CTN_AMAX_SLOTS] max |dOut[m]| / max |X[m]| (as stored), {max |gamma|, max |beta|} of the prologue
     const unsigned* g_amax; const unsigned* x_amax; const float* pro_gbmax;
-    // chained launches (ctn_wgrad_chain, ctn_common.h): the slabs of the PREVIOUS weight gradient on this stream, summed by this
-    // launch's workgroups while their first tiles are in flight (nullptr: nothing pending)
-    const float* prev_slab; float* prev_out; long long prev_n; int prev_nsplit;
 };
 
 

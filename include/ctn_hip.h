@@ -86,13 +86,9 @@ size_t ctn_pw_wgrad_workspace(int M, int R, int Cn, int Kp);
  * steps -- workspace sizes and statistics layouts depend on them).  Keys: "arith" (below); "b3_tile" / "b3_tile_k3" 0|1|2|3 =
  * 128x128 / 128x64 / 256x64 / 256x64 on 8 waves: tile of the split forward / input-gradient kernels (the prologue + residual form has its
  * own); "b3_wgrad_blocks", "wgrad_blocks": target workgroups per weight-gradient launch (split-bf16 / fp32 MFMA);
- * "pw_tile" -1|0..3: tile of the fp32-MFMA forward kernel (also CTN_PW_TILE); "b3_ws" 0|1 (default 0): run the h3 forward /
- * input-gradient GEMMs on the wave-specialised persistent kernel (csrc/ctn_gemm_ws.h; same values, measured slower: kept as a tested
- * experiment), "b3_ws_blocks": its workgroup count; "cln_fr" 16|32: frames per workgroup of the channel-wise LayerNorm backward
+ * "pw_tile" -1|0..3: tile of the fp32-MFMA forward kernel (also CTN_PW_TILE); "cln_fr" 16|32: frames per workgroup of the channel-wise LayerNorm backward
  * kernel (16: three 256-thread workgroups per CU; changes ctn_cln_bwd_blocks()); "cln_lean" 0|1 (default 1): ctn_cln_bwd at 512 channels with PReLU and without `add` /
- * `relu_ref` runs a kernel specialised for that form (same bits, 11 % faster alone); "wgrad_chain" 0|1 (default 0): inside the
- * composite stacks the split-K slabs of a weight gradient are summed by the NEXT weight-gradient launch of the stream instead of a
- * slab_reduce launch of their own (same addition order, same bits; measured equal in the step); "cln_fuse" 0|1|2 (default 2): 1 = the
+ * `relu_ref` runs a kernel specialised for that form (same bits, 11 % faster alone); "cln_fuse" 0|1|2 (default 2): 1 = the
  * composite cLN stacks run the second norm's backward inside the input-gradient GEMM's epilogue and the depthwise backward
  * (ctn_pw_dgrad_cln / ctn_cln_bwd_frame / ctn_dw_bwd_cln) instead of as a ctn_cln_bwd pass; 2 = also the first norm's forward
  * inside the first 1x1 conv's epilogue and the depthwise kernel's prologue (ctn_pw_gemm_cln / ctn_cln_stats_frame / ctn_dw_fwd_cln:

@@ -11,7 +11,10 @@ the time of the call, with ops._side_stream() and torch's current stream).  Addr
 The fixture pins ONE machine: workspace sizes and partial counts follow the CU count, so it stores torch.version.hip, the device
 name and the CU count, and a run anywhere else FAILS with the instruction below (it does not skip).  To re-record, check out the
 parent of the commit under review (the fixture in the tree was recorded from the commit before ClnBlock and CumLnBlock became one
-node over a record of the norm's calls; its older cases expand to what the fixture before it held), build it, copy this module over
+node over a record of the norm's calls; its older cases expand to what the fixture before it held; since then only the workspace
+byte counts of ctn_tcn_gln_bwd / ctn_tcn_cln_bwd were lowered, by arithmetic on the recorded values, when the second split-K slab
+buffer left both workspaces: recorded - align256(max(ctn_pw_wgrad_workspace(M, H, B, Kp), ctn_pw_wgrad_workspace(M, B, H, Kp))) with
+the slab size from the parent's library under the case's arithmetic), build it, copy this module over
 its own, and run there
     python tests/test_gpu_ops_trace.py --record tests/golden/ops_call_trace.json
 never from a tree whose ops.py is the one under review.

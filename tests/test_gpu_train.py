@@ -91,38 +91,6 @@ def test_bucketed_backward_equals_the_single_call(norm, causal, side):
         ops._SIDE_ENABLED = saved_side
 
 
-@pytest.mark.parametrize("side", [True, False])
-@pytest.mark.parametrize("norm,causal", [("gLN", False), ("cLN", True)])
-def test_chained_weight_gradients_equal_the_unchained(norm, causal, side):
-    """Inside the composite stacks the split-K slabs of a weight gradient are summed by the next weight-gradient launch of the
-    stream (ctn_tune("wgrad_chain", 1); opt-in) instead of a slab_reduce launch of their own: the same additions in the same
-    order, so every gradient must be BITWISE the un-chained one's -- at widths where the split kernels run (B = 64, H = 128), an
-    odd number of blocks per call, with the weight gradients on the second stream and on the main one."""
-    from conv_tasnet_amd import ops
-    torch.manual_seed(5)
-    m = ctn.ConvTasNet(64, 20, 64, 128, 3, 3, 1, 2, norm_type=norm, causal=causal).to(DEV)
-    opt = FlatAdam(m.parameters(), lr=1e-3)
-    mix, lens, src = O.synth_batch(41, 3, 4005)
-    mix, lens, src = mix.to(DEV), lens.to(DEV), src.to(DEV)
-    saved_side = ops._SIDE_ENABLED
-    ops._SIDE_ENABLED = side
-    try:
-        grads = []
-        for chain in (0, 1, 1):
-            ctn.lib.call("ctn_tune", b"wgrad_chain", chain)
-            opt.zero_grad()
-            ctn.cal_loss(src, m(mix), lens)[0].backward()
-            ops.join_side_stream(opt.flat_grads.device)
-            torch.cuda.synchronize()
-            grads.append(opt.flat_grads.clone())
-        assert float(grads[0].abs().max()) > 0
-        assert torch.equal(grads[0], grads[1]), "%d gradient elements differ" % int((grads[0] != grads[1]).sum())
-        assert torch.equal(grads[1], grads[2])
-    finally:
-        ctn.lib.call("ctn_tune", b"wgrad_chain", 0)
-        ops._SIDE_ENABLED = saved_side
-
-
 def test_flatadam_state_interchanges_with_torch_adam():
     g, m, batches = _traj_setup()
     opt = FlatAdam(m.parameters(), lr=1e-3)

@@ -44,6 +44,32 @@ def test_bad_arguments_return_error_codes_not_crashes():
         ctn.lib.call("ctn_im2col", 0, 0, 1, 100, 20, 20, 9, 64, 0)
 
 
+def test_tune_refuses_the_removed_keys_and_keeps_the_others():
+    """The keys of the removed persistent GEMM and chained weight gradients are unknown keys now; the switches that stayed still
+    take their default values (read from the sources: the mirror of the cLN dispatch and the lines that parse the environment)."""
+    import re
+    import norm_oracle as NO
+    from conftest import DEFAULT_ARITH
+    from conv_tasnet_amd import ops
+    csrc = os.path.join(ROOT, "conv-tasnet_amd", "csrc")
+    cln, dw = (open(os.path.join(csrc, f)).read() for f in ("ctn_cln.hip", "ctn_dw.hip"))
+    assert "int g_ctn_cln_fr = %d;" % NO.DEFAULT_FR in cln and "int g_ctn_cln_lean = %d;" % NO.DEFAULT_LEAN in cln
+    defaults = {b"arith": ops._ARITH_NAMES.index(DEFAULT_ARITH), b"cln_fr": NO.DEFAULT_FR, b"cln_lean": NO.DEFAULT_LEAN,
+                b"cln_fuse": int(re.search(r"g_ctn_cln_fuse = \(e && [^;]*\? \*e - '0' : (\d);", cln).group(1)),
+                b"gln_fuse": int(re.search(r"g_ctn_gln_fuse = \(e && [^;]*\? \*e - '0' : (\d);", dw).group(1))}
+    tune = ctn.lib.load().ctn_tune
+    try:
+        for key in (b"b3_ws", b"b3_ws_blocks", b"wgrad_chain"):
+            for value in (0, 1):
+                assert tune(key, value) == -1, key
+                assert key in ctn.lib.ctn_last_error(), (key, ctn.lib.ctn_last_error())
+        for key, value in defaults.items():
+            assert tune(key, value) == 0, (key, value, ctn.lib.ctn_last_error())
+    finally:
+        for key, value in defaults.items():
+            tune(key, value)
+
+
 def _dw_call(name, **kw):
     """A depthwise entry point on fake 16-byte-aligned pointers with complete, valid arguments except for `kw` (by the header's
     parameter names): such a call must be refused before any HIP call.  -> (status, message)"""
