@@ -1,4 +1,4 @@
-// Fused low-latency streaming inference for the causal cLN model (include/ctn_hip.h, "streaming" section).
+// Fused low-latency streaming inference for the causal cLN and cumLN models (include/ctn_hip.h, "streaming" section).
 //
 // Everything of the causal stack except the depthwise taps is frame-local, so one workgroup carries a tile of ST_TC frame columns of
 // ONE stream through   depthwise -> PReLU -> cLN -> 1x1 + residual -> next block's 1x1 -> PReLU -> cLN   in LDS (a "stage").  The only
@@ -10,8 +10,11 @@
 // Arithmetic is frame-local and fixed-order: every output value of frame k of stream m is a k-ordered fp32 FMA chain
 // (v_mfma_f32_16x16x4_f32) or a fixed-order sum over the channels of that frame alone, so it does not depend on the chunk the frame
 // arrived in, on its column position in a tile, or on the other streams.
+// The cumulative norm (cumLN) adds fp64 running sums per stream, block and norm, continued in the order of the absolute frame index
+// from a carried record (tile_cumln): the same independence, at one tile per stream and step.
 #include "ctn_common.h"
 #include <algorithm>
+#include <type_traits>
 
 namespace {
 
@@ -183,6 +186,91 @@ __device__ __forceinline__ void tile_cln(float* t, int Ch, const float* __restri
     __syncthreads();
 }
 
+// ---- cumulative layer norm (norm_type 'cumLN'; the contract of ctn_cumln_fwd) -----------------------------------------------------------
+// One carry record per slot, block and norm: the sums of a and a^2 over all channels of all frames so far, and the number of frames.
+// `cum` holds two banks of [M][nblocks][2] records: the current one, which the kernels of a step only read, and the pending one, which
+// one workgroup per slot writes and the step's last launch copies over the current one (stream_advance_cum_kernel).
+struct CumRec {
+    double c1, c2;
+    unsigned long long count, spare;
+};
+static_assert(sizeof(CumRec) == 32, "CumRec is 32 bytes in the C ABI (ctn_stream_cum_bytes)");
+
+// LDS behind the [B + H][ST_TC] tiles of a cumulative kernel: the (sum, sum of squares) partials of every wave and column, the ST_TC
+// column sums, the ST_TC (mean, rstd) pairs.
+constexpr size_t ST_CUM_LDS = (size_t)(ST_NW + 1) * ST_TC * sizeof(double2) + ST_TC * sizeof(float2);
+
+// In place: t = gamma * ((prelu(t) - mu_c) * r_c) + beta with the statistics of column c taken over all channels of the stream's frames
+// up to and including that column: C = rec + the sums of columns 0 .. c, n = Ch * (rec.count + c + 1), mu = C1 / n,
+// r = 1 / sqrt(max(C2 / n - mu^2, 0) + eps).  fp64 from the first addition to mu and r, which are rounded to fp32 once; the last line is
+// tile_cln's.  Thread (group g, column c) sums rows g, g+ST_GRP, ...; the four groups of a wave are added by two exchanges across the
+// lanes of a column, (g0 + g1) + (g2 + g3), which leaves the same bits in all four (the partials stay in registers: 4 KB of LDS
+// instead of 16); lane c of the first 16 adds the ST_NW wave partials of its column in ascending order, then runs the chain
+// C_i = C_{i-1} + s_i from the record to its own column: the same additions in the same order whatever the column, the call and the
+// workgroup.  Columns >= nvalid add nothing and are left without statistics (mu = r = 0).
+// pend != null: this workgroup stores the advanced record.  part: ST_CUM_LDS bytes, 16-byte aligned.  Starts and ends with a barrier.
+__device__ __forceinline__ void tile_cumln(float* t, int Ch, const float* __restrict__ alpha_p, const float* __restrict__ gamma,
+                                           const float* __restrict__ beta, double2* part, const CumRec* __restrict__ rec,
+                                           CumRec* __restrict__ pend, int nvalid) {
+    const int col = threadIdx.x & (ST_TC - 1), grp = threadIdx.x / ST_TC;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    double2* colsum = part + ST_NW * ST_TC;
+    float2* stat = reinterpret_cast<float2*>(colsum + ST_TC);
+    const bool has_a = alpha_p != nullptr;
+    const float al = has_a ? alpha_p[0] : 1.f;
+    __syncthreads();
+    double s1 = 0.0, s2 = 0.0;
+    for (int r = grp; r < Ch; r += ST_GRP) {
+        float v = t[r * ST_TC + col];
+        if (has_a) { v = prelu_f(v, al); t[r * ST_TC + col] = v; }
+        s1 += (double)v;
+        s2 = fma((double)v, (double)v, s2);
+    }
+    s1 += __shfl_xor(s1, ST_TC);
+    s2 += __shfl_xor(s2, ST_TC);
+    s1 += __shfl_xor(s1, 2 * ST_TC);
+    s2 += __shfl_xor(s2, 2 * ST_TC);
+    if (lane < ST_TC) part[wave * ST_TC + col] = double2{s1, s2};
+    __syncthreads();
+    if (threadIdx.x < ST_TC) {
+        double a1 = 0.0, a2 = 0.0;
+#pragma unroll
+        for (int i = 0; i < ST_NW; ++i) {
+            const double2 p = part[i * ST_TC + col];
+            a1 += p.x;
+            a2 += p.y;
+        }
+        colsum[col] = double2{a1, a2};
+    }
+    __syncthreads();
+    if (threadIdx.x < ST_TC) {
+        float2 st = float2{0.f, 0.f};
+        if (col < nvalid) {
+            double c1 = rec->c1, c2 = rec->c2;
+            const unsigned long long cnt = rec->count;
+            for (int i = 0; i <= col; ++i) {
+                c1 += colsum[i].x;
+                c2 += colsum[i].y;
+            }
+            const double n = (double)Ch * (double)(cnt + (unsigned long long)col + 1ull);
+            const double mu = c1 / n;
+            double var = c2 / n - mu * mu;
+            if (var < 0.0) var = 0.0;
+            st = float2{(float)mu, (float)(1.0 / sqrt(var + (double)CTN_EPS))};
+            if (pend != nullptr && col == nvalid - 1) {
+                pend->c1 = c1;
+                pend->c2 = c2;
+                pend->count = cnt + (unsigned long long)nvalid;
+            }
+        }
+        stat[col] = st;
+    }
+    __syncthreads();
+    const float mu = stat[col].x, rs = stat[col].y;
+    for (int r = grp; r < Ch; r += ST_GRP) t[r * ST_TC + col] = gamma[r] * ((t[r * ST_TC + col] - mu) * rs) + beta[r];
+    __syncthreads();
+}
+
 // global [rows][ld] columns k0 .. k0+nvalid-1 <-> LDS [rows][ST_TC]; columns past nvalid are zeros in LDS and are never stored
 __device__ __forceinline__ void tile_load(float* t, const float* __restrict__ g, int rows, int ld, int k0, int nvalid) {
     for (int e = threadIdx.x; e < rows * ST_TC; e += ST_NT) {
@@ -294,14 +382,24 @@ struct StageArgs {
     int B, H, P, F, tiles;
 };
 
+// The cumulative forms take the record banks as well: stage / block j reads cur[(m * nblocks + j) * 2 + norm] and writes pend[same].
+struct CumArgs {
+    const CumRec* cur;
+    CumRec* pend;
+    int nblocks, j;         // j: the stage (StageArgs: blocks j-1 and j) or the block (RowsArgs)
+};
+struct StageArgsCum : StageArgs { CumArgs c; };
+template <bool CUM> using stage_args_t = std::conditional_t<CUM, StageArgsCum, StageArgs>;
+
 // RAGGED (every kernel of a step): slot m computes nf[m] <= F frames from its own ring position; a workgroup whose tile starts at or
 // beyond nf[m] returns before its first load and barrier (blockIdx and the table only: uniform over the workgroup).
-template <bool RAGGED>
-__global__ __launch_bounds__(ST_NT) void stream_stage_kernel(StageArgs a) {
+// CUM: cumulative statistics (tile_cumln) in place of the per-frame ones; tiles == 1, and this workgroup stores the pending records.
+template <bool RAGGED, bool CUM>
+__global__ __launch_bounds__(ST_NT) void stream_stage_kernel(stage_args_t<CUM> a) {
     extern __shared__ float lds[];
     float* ybuf = lds;                              // [B][16]
     float* hbuf = ybuf + (size_t)a.B * ST_TC;       // [H][16]
-    float* part = hbuf + (size_t)a.H * ST_TC;       // [ST_GRP][16]
+    float* part = hbuf + (size_t)a.H * ST_TC;       // [ST_GRP][16]  (CUM: ST_CUM_LDS bytes)
     const int m = blockIdx.x / a.tiles, k0 = (blockIdx.x % a.tiles) * ST_TC;
     const int nf = slot_frames<RAGGED>(a.tab, m, a.F);
     if (RAGGED && k0 >= nf) return;
@@ -313,7 +411,12 @@ __global__ __launch_bounds__(ST_NT) void stream_stage_kernel(StageArgs a) {
     if (a.prev) {
         const float* vec = a.prev + (size_t)2 * H * B;
         tile_dw_any<false>(hbuf, a.ring_prev + (size_t)m * H * a.Rp, a.Rp, pos, a.dp, H, P, vec + 4 + 4 * H, nullptr);
-        tile_cln(hbuf, H, vec + 1, vec + 4 + 2 * H, vec + 4 + 3 * H, part);
+        if constexpr (CUM) {
+            const size_t r = ((size_t)m * a.c.nblocks + (a.c.j - 1)) * 2 + 1;
+            tile_cumln(hbuf, H, vec + 1, vec + 4 + 2 * H, vec + 4 + 3 * H, reinterpret_cast<double2*>(part), a.c.cur + r, a.c.pend + r, nvalid);
+        } else {
+            tile_cln(hbuf, H, vec + 1, vec + 4 + 2 * H, vec + 4 + 3 * H, part);
+        }
         tile_gemm<EPI_ADD>(a.prev + (size_t)H * B, B / 16, H / 16, hbuf, ybuf);
         __syncthreads();
         tile_store(ybuf, yg, B, a.F, k0, nvalid);
@@ -322,7 +425,12 @@ __global__ __launch_bounds__(ST_NT) void stream_stage_kernel(StageArgs a) {
         const float* vec = a.cur + (size_t)2 * H * B;
         __syncthreads();
         tile_gemm<EPI_STORE>(a.cur, H / 16, B / 16, ybuf, hbuf);
-        tile_cln(hbuf, H, vec, vec + 4, vec + 4 + H, part);
+        if constexpr (CUM) {
+            const size_t r = ((size_t)m * a.c.nblocks + a.c.j) * 2;
+            tile_cumln(hbuf, H, vec, vec + 4, vec + 4 + H, reinterpret_cast<double2*>(part), a.c.cur + r, a.c.pend + r, nvalid);
+        } else {
+            tile_cln(hbuf, H, vec, vec + 4, vec + 4 + H, part);
+        }
         ring_store(a.ring_cur + (size_t)m * H * a.Rc, a.Rc, pos, hbuf, H, nvalid);
     }
 }
@@ -361,8 +469,13 @@ __global__ __launch_bounds__(ST_NT) void stream_rows_a_kernel(RowsArgs a) {
     tile_store(hbuf + (size_t)rt0 * 16 * ST_TC, a.hraw + ((size_t)m * a.H + rt0 * 16) * a.F, (rt1 - rt0) * 16, a.F, 0, nf);
 }
 
-template <bool RAGGED>
-__global__ __launch_bounds__(ST_NT) void stream_rows_b_kernel(RowsArgs a) {
+struct RowsArgsCum : RowsArgs { CumArgs c; };
+template <bool CUM> using rows_args_t = std::conditional_t<CUM, RowsArgsCum, RowsArgs>;
+
+// CUM: every one of the slot's nsplit workgroups reads the same two current records and forms the same statistics in the same order;
+// slice 0 alone stores the pending ones.
+template <bool RAGGED, bool CUM>
+__global__ __launch_bounds__(ST_NT) void stream_rows_b_kernel(rows_args_t<CUM> a) {
     extern __shared__ float lds[];
     float* ybuf = lds;
     float* hbuf = ybuf + (size_t)a.B * ST_TC;
@@ -378,10 +491,21 @@ __global__ __launch_bounds__(ST_NT) void stream_rows_b_kernel(RowsArgs a) {
     float* ring = a.ring + (size_t)m * H * a.R;
     tile_load(hbuf, a.hraw + (size_t)m * H * a.F, H, a.F, 0, nf);
     tile_load(ybuf + (size_t)rt0 * 16 * ST_TC, yg, (rt1 - rt0) * 16, a.F, 0, nf);
-    tile_cln(hbuf, H, vec, vec + 4, vec + 4 + H, part);
+    if constexpr (CUM) {
+        const size_t r = ((size_t)m * a.c.nblocks + a.c.j) * 2;
+        tile_cumln(hbuf, H, vec, vec + 4, vec + 4 + H, reinterpret_cast<double2*>(part), a.c.cur + r, sp == 0 ? a.c.pend + r : nullptr, nf);
+    } else {
+        tile_cln(hbuf, H, vec, vec + 4, vec + 4 + H, part);
+    }
     if (sp == 0) ring_store(ring, a.R, pos, hbuf, H, nf);
     tile_dw_any<true>(hbuf, ring, a.R, pos, a.d, H, a.P, vec + 4 + 4 * H, hbuf);
-    tile_cln(hbuf, H, vec + 1, vec + 4 + 2 * H, vec + 4 + 3 * H, part);
+    if constexpr (CUM) {
+        const size_t r = ((size_t)m * a.c.nblocks + a.c.j) * 2 + 1;
+        tile_cumln(hbuf, H, vec + 1, vec + 4 + 2 * H, vec + 4 + 3 * H, reinterpret_cast<double2*>(part), a.c.cur + r,
+                   sp == 0 ? a.c.pend + r : nullptr, nf);
+    } else {
+        tile_cln(hbuf, H, vec + 1, vec + 4 + 2 * H, vec + 4 + 3 * H, part);
+    }
     for (int rt = rt0 + wave; rt < rt1; rt += ST_NW)
         gemm_rows<EPI_ADD, 1>(reinterpret_cast<const float4*>(a.blk + (size_t)H * B), rt, H / 16, hbuf, ybuf);
     __syncthreads();
@@ -395,6 +519,32 @@ __global__ void stream_advance_kernel(unsigned* pos, int frames) {
 __global__ __launch_bounds__(256) void stream_advance_ragged_kernel(unsigned* __restrict__ pos, const int* __restrict__ tab, int M, int F) {
     const int m = blockIdx.x * 256 + threadIdx.x;
     if (m < M) pos[m] += (unsigned)slot_frames<true>(tab, m, F);
+}
+
+// The last launch of a cumulative step: the pending records of every slot that computed frames become its current ones (`per` records per
+// slot), and the ring position(s) advance as in the two kernels above.  Until here no kernel of the step has written a current record.
+template <bool RAGGED>
+__global__ __launch_bounds__(256) void stream_advance_cum_kernel(unsigned* __restrict__ pos, const int* __restrict__ tab, int M, int F,
+                                                                 CumRec* __restrict__ cur, const CumRec* __restrict__ pend, int per) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i < (long long)M * per && slot_frames<RAGGED>(tab, (int)(i / per), F) > 0) cur[i] = pend[i];
+    if (RAGGED) {
+        if (i < M) pos[i] += (unsigned)slot_frames<true>(tab, (int)i, F);
+    } else if (i == 0) {
+        pos[0] += (unsigned)F;
+    }
+}
+
+// The listed slots' records, current and pending, back to zero: blockIdx.y = entry of the list, `per` records per slot and bank.
+struct CumResetArgs {
+    int slot[ST_RST_SLOTS];
+};
+__global__ __launch_bounds__(64) void stream_cum_reset_slots_kernel(CumRec* __restrict__ cum, CumResetArgs a, int M, int per) {
+    const int m = a.slot[blockIdx.y];
+    for (int i = blockIdx.x * 64 + threadIdx.x; i < 2 * per; i += gridDim.x * 64) {
+        const size_t r = (size_t)(i / per) * M * per + (size_t)m * per + i % per;
+        cum[r] = CumRec{0.0, 0.0, 0ull, 0ull};
+    }
 }
 
 // ---- front end: frames of the sample buffer -> relu(U x) = w -> cLN -> bottleneck 1x1 = y ---------------------------
@@ -631,38 +781,45 @@ int ctn_stream_reset(void* state, size_t bytes, void* stream) {
 
 namespace {
 
-// tab == null: one frame count and the state's own position word; else the ragged step (table + one position word per slot)
-int tcn_cln_launch(const void* packed, const int* dilation, int nblocks, float* y, void* state, const int* tab, unsigned* pos_m,
-                   int M, int B, int H, int P, int frames, int max_frames, void* stream) {
-    const size_t lds = ((size_t)(B + H) * ST_TC + ST_GRP * ST_TC) * sizeof(float);
+// tab == null: one frame count and the state's own position word; else the ragged step (table + one position word per slot).
+// CUM: the cumulative kernels on the record banks in `cum` (frames <= ST_TC: one tile per slot), committed by the step's last launch.
+template <bool CUM>
+int tcn_launch(const void* packed, const int* dilation, int nblocks, float* y, void* state, void* cum, const int* tab, unsigned* pos_m,
+               int M, int B, int H, int P, int frames, int max_frames, void* stream) {
+    const size_t lds = (size_t)(B + H) * ST_TC * sizeof(float) + (CUM ? ST_CUM_LDS : ST_GRP * ST_TC * sizeof(float));
     const int tiles = ctn_cdiv(frames, ST_TC);
     const size_t bf = block_floats(B, H, P);
     float* ring = (float*)state + ST_HDR;
     const unsigned* pos = tab ? pos_m : (const unsigned*)state;
+    const int per = nblocks * 2;                    // records per slot and bank
+    CumArgs ca;
+    ca.cur = (const CumRec*)cum; ca.pend = (CumRec*)cum + (size_t)M * per; ca.nblocks = nblocks; ca.j = 0;
     // at most one tile per stream and room for >= 2 workgroups per stream in one round of the CUs: two row-split launches per block
     const int cap = 256 / M;
     if (frames <= ST_TC && cap >= 2) {
         float* hraw = ring;
         for (int j = 0; j < nblocks; ++j) hraw += (size_t)M * H * (size_t)ring_len(P, dilation[j], max_frames);
         for (int j = 0; j < nblocks; ++j) {
-            RowsArgs a;
+            rows_args_t<CUM> a;
             a.blk = (const float*)packed + (size_t)j * bf;
             a.y = y; a.hraw = hraw; a.ring = ring; a.pos = pos; a.tab = tab;
             a.R = (int)ring_len(P, dilation[j], max_frames); a.d = dilation[j];
             a.B = B; a.H = H; a.P = P; a.F = frames;
+            if constexpr (CUM) { a.c = ca; a.c.j = j; }
             a.nsplit = std::max(1, std::min(std::min(H / 16, 16), cap));
-            if (tab) hipLaunchKernelGGL(stream_rows_a_kernel<true>, dim3((unsigned)(M * a.nsplit)), dim3(ST_NT), lds, (hipStream_t)stream, a);
-            else hipLaunchKernelGGL(stream_rows_a_kernel<false>, dim3((unsigned)(M * a.nsplit)), dim3(ST_NT), lds, (hipStream_t)stream, a);
+            const RowsArgs& ra = a;                 // rows_a has no norm: one kernel for both
+            if (tab) hipLaunchKernelGGL(stream_rows_a_kernel<true>, dim3((unsigned)(M * a.nsplit)), dim3(ST_NT), lds, (hipStream_t)stream, ra);
+            else hipLaunchKernelGGL(stream_rows_a_kernel<false>, dim3((unsigned)(M * a.nsplit)), dim3(ST_NT), lds, (hipStream_t)stream, ra);
             a.nsplit = std::max(1, std::min(std::min(B / 16, 16), cap));
-            if (tab) hipLaunchKernelGGL(stream_rows_b_kernel<true>, dim3((unsigned)(M * a.nsplit)), dim3(ST_NT), lds, (hipStream_t)stream, a);
-            else hipLaunchKernelGGL(stream_rows_b_kernel<false>, dim3((unsigned)(M * a.nsplit)), dim3(ST_NT), lds, (hipStream_t)stream, a);
+            if (tab) hipLaunchKernelGGL((stream_rows_b_kernel<true, CUM>), dim3((unsigned)(M * a.nsplit)), dim3(ST_NT), lds, (hipStream_t)stream, a);
+            else hipLaunchKernelGGL((stream_rows_b_kernel<false, CUM>), dim3((unsigned)(M * a.nsplit)), dim3(ST_NT), lds, (hipStream_t)stream, a);
             ring += (size_t)M * H * a.R;
         }
     } else {
         float* ring_prev = nullptr;
         int Rp = 0;
         for (int j = 0; j <= nblocks; ++j) {
-            StageArgs a;
+            stage_args_t<CUM> a;
             a.prev = j >= 1 ? (const float*)packed + (size_t)(j - 1) * bf : nullptr;
             a.cur = j < nblocks ? (const float*)packed + (size_t)j * bf : nullptr;
             a.y = y;
@@ -673,15 +830,48 @@ int tcn_cln_launch(const void* packed, const int* dilation, int nblocks, float* 
             a.Rc = j < nblocks ? (int)ring_len(P, dilation[j], max_frames) : 0;
             a.pos = pos; a.tab = tab;
             a.B = B; a.H = H; a.P = P; a.F = frames; a.tiles = tiles;
-            if (tab) hipLaunchKernelGGL(stream_stage_kernel<true>, dim3((unsigned)(M * tiles)), dim3(ST_NT), lds, (hipStream_t)stream, a);
-            else hipLaunchKernelGGL(stream_stage_kernel<false>, dim3((unsigned)(M * tiles)), dim3(ST_NT), lds, (hipStream_t)stream, a);
+            if constexpr (CUM) { a.c = ca; a.c.j = j; }
+            if (tab) hipLaunchKernelGGL((stream_stage_kernel<true, CUM>), dim3((unsigned)(M * tiles)), dim3(ST_NT), lds, (hipStream_t)stream, a);
+            else hipLaunchKernelGGL((stream_stage_kernel<false, CUM>), dim3((unsigned)(M * tiles)), dim3(ST_NT), lds, (hipStream_t)stream, a);
             ring_prev = ring;
             Rp = a.Rc;
             ring += (size_t)M * H * a.Rc;
         }
     }
-    if (tab) hipLaunchKernelGGL(stream_advance_ragged_kernel, dim3((unsigned)ctn_cdiv(M, 256)), dim3(256), 0, (hipStream_t)stream, pos_m, tab, M, frames);
-    else hipLaunchKernelGGL(stream_advance_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (unsigned*)state, frames);
+    if constexpr (CUM) {
+        const dim3 g((unsigned)ctn_cdivll((long long)M * per, 256));
+        if (tab) hipLaunchKernelGGL(stream_advance_cum_kernel<true>, g, dim3(256), 0, (hipStream_t)stream, pos_m, tab, M, frames, (CumRec*)cum, (const CumRec*)ca.pend, per);
+        else hipLaunchKernelGGL(stream_advance_cum_kernel<false>, g, dim3(256), 0, (hipStream_t)stream, (unsigned*)state, tab, M, frames, (CumRec*)cum, (const CumRec*)ca.pend, per);
+    } else if (tab) {
+        hipLaunchKernelGGL(stream_advance_ragged_kernel, dim3((unsigned)ctn_cdiv(M, 256)), dim3(256), 0, (hipStream_t)stream, pos_m, tab, M, frames);
+    } else {
+        hipLaunchKernelGGL(stream_advance_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (unsigned*)state, frames);
+    }
+    return CTN_OK;
+}
+
+// The argument checks every stack entry point shares (`fn`: its name in the messages).
+int tcn_check(const char* fn, const void* packed, const int* dilation, int nblocks, const float* y, const void* state, int M, int B, int H,
+              int P, int frames, int max_frames) {
+    CTN_REQUIRE(packed && dilation && y && state, "%s: null pointer", fn);
+    CTN_REQUIRE(nblocks > 0 && M > 0, "%s: bad sizes", fn);
+    CTN_REQUIRE(B > 0 && H > 0 && B % 16 == 0 && H % 16 == 0, "%s: B and H must be positive multiples of 16 (got %d, %d)", fn, B, H);
+    CTN_REQUIRE(P >= 1 && P <= ST_MAXP, "%s: kernel size must be 1..%d (got %d)", fn, ST_MAXP, P);
+    CTN_REQUIRE(max_frames >= 1 && max_frames <= (1 << 20), "%s: bad max_frames", fn);
+    CTN_REQUIRE(frames >= 1 && frames <= max_frames, "%s: frames must be 1..max_frames (got %d, max_frames %d)", fn, frames, max_frames);
+    CTN_REQUIRE(ctn_aligned16(packed) && ctn_aligned16(state), "%s: packed and state must be 16-byte aligned", fn);
+    for (int j = 0; j < nblocks; ++j)
+        CTN_REQUIRE(dilation[j] >= 1 && dilation[j] <= (1 << 20), "%s: bad dilation %d of block %d", fn, dilation[j], j);
+    return CTN_OK;
+}
+
+// ... and what the cumulative ones add: one tile per step, the record banks, the LDS of tile_cumln.
+int tcn_check_cum(const char* fn, const void* cum, int B, int H, int frames) {
+    CTN_REQUIRE(frames <= ST_TC, "%s: at most %d frames per step (got %d): cut longer chunks into consecutive steps", fn, ST_TC, frames);
+    CTN_REQUIRE(cum, "%s: null record buffer (cum)", fn);
+    CTN_REQUIRE(ctn_aligned16(cum), "%s: cum must be 16-byte aligned", fn);
+    const size_t lds = (size_t)(B + H) * ST_TC * sizeof(float) + ST_CUM_LDS;
+    CTN_REQUIRE(lds <= ST_MAX_LDS, "%s: B + H = %d needs %zu bytes of LDS per tile with the fp64 partial sums (limit %zu)", fn, B + H, lds, ST_MAX_LDS);
     return CTN_OK;
 }
 
@@ -691,18 +881,10 @@ extern "C" {
 
 int ctn_stream_tcn_cln(const void* packed, const int* dilation, int nblocks, float* y, void* state, int M, int B, int H, int P,
                        int frames, int max_frames, void* stream) {
-    CTN_REQUIRE(packed && dilation && y && state, "ctn_stream_tcn_cln: null pointer");
-    CTN_REQUIRE(nblocks > 0 && M > 0, "ctn_stream_tcn_cln: bad sizes");
-    CTN_REQUIRE(B > 0 && H > 0 && B % 16 == 0 && H % 16 == 0, "ctn_stream_tcn_cln: B and H must be positive multiples of 16 (got %d, %d)", B, H);
-    CTN_REQUIRE(P >= 1 && P <= ST_MAXP, "ctn_stream_tcn_cln: kernel size must be 1..%d (got %d)", ST_MAXP, P);
-    CTN_REQUIRE(max_frames >= 1 && max_frames <= (1 << 20), "ctn_stream_tcn_cln: bad max_frames");
-    CTN_REQUIRE(frames >= 1 && frames <= max_frames, "ctn_stream_tcn_cln: frames must be 1..max_frames (got %d, max_frames %d)", frames, max_frames);
-    CTN_REQUIRE(ctn_aligned16(packed) && ctn_aligned16(state), "ctn_stream_tcn_cln: packed and state must be 16-byte aligned");
-    for (int j = 0; j < nblocks; ++j)
-        CTN_REQUIRE(dilation[j] >= 1 && dilation[j] <= (1 << 20), "ctn_stream_tcn_cln: bad dilation %d of block %d", dilation[j], j);
+    if (int rc = tcn_check("ctn_stream_tcn_cln", packed, dilation, nblocks, y, state, M, B, H, P, frames, max_frames)) return rc;
     const size_t lds = ((size_t)(B + H) * ST_TC + ST_GRP * ST_TC) * sizeof(float);
     CTN_REQUIRE(lds <= ST_MAX_LDS, "ctn_stream_tcn_cln: B + H = %d needs %zu bytes of LDS per tile (limit %zu)", B + H, lds, ST_MAX_LDS);
-    tcn_cln_launch(packed, dilation, nblocks, y, state, nullptr, nullptr, M, B, H, P, frames, max_frames, stream);
+    tcn_launch<false>(packed, dilation, nblocks, y, state, nullptr, nullptr, nullptr, M, B, H, P, frames, max_frames, stream);
     CTN_CHECK_LAUNCH("ctn_stream_tcn_cln");
     return CTN_OK;
 }
@@ -796,20 +978,12 @@ int ctn_stream_front_ragged(const float* x, int xld, const void* Up, const float
 
 int ctn_stream_tcn_cln_ragged(const void* packed, const int* dilation, int nblocks, float* y, void* state, const int* tab, void* pos,
                               int M, int B, int H, int P, int frames, int max_frames, void* stream) {
-    CTN_REQUIRE(packed && dilation && y && state, "ctn_stream_tcn_cln_ragged: null pointer");
+    if (int rc = tcn_check("ctn_stream_tcn_cln_ragged", packed, dilation, nblocks, y, state, M, B, H, P, frames, max_frames)) return rc;
     CTN_REQUIRE(tab, "ctn_stream_tcn_cln_ragged: null step table (tab)");
     CTN_REQUIRE(pos, "ctn_stream_tcn_cln_ragged: null position array (pos)");
-    CTN_REQUIRE(nblocks > 0 && M > 0, "ctn_stream_tcn_cln_ragged: bad sizes");
-    CTN_REQUIRE(B > 0 && H > 0 && B % 16 == 0 && H % 16 == 0, "ctn_stream_tcn_cln_ragged: B and H must be positive multiples of 16 (got %d, %d)", B, H);
-    CTN_REQUIRE(P >= 1 && P <= ST_MAXP, "ctn_stream_tcn_cln_ragged: kernel size must be 1..%d (got %d)", ST_MAXP, P);
-    CTN_REQUIRE(max_frames >= 1 && max_frames <= (1 << 20), "ctn_stream_tcn_cln_ragged: bad max_frames");
-    CTN_REQUIRE(frames >= 1 && frames <= max_frames, "ctn_stream_tcn_cln_ragged: frames must be 1..max_frames (got %d, max_frames %d)", frames, max_frames);
-    CTN_REQUIRE(ctn_aligned16(packed) && ctn_aligned16(state), "ctn_stream_tcn_cln_ragged: packed and state must be 16-byte aligned");
-    for (int j = 0; j < nblocks; ++j)
-        CTN_REQUIRE(dilation[j] >= 1 && dilation[j] <= (1 << 20), "ctn_stream_tcn_cln_ragged: bad dilation %d of block %d", dilation[j], j);
     const size_t lds = ((size_t)(B + H) * ST_TC + ST_GRP * ST_TC) * sizeof(float);
     CTN_REQUIRE(lds <= ST_MAX_LDS, "ctn_stream_tcn_cln_ragged: B + H = %d needs %zu bytes of LDS per tile (limit %zu)", B + H, lds, ST_MAX_LDS);
-    tcn_cln_launch(packed, dilation, nblocks, y, state, tab, (unsigned*)pos, M, B, H, P, frames, max_frames, stream);
+    tcn_launch<false>(packed, dilation, nblocks, y, state, nullptr, tab, (unsigned*)pos, M, B, H, P, frames, max_frames, stream);
     CTN_CHECK_LAUNCH("ctn_stream_tcn_cln_ragged");
     return CTN_OK;
 }
@@ -877,6 +1051,53 @@ int ctn_stream_reset_slots(void* state, float* x, int xld, float* ola_tail, void
         }
     }
     CTN_CHECK_LAUNCH("ctn_stream_reset_slots");
+    return CTN_OK;
+}
+
+// ---- the cumLN stack: the same launches with cumulative statistics, one carry record per slot, block and norm in `cum` ------------------
+size_t ctn_stream_cum_bytes(int M, int nblocks) {
+    if (M < 1 || nblocks < 1) return 0;
+    return (size_t)2 * M * nblocks * 2 * sizeof(CumRec);
+}
+
+int ctn_stream_tcn_cumln(const void* packed, const int* dilation, int nblocks, float* y, void* state, void* cum, int M, int B, int H, int P,
+                         int frames, int max_frames, void* stream) {
+    const char* fn = "ctn_stream_tcn_cumln";
+    if (int rc = tcn_check(fn, packed, dilation, nblocks, y, state, M, B, H, P, frames, max_frames)) return rc;
+    if (int rc = tcn_check_cum(fn, cum, B, H, frames)) return rc;
+    tcn_launch<true>(packed, dilation, nblocks, y, state, cum, nullptr, nullptr, M, B, H, P, frames, max_frames, stream);
+    CTN_CHECK_LAUNCH("ctn_stream_tcn_cumln");
+    return CTN_OK;
+}
+
+int ctn_stream_tcn_cumln_ragged(const void* packed, const int* dilation, int nblocks, float* y, void* state, void* cum, const int* tab,
+                                void* pos, int M, int B, int H, int P, int frames, int max_frames, void* stream) {
+    const char* fn = "ctn_stream_tcn_cumln_ragged";
+    if (int rc = tcn_check(fn, packed, dilation, nblocks, y, state, M, B, H, P, frames, max_frames)) return rc;
+    CTN_REQUIRE(tab, "%s: null step table (tab)", fn);
+    CTN_REQUIRE(pos, "%s: null position array (pos)", fn);
+    if (int rc = tcn_check_cum(fn, cum, B, H, frames)) return rc;
+    tcn_launch<true>(packed, dilation, nblocks, y, state, cum, tab, (unsigned*)pos, M, B, H, P, frames, max_frames, stream);
+    CTN_CHECK_LAUNCH("ctn_stream_tcn_cumln_ragged");
+    return CTN_OK;
+}
+
+int ctn_stream_cum_reset_slots(void* cum, const int* slots, int nslots, int M, int nblocks, void* stream) {
+    CTN_REQUIRE(cum && slots, "ctn_stream_cum_reset_slots: null pointer");
+    CTN_REQUIRE(ctn_aligned16(cum), "ctn_stream_cum_reset_slots: cum must be 16-byte aligned");
+    CTN_REQUIRE(M > 0 && nblocks > 0, "ctn_stream_cum_reset_slots: bad sizes");
+    CTN_REQUIRE(nslots >= 1 && nslots <= M, "ctn_stream_cum_reset_slots: nslots must be 1..M (got %d, M %d)", nslots, M);
+    for (int i = 0; i < nslots; ++i)
+        CTN_REQUIRE(slots[i] >= 0 && slots[i] < M, "ctn_stream_cum_reset_slots: slot %d (entry %d of the list) is outside 0..%d", slots[i], i, M - 1);
+    const int per = nblocks * 2;
+    for (int s0 = 0; s0 < nslots; s0 += ST_RST_SLOTS) {
+        const int ns = std::min(ST_RST_SLOTS, nslots - s0);
+        CumResetArgs a;
+        for (int i = 0; i < ST_RST_SLOTS; ++i) a.slot[i] = slots[s0 + std::min(i, ns - 1)];
+        hipLaunchKernelGGL(stream_cum_reset_slots_kernel, dim3((unsigned)std::min(ctn_cdiv(2 * per, 64), 64), (unsigned)ns), dim3(64), 0,
+                           (hipStream_t)stream, (CumRec*)cum, a, M, per);
+    }
+    CTN_CHECK_LAUNCH("ctn_stream_cum_reset_slots");
     return CTN_OK;
 }
 

@@ -10,7 +10,9 @@ R*(P-1)*(2^X-1) frames (2040 at the paper config) -- but it is state, not recomp
 ``norm_type='cumLN'`` (the paper's cumulative layer norm, csrc/ctn_cumln.hip) adds one more kind of state: per norm the prefix sums
 of the frames so far and their count, kept in device memory and advanced by the scan kernel itself (so a captured graph replays
 it); the order of the prefix sums is fixed by the absolute frame index, so the statistics do not depend on the chunking.
-`StreamingSeparator` serves such models; the fused classes below do not.
+`StreamingSeparator` serves such models with the training kernels; the fused classes below serve them with ``cumulative=True``: the
+fused kernels then carry one (sum, sum of squares, frame count) record per stream, block and norm in a device buffer of their own
+and run at most 16 frames (one tile) per stream and step, because a tile's statistics need the sums of the tiles before it.
 
 All arithmetic runs through the same HIP entry points as training (ops.py); torch only slices / concatenates.
 """
@@ -161,18 +163,34 @@ class StreamingSeparator:
         return out
 
 
+CUM_STEP = 16    # frames per stream and step of the cumulative kernels: one tile (ctn_stream_tcn_cumln in include/ctn_hip.h)
+
+
+def check_fused_model(model, cumulative):
+    """-> bool(cumulative) if the fused streaming kernels serve `model` in that mode, else ValueError (pure host code, no GPU)."""
+    if not model.causal or model.norm_type not in ("cLN", "cumLN"):
+        raise ValueError("the fused streaming kernels need the causal cLN or cumLN variant (gLN statistics span the whole utterance)")
+    if model.norm_type == "cumLN" and not cumulative:
+        raise ValueError("a cumLN model needs cumulative=True here (or StreamingSeparator): the cumulative kernels are opt-in because "
+                         "they keep a carry record per stream, block and norm and run at most %d frames per stream and step "
+                         "(longer pushes are cut into such steps)" % CUM_STEP)
+    if cumulative and model.norm_type != "cumLN":
+        raise ValueError("cumulative=True is for norm_type 'cumLN'; this model has norm_type %r" % (model.norm_type,))
+    return bool(cumulative)
+
+
 class _FusedBase:
     """What FusedStreamingSeparator and FusedStreamPool share: the checks, the packed weights and the fixed buffers of a chunk step."""
 
-    def _setup(self, model, batch, max_chunk_frames, graph):
+    def _setup(self, model, batch, max_chunk_frames, graph, cumulative=False):
         import ctypes
-        if not model.causal or model.norm_type != "cLN":
-            raise ValueError("the fused streaming kernels need the causal cLN variant (gLN statistics span the whole utterance; "
-                             "cumLN is not supported here: use StreamingSeparator)")
+        self.cumulative = check_fused_model(model, cumulative)
         if max_chunk_frames < 1 or batch < 1:
             raise ValueError("batch and max_chunk_frames must be positive")
         m = self.m = model
         self.M, self.F = int(batch), int(max_chunk_frames)
+        if self.cumulative:
+            self.F = min(self.F, CUM_STEP)       # one tile per stream and step; push / plan_steps cut longer pushes at self.F
         self.L, self.S = m.L, m.L // 2
         if m.L % 4 or m.N % 16 or m.B % 16 or m.H % 16:
             raise ValueError("the fused streaming kernels need L % 4 == 0 and N, B, H multiples of 16")
@@ -186,6 +204,8 @@ class _FusedBase:
         u8 = dict(dtype=torch.uint8, device=dev)
         self.state_bytes = lib.ctn_stream_state_bytes(M, m.H, m.P, self.dil, nb, F)
         self.state = torch.zeros(self.state_bytes, **u8)
+        # cumLN: the carry records of every slot, block and norm (two banks); zeros = the start of a stream
+        self.cum = torch.zeros(lib.ctn_stream_cum_bytes(M, nb), **u8) if self.cumulative else None
         self.packed = torch.empty(lib.ctn_stream_pack_bytes(m.B, m.H, m.P, nb), **u8)
         self.Up = torch.empty(lib.ctn_stream_pack_gemm_bytes(m.N, m.L), **u8)
         self.Wbp = torch.empty(lib.ctn_stream_pack_gemm_bytes(m.B, m.N), **u8)
@@ -267,15 +287,23 @@ class FusedStreamingSeparator(_FusedBase):
     Every stream of the batch starts on the same push and delivers the same number of hops; streams that join, leave, reset or
     deliver different amounts per push are served by `FusedStreamPool` (below; same kernels, same bits).  Out of scope: gLN /
     non-causal models (ValueError), training (no autograd).
+
+    ``cumulative=True`` serves a causal cumLN model (the paper's cumulative layer norm) on the cumulative forms of the same kernels
+    (ctn_stream_tcn_cumln): `max_chunk_frames` is clamped to 16, a step is the same 2 * nblocks + 4 launches (the one that advances
+    the ring position also commits the carry records), a longer push is cut into consecutive 16-frame steps inside `push`, and the
+    same bitwise independence of the chunking and of the other streams holds.  It is opt-in: a cumLN model without the keyword, and the
+    keyword with any other model, is a ValueError.
     """
 
-    def __init__(self, model, batch=1, max_chunk_frames=64, graph=False):
-        self._setup(model, batch, max_chunk_frames, graph)
+    def __init__(self, model, batch=1, max_chunk_frames=64, graph=False, cumulative=False):
+        self._setup(model, batch, max_chunk_frames, graph, cumulative)
         self.first = True
 
     def reset(self):
         """Back to the start of a stream (every stream of the batch); packed weights and captured graphs stay valid."""
         lib.call("ctn_stream_reset", self.state.data_ptr(), self.state_bytes, ops._stream())
+        if self.cumulative:
+            self.cum.zero_()
         self.x.zero_()
         self.ola_tail.zero_()
         self.first = True
@@ -307,8 +335,12 @@ class FusedStreamingSeparator(_FusedBase):
         g0, b0 = self._small[4], self._small[5]
         lib.call("ctn_stream_front", self.x.data_ptr(), self.xld, self.Up.data_ptr(), g0.data_ptr(), b0.data_ptr(), self.Wbp.data_ptr(),
                  self.w.data_ptr(), self.y.data_ptr(), M, m.N, m.L, m.B, frames, st)
-        lib.call("ctn_stream_tcn_cln", self.packed.data_ptr(), self.dil, self.nb, self.y.data_ptr(), self.state.data_ptr(),
-                 M, m.B, m.H, m.P, frames, self.F, st)
+        if self.cumulative:
+            lib.call("ctn_stream_tcn_cumln", self.packed.data_ptr(), self.dil, self.nb, self.y.data_ptr(), self.state.data_ptr(),
+                     self.cum.data_ptr(), M, m.B, m.H, m.P, frames, self.F, st)
+        else:
+            lib.call("ctn_stream_tcn_cln", self.packed.data_ptr(), self.dil, self.nb, self.y.data_ptr(), self.state.data_ptr(),
+                     M, m.B, m.H, m.P, frames, self.F, st)
         lib.call("ctn_stream_back", self.y.data_ptr(), self.w.data_ptr(), self.Wmp.data_ptr(), self.Vp.data_ptr(), self.fr.data_ptr(),
                  self.out.data_ptr(), self.ola_tail.data_ptr(), self.x.data_ptr(), self.xld, M, m.N, m.L, m.B, m.C, frames, self.soft, st)
         return self._out_view(frames)
@@ -371,10 +403,13 @@ class FusedStreamPool(_FusedBase):
     padded output rows: two launches and one small upload more than the class, none of them per slot.  ``graph=True`` replays
     front + stack + back as one HIP graph per maximum frame count from its second occurrence on; the per-slot counts live in the
     table, never in a graph; `open` / `close` and both copies stay outside the graphs.
+
+    ``cumulative=True``: a cumLN model, as for `FusedStreamingSeparator` (steps of at most 16 frames per slot); `open` also zeroes
+    the slot's carry records, and a slot that delivers nothing in a step keeps them bit for bit.
     """
 
-    def __init__(self, model, slots=1, max_chunk_frames=16, graph=False):
-        self._setup(model, slots, max_chunk_frames, graph)
+    def __init__(self, model, slots=1, max_chunk_frames=16, graph=False, cumulative=False):
+        self._setup(model, slots, max_chunk_frames, graph, cumulative)
         dev, M = self.dev, self.M
         self.pos = torch.zeros(M, dtype=torch.int32, device=dev)
         self.tab = torch.zeros((M, TAB), dtype=torch.int32, device=dev)
@@ -400,6 +435,8 @@ class FusedStreamPool(_FusedBase):
         m = self.m
         lib.call("ctn_stream_reset_slots", self.state.data_ptr(), self.x.data_ptr(), self.xld, self.ola_tail.data_ptr(), self.pos.data_ptr(),
                  (ctypes.c_int * 1)(slot), 1, self.M, m.H, m.P, self.dil, self.nb, self.F, m.C, m.L, ops._stream())
+        if self.cumulative:
+            lib.call("ctn_stream_cum_reset_slots", self.cum.data_ptr(), (ctypes.c_int * 1)(slot), 1, self.M, self.nb, ops._stream())
         self.is_open[slot], self.fresh[slot] = True, True
         return slot
 
@@ -486,8 +523,12 @@ class FusedStreamPool(_FusedBase):
         g0, b0, tab = self._small[4], self._small[5], self.tab.data_ptr()
         lib.call("ctn_stream_front_ragged", self.x.data_ptr(), self.xld, self.Up.data_ptr(), g0.data_ptr(), b0.data_ptr(),
                  self.Wbp.data_ptr(), self.w.data_ptr(), self.y.data_ptr(), tab, M, m.N, m.L, m.B, frames, st)
-        lib.call("ctn_stream_tcn_cln_ragged", self.packed.data_ptr(), self.dil, self.nb, self.y.data_ptr(), self.state.data_ptr(),
-                 tab, self.pos.data_ptr(), M, m.B, m.H, m.P, frames, self.F, st)
+        if self.cumulative:
+            lib.call("ctn_stream_tcn_cumln_ragged", self.packed.data_ptr(), self.dil, self.nb, self.y.data_ptr(), self.state.data_ptr(),
+                     self.cum.data_ptr(), tab, self.pos.data_ptr(), M, m.B, m.H, m.P, frames, self.F, st)
+        else:
+            lib.call("ctn_stream_tcn_cln_ragged", self.packed.data_ptr(), self.dil, self.nb, self.y.data_ptr(), self.state.data_ptr(),
+                     tab, self.pos.data_ptr(), M, m.B, m.H, m.P, frames, self.F, st)
         lib.call("ctn_stream_back_ragged", self.y.data_ptr(), self.w.data_ptr(), self.Wmp.data_ptr(), self.Vp.data_ptr(),
                  self.fr.data_ptr(), self.out.data_ptr(), self.ola_tail.data_ptr(), self.x.data_ptr(), self.xld, tab,
                  M, m.N, m.L, m.B, m.C, frames, self.soft, st)
@@ -536,15 +577,18 @@ class ResamplingStreamPool:
         x8 zero-padded to max(L, the next multiple of S), through FusedStreamingSeparator(model, batch=1) as one push plus flush()
         the result cut to len(x8), then resample(., model_rate, output_rate)
     whatever the cuts and whatever the other slots do (for zeros != 32 read `resample` as the same sum with that filter).
-    `zeros` sets the resamplers' look-ahead (see StreamResampler); ``graph`` is the pool's: the resample launches stay outside its graphs.
+    `zeros` sets the resamplers' look-ahead (see StreamResampler); ``graph`` and ``cumulative`` are the pool's: the resample launches
+    stay outside its graphs.
     """
 
-    def __init__(self, model, slots=1, max_chunk_frames=16, model_rate=8000, input_rate=8000, output_rate=None, zeros=ZEROS, graph=False):
+    def __init__(self, model, slots=1, max_chunk_frames=16, model_rate=8000, input_rate=8000, output_rate=None, zeros=ZEROS, graph=False,
+                 cumulative=False):
         from . import resample as rs
+        check_fused_model(model, cumulative)                   # ValueError on a model / mode mismatch before anything is built
         rs.ratio(input_rate, model_rate)                       # ValueError on a bad rate before anything is built
         if output_rate is not None:
             rs.ratio(model_rate, output_rate)
-        self.pool = pool = FusedStreamPool(model, slots, max_chunk_frames, graph)
+        self.pool = pool = FusedStreamPool(model, slots, max_chunk_frames, graph, cumulative)
         self.M, self.S, self.L, self.C, self.dev = pool.M, pool.S, pool.L, model.C, pool.dev
         piece = pool.F * pool.S                                  # model-rate samples of one pool step
         self.in_rs = rs.StreamResampler(self.M, input_rate, model_rate, max(1, piece * int(input_rate) // int(model_rate)), zeros=zeros,

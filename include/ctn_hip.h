@@ -607,6 +607,31 @@ int ctn_stream_store_ragged(const float* out, float* dst, long long dld, const i
 int ctn_stream_reset_slots(void* state, float* x, int xld, float* ola_tail, void* pos, const int* slots, int nslots, int M, int H, int P,
                            const int* dilation, int nblocks, int max_frames, int C, int L, void* stream);
 
+/* ---- the same stack with the cumulative layer norm (norm_type 'cumLN', csrc/ctn_stream.hip) -------------------------------------------
+ * ctn_stream_tcn_cumln / _ragged are ctn_stream_tcn_cln / _ragged with both norms of every block cumulative, under the contract of
+ * ctn_cumln_fwd: with a = prelu(input),  s1 = sum_ch a[ch,k],  s2 = sum_ch a[ch,k]^2  of the frame's own channels and C1, C2 their
+ * running sums over the stream's frames 0 .. k,   n = Ch (k + 1),  mu = C1 / n,  r = 1 / sqrt(max(C2 / n - mu^2, 0) + 1e-8),
+ * out = gamma (a - mu) r + beta.  Everything from the first addition to mu and r is fp64; mu and r are rounded to fp32 once and applied
+ * in fp32.  The prefix is the plain chain C_k = C_(k-1) + s_k continued from the carried sums, so a frame's statistics depend on its
+ * absolute index and the stream's past only: not on the chunking, the column, the kernel form or the other slots.  `packed`, `state`,
+ * `tab` and `pos` are those of the cLN calls (ctn_stream_pack serves both norms); front and back end are the same calls.
+ *   cum: caller-owned device buffer of ctn_stream_cum_bytes(M, nblocks) bytes, 16-byte aligned: two banks (current, pending) of
+ *        [M][nblocks][2 norms] records of 32 bytes: { double C1; double C2; uint64 frames; uint64 unused }.  All zeros = the start
+ *        of a stream (zero the whole buffer with a memset, or listed slots with ctn_stream_cum_reset_slots).  The kernels of a step read
+ *        the current bank and one workgroup per slot writes the pending one; the step's last launch, which also advances the ring
+ *        position(s), copies pending over current for every slot that computed frames (ragged: nf[m] > 0; a slot with nf[m] = 0 keeps
+ *        both banks bit for bit).  The frame count is the record's own 64-bit word, not the 32-bit ring position.
+ *   frames <= 16: a tile's prefix needs the sums of the stream's earlier tiles and no kernel here waits on another workgroup, so a step
+ *        is at most ONE 16-frame tile per slot; the caller cuts longer chunks into consecutive steps.  max_frames is what `state` was
+ *        sized with, as above.  LDS: (B + H) * 64 + 4480 bytes <= 64 KiB (the fp64 partial sums of both moments, per wave).
+ *   ctn_stream_cum_reset_slots: both banks of the `nslots` slots listed in `slots` (HOST array) zeroed, one launch per 32 slots. */
+size_t ctn_stream_cum_bytes(int M, int nblocks);
+int ctn_stream_tcn_cumln(const void* packed, const int* dilation, int nblocks, float* y, void* state, void* cum,
+                         int M, int B, int H, int P, int frames, int max_frames, void* stream);
+int ctn_stream_tcn_cumln_ragged(const void* packed, const int* dilation, int nblocks, float* y, void* state, void* cum,
+                                const int* tab, void* pos, int M, int B, int H, int P, int frames, int max_frames, void* stream);
+int ctn_stream_cum_reset_slots(void* cum, const int* slots, int nslots, int M, int nblocks, void* stream);
+
 /* ---- on-device dynamic mixing: a resident single-speaker corpus and the minibatch sampler (csrc/ctn_dynmix.hip) ---------
  * replaces the offline mixture set of the reference's recipe: the list tools/create_txt_file_like_wsj0.py draws (two
  * speakers, snr_1 = randrange(1, 250) / 100 dB, snr_2 = -snr_1) and tools/matlab-code/create_wav_2speakers.m builds
