@@ -226,17 +226,20 @@ class TemporalConvNet(nn.Module):
         K = (mixture.size(-1) - L) // (L // 2) + 1
         return w, x, K
 
+    # norm_type of the TemporalBlocks -> (composite autograd node, its no_grad form)
+    _STACKS = {"gLN": (ops.TcnGln, ops.tcn_gln_infer), "cLN": (ops.TcnCln, ops.tcn_cln_infer), "cumLN": (ops.TcnCumLn, ops.tcn_cumln_infer)}
+
     def blocks(self, x, K):
         blks = [blk for rep in self.network[2] for blk in rep]
         norms = set(b.norm_type for b in blks)
-        if ops.composite_enabled() and blks and norms in ({"gLN"}, {"cLN"}):
-            # the whole stack behind one C call per direction (ctn_tcn_{gln,cln}_fwd / _bwd); bitwise the per-block path
+        if ops.composite_enabled() and blks and len(norms) == 1 and next(iter(norms)) in self._STACKS:
+            # the whole stack behind one C call per direction (ctn_tcn_{gln,cln,cumln}_fwd / _bwd); bitwise the per-block path
             params = [p for b in blks for p in b.fused_params()]
             dil = [b.dilation for b in blks]
-            gln = norms == {"gLN"}
+            node, infer = self._STACKS[next(iter(norms))]
             if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in params)):
-                return (ops.TcnGln if gln else ops.TcnCln).apply(x, K, dil, blks[0].causal, *params)
-            return (ops.tcn_gln_infer if gln else ops.tcn_cln_infer)(x.contiguous(), K, dil, blks[0].causal, params)
+                return node.apply(x, K, dil, blks[0].causal, *params)
+            return infer(x.contiguous(), K, dil, blks[0].causal, params)
         for blk in blks:
             x = blk.fused(x, K)
         return x

@@ -441,6 +441,10 @@ int ctn_tcn_gln_bwd(const void* const* params, void* const* grads, const int* di
 }  // extern "C"
 
 // ---- cLN stack (causal BASELINE config): the same host-side composite over the un-fused norm kernels ------------------
+// ---- cumLN stack (the paper's causal model): the cLN stack's fully fused chain (what ctn_tune("cln_fuse", 2) selects there, here
+// always) with the four per-frame calls replaced by the scans and passes of csrc/ctn_cumln.hip.  One body serves both: `cum` switches
+// those four sites (forward: the first norm's statistics, the second norm's pass; backward: the second norm's constants, the first
+// norm's pass), adds the scan work regions behind the cLN workspace layouts, and nothing else.
 namespace {
 struct ClnBwdWs {
     size_t dn2, dd, dn1, pcw, pcn, dap, slab, wp, amax, colp, fc, total, slab_bytes, pcw_slot, pcn_slot, dap_slot;
@@ -488,34 +492,47 @@ size_t ctn_tcn_cln_fwd_workspace(int M, int B, int H, int Kp, int nblocks) {
            align256((size_t)M * ctn_pw_col_parts(M, H, Kp, cln_fwd_w_form(B, H)) * Kp * 2 * sizeof(double));
 }
 size_t ctn_tcn_cln_bwd_workspace(int M, int B, int H, int Kp, int P, int nblocks) { return cln_bwd_ws(M, B, H, Kp, P, nblocks).total; }
+// the cLN layouts, then the work regions of ctn_cumln_fwd_amax / ctn_cumln_bwd_amax: forward one per half-batch chain (the two chains
+// run concurrently on two streams), backward one (the chain is one stream; a bucketed call has a workspace of its own)
+static size_t cumln_work_region(int M, int Kp) { return align256(ctn_cumln_work_bytes(M, Kp)); }
+size_t ctn_tcn_cumln_fwd_workspace(int M, int B, int H, int Kp, int nblocks) {
+    return ctn_tcn_cln_fwd_workspace(M, B, H, Kp, nblocks) + 2 * cumln_work_region(M, Kp);
+}
+size_t ctn_tcn_cumln_bwd_workspace(int M, int B, int H, int Kp, int P, int nblocks) {
+    return cln_bwd_ws(M, B, H, Kp, P, nblocks).total + cumln_work_region(M, Kp);
+}
 
-int ctn_tcn_cln_fwd(const void* const* params, const int* dilation, int nblocks, const float* x0,
-                    float* xs, float* h1s, float* n1s, float* ds, float* n2s, float* st, unsigned* amax, int save,
-                    int M, int B, int H, int K, int Kp, int P, int causal,
-                    void* workspace, size_t workspace_bytes, void* stream, void* side_stream) {
-    CTN_REQUIRE(params && dilation && nblocks > 0 && x0 && xs && h1s && n1s && ds && n2s && st && workspace, "ctn_tcn_cln_fwd: null pointer");
+static int frame_stack_fwd(const bool cum, const char* const who, const void* const* params, const int* dilation, int nblocks, const float* x0,
+                           float* xs, float* h1s, float* n1s, float* ds, float* n2s, float* st, unsigned* amax, int save,
+                           int M, int B, int H, int K, int Kp, int P, int causal,
+                           void* workspace, size_t workspace_bytes, void* stream, void* side_stream) {
+    CTN_REQUIRE(params && dilation && nblocks > 0 && x0 && xs && h1s && (n1s || cum) && ds && n2s && st && workspace, "%s: null pointer", who);
+    CTN_REQUIRE(!cum || causal == 1, "%s: the cumulative norm is the causal model's: causal must be 1 (got %d)", who, causal);
     const bool h3 = use_h3(B, H);
-    CTN_REQUIRE(!h3 || amax, "ctn_tcn_cln_fwd: the h3 arithmetic needs the amax array");
-    CTN_REQUIRE(M > 0 && B > 0 && H > 0 && K > 0 && Kp >= K && P >= 1, "ctn_tcn_cln_fwd: bad sizes");
-    if (workspace_bytes < ctn_tcn_cln_fwd_workspace(M, B, H, Kp, nblocks)) {
-        ctn_set_error("ctn_tcn_cln_fwd: workspace too small (%zu < %zu)", workspace_bytes, ctn_tcn_cln_fwd_workspace(M, B, H, Kp, nblocks));
+    CTN_REQUIRE(!h3 || amax, "%s: the h3 arithmetic needs the amax array", who);
+    CTN_REQUIRE(M > 0 && B > 0 && H > 0 && K > 0 && Kp >= K && P >= 1, "%s: bad sizes", who);
+    const size_t cln_bytes = ctn_tcn_cln_fwd_workspace(M, B, H, Kp, nblocks);
+    const size_t need = cum ? ctn_tcn_cumln_fwd_workspace(M, B, H, Kp, nblocks) : cln_bytes;
+    if (workspace_bytes < need) {
+        ctn_set_error("%s: workspace too small (%zu < %zu)", who, workspace_bytes, need);
         return CTN_ERR_WORKSPACE;
     }
+    char* const cwork = (char*)workspace + cln_bytes;         // cum: [2 chains] scan work regions
     const size_t xsz = (size_t)M * B * Kp, hsz = (size_t)M * H * Kp, ssz = (size_t)M * Kp;
     char* const wreg = (char*)workspace;
     const size_t slot = wslot_bytes(B, H);
     int rc, tw1 = 0, tw2 = 0;
     for (int i = 0; i < nblocks; ++i)
-        for (int j = 0; j < NPARAM; ++j) CTN_REQUIRE(params[(size_t)i * NPARAM + j], "ctn_tcn_cln_fwd: block %d parameter %d is null", i, j);
+        for (int j = 0; j < NPARAM; ++j) CTN_REQUIRE(params[(size_t)i * NPARAM + j], "%s: block %d parameter %d is null", who, i, j);
     if ((rc = prepare_weights(params, nblocks, B, H, false, wreg, slot, &tw1, &tw2, h3, nullptr, stream))) return rc;
     // ctn_tune("cln_fuse", 2): the first norm has no pass and no stored output -- its per-frame statistics come out of K1's epilogue
     // (column partials + ctn_cln_stats_frame) and the norm is applied in the depthwise kernel's prologue
-    const bool fuse1 = ctn_cln_fuse() >= 2;
+    const bool fuse1 = cum || ctn_cln_fuse() >= 2;          // (the cumulative norm has the fused chain only)
     const int wform = cln_fwd_w_form(B, H), ncol = ctn_pw_col_parts(M, H, Kp, wform);
     double* const colp = (double*)((char*)workspace + align256((size_t)nblocks * 2 * wslot_bytes(B, H)));
     if (h3) {
         if (hipMemsetAsync(amax, 0, (size_t)nblocks * 2 * M * CTN_AMAX_SLOTS * sizeof(unsigned), (hipStream_t)stream) != hipSuccess) {
-            ctn_set_error("ctn_tcn_cln_fwd: hipMemsetAsync failed");
+            ctn_set_error("%s: hipMemsetAsync failed", who);
             return CTN_ERR_LAUNCH;
         }
         if ((rc = PROBED(F_PREP, stream, ctn_absmax_rows(x0, M, (long long)B * Kp, amax, stream)))) return rc;
@@ -529,7 +546,7 @@ int ctn_tcn_cln_fwd(const void* const* params, const int* dilation, int nblocks,
         const float* const* p = (const float* const*)(params + (size_t)i * NPARAM);
         const size_t s = save ? (size_t)i : 0;
         const float* const xin = i == 0 ? x0 : xs + (save ? (size_t)(i - 1) : (size_t)((i - 1) & 1)) * xsz;
-        float* const h1 = h1s + s * hsz; float* const n1 = n1s + s * hsz; float* const d = ds + s * hsz; float* const n2 = n2s + s * hsz;
+        float* const h1 = h1s + s * hsz; float* const n1 = cum ? nullptr : n1s + s * hsz; float* const d = ds + s * hsz; float* const n2 = n2s + s * hsz;
         float* const out = xs + (save ? (size_t)i : (size_t)(i & 1)) * xsz;
         float* const stb = st + s * 4 * ssz;
         for (int step = 0; step < 5; ++step)
@@ -542,6 +559,8 @@ int ctn_tcn_cln_fwd(const void* const* params, const int* dilation, int nblocks,
                 double* const cp = colp + (size_t)m0 * ncol * Kp * 2;
                 if (step == 0 && fuse1)
                     rc = PROBED(F_K1, sc, ctn_pw_gemm_cln(wreg + (size_t)(2 * i) * slot, wform, xin + xo, h1 + ho, Mc, H, B, K, Kp, p[P_A1], cp, ax, sc));
+                else if (step == 1 && cum)
+                    rc = PROBED(F_FRAME, sc, ctn_cumln_stats_frame(cp, ncol, stb + so, stb + ssz + so, nullptr, nullptr, Mc, H, K, Kp, sc));
                 else if (step == 1 && fuse1)
                     rc = PROBED(F_FRAME, sc, ctn_cln_stats_frame(cp, ncol, stb + so, stb + ssz + so, Mc, H, Kp, sc));
                 else if (step == 2 && fuse1)
@@ -558,6 +577,9 @@ int ctn_tcn_cln_fwd(const void* const* params, const int* dilation, int nblocks,
                 else if (step == 2)
                     rc = PROBED(F_K2, sc, ctn_dw_fwd(n1 + ho, d + ho, p[P_D], Mc, H, K, Kp, P, dilation[i], causal, nullptr, 0, nullptr, nullptr, nullptr,
                                                      nullptr, nullptr, nullptr, nullptr, sc));
+                else if (step == 3 && cum)
+                    rc = PROBED(F_CLN_FWD, sc, ctn_cumln_fwd_amax(d + ho, n2 + ho, stb + 2 * ssz + so, stb + 3 * ssz + so, Mc, H, K, Kp, p[P_G2], p[P_B2], p[P_A2],
+                                                                  nullptr, nullptr, cwork + (size_t)c * cumln_work_region(M, Kp), an, sc));
                 else if (step == 3)
                     rc = PROBED(F_CLN_FWD, sc, ctn_cln_fwd(d + ho, n2 + ho, stb + 2 * ssz + so, stb + 3 * ssz + so, Mc, H, K, Kp, p[P_G2], p[P_B2], p[P_A2], an, sc));
                 else if (h3)
@@ -574,35 +596,54 @@ int ctn_tcn_cln_fwd(const void* const* params, const int* dilation, int nblocks,
     return CTN_OK;
 }
 
-int ctn_tcn_cln_bwd(const void* const* params, void* const* grads, const int* dilation, int nblocks,
-                    const float* x0, const float* xs, const float* h1s, const float* n1s, const float* ds, const float* n2s,
-                    const float* st, const unsigned* amax, const float* dout, float* dxs, float* dh1s,
+int ctn_tcn_cln_fwd(const void* const* params, const int* dilation, int nblocks, const float* x0,
+                    float* xs, float* h1s, float* n1s, float* ds, float* n2s, float* st, unsigned* amax, int save,
                     int M, int B, int H, int K, int Kp, int P, int causal,
-                    void* workspace, size_t workspace_bytes, void* stream, void* side_stream, int flags) {
-    CTN_REQUIRE(params && grads && dilation && nblocks > 0 && x0 && xs && h1s && n1s && ds && n2s && st && dout && dxs && dh1s && workspace,
-                "ctn_tcn_cln_bwd: null pointer");
+                    void* workspace, size_t workspace_bytes, void* stream, void* side_stream) {
+    return frame_stack_fwd(false, "ctn_tcn_cln_fwd", params, dilation, nblocks, x0, xs, h1s, n1s, ds, n2s, st, amax, save, M, B, H, K, Kp, P, causal,
+                           workspace, workspace_bytes, stream, side_stream);
+}
+
+int ctn_tcn_cumln_fwd(const void* const* params, const int* dilation, int nblocks, const float* x0,
+                      float* xs, float* h1s, float* n1s, float* ds, float* n2s, float* st, unsigned* amax, int save,
+                      int M, int B, int H, int K, int Kp, int P, int causal,
+                      void* workspace, size_t workspace_bytes, void* stream, void* side_stream) {
+    return frame_stack_fwd(true, "ctn_tcn_cumln_fwd", params, dilation, nblocks, x0, xs, h1s, n1s, ds, n2s, st, amax, save, M, B, H, K, Kp, P, causal,
+                           workspace, workspace_bytes, stream, side_stream);
+}
+
+static int frame_stack_bwd(const bool cum, const char* const who, const void* const* params, void* const* grads, const int* dilation, int nblocks,
+                           const float* x0, const float* xs, const float* h1s, const float* n1s, const float* ds, const float* n2s,
+                           const float* st, const unsigned* amax, const float* dout, float* dxs, float* dh1s,
+                           int M, int B, int H, int K, int Kp, int P, int causal,
+                           void* workspace, size_t workspace_bytes, void* stream, void* side_stream, int flags) {
+    CTN_REQUIRE(params && grads && dilation && nblocks > 0 && x0 && xs && h1s && (n1s || cum) && ds && n2s && st && dout && dxs && dh1s && workspace,
+                "%s: null pointer", who);
+    CTN_REQUIRE(!cum || causal == 1, "%s: the cumulative norm is the causal model's: causal must be 1 (got %d)", who, causal);
     const bool h3 = use_h3(B, H);
-    CTN_REQUIRE(!h3 || amax, "ctn_tcn_cln_bwd: the h3 arithmetic needs the forward pass's amax array");
-    CTN_REQUIRE(M > 0 && B > 0 && H > 0 && K > 0 && Kp >= K && P >= 1, "ctn_tcn_cln_bwd: bad sizes");
+    CTN_REQUIRE(!h3 || amax, "%s: the h3 arithmetic needs the forward pass's amax array", who);
+    CTN_REQUIRE(M > 0 && B > 0 && H > 0 && K > 0 && Kp >= K && P >= 1, "%s: bad sizes", who);
     const ClnBwdWs w = cln_bwd_ws(M, B, H, Kp, P, nblocks);
-    if (workspace_bytes < w.total) {
-        ctn_set_error("ctn_tcn_cln_bwd: workspace too small (%zu < %zu)", workspace_bytes, w.total);
+    const size_t need = w.total + (cum ? cumln_work_region(M, Kp) : 0);
+    if (workspace_bytes < need) {
+        ctn_set_error("%s: workspace too small (%zu < %zu)", who, workspace_bytes, need);
         return CTN_ERR_WORKSPACE;
     }
     char* const ws = (char*)workspace;
+    void* const cwork = ws + w.total;           // cum: the scan work region of the first norm's backward pass
     float* const dn2 = (float*)(ws + w.dn2);
     float* const dd = (float*)(ws + w.dd);
     float* const dn1 = (float*)(ws + w.dn1);
     double* const colp = (double*)(ws + w.colp);
     float* const fc = (float*)(ws + w.fc);
-    const bool fuse = ctn_cln_fuse() != 0, fuse1 = ctn_cln_fuse() >= 2;      // fuse1: n1 was never stored (forward under the same setting)
+    const bool fuse = cum || ctn_cln_fuse() != 0, fuse1 = cum || ctn_cln_fuse() >= 2;      // fuse1: n1 was never stored (forward under the same setting)
     void* const slab = ws + w.slab;         // split-K slabs of the weight gradients: all on one stream, each followed by its reduce
     const size_t xsz = (size_t)M * B * Kp, hsz = (size_t)M * H * Kp, ssz = (size_t)M * Kp;
     void* const wst = side_stream ? side_stream : stream;
     int rc;
     for (int i = 0; i < nblocks; ++i)
         for (int j = 0; j < NPARAM; ++j)
-            CTN_REQUIRE(params[(size_t)i * NPARAM + j] && grads[(size_t)i * NPARAM + j], "ctn_tcn_cln_bwd: block %d parameter / gradient %d is null", i, j);
+            CTN_REQUIRE(params[(size_t)i * NPARAM + j] && grads[(size_t)i * NPARAM + j], "%s: block %d parameter / gradient %d is null", who, i, j);
     char* const wreg = ws + w.wp;
     const size_t slot = wslot_bytes(B, H);
     int twh = -1, twb = -1;
@@ -610,7 +651,7 @@ int ctn_tcn_cln_bwd(const void* const* params, void* const* grads, const int* di
     unsigned* const amax_b = (unsigned*)(ws + w.amax);          // [nblocks][dy | dh1][M][slots]
     if (h3) {
         if (hipMemsetAsync(amax_b, 0, (size_t)nblocks * 2 * M * CTN_AMAX_SLOTS * sizeof(unsigned), (hipStream_t)stream) != hipSuccess) {
-            ctn_set_error("ctn_tcn_cln_bwd: hipMemsetAsync failed");
+            ctn_set_error("%s: hipMemsetAsync failed", who);
             return CTN_ERR_LAUNCH;
         }
         if ((rc = PROBED(F_PREP, stream, ctn_absmax_rows(dout, M, (long long)B * Kp, amax_b + (size_t)(2 * (nblocks - 1)) * M * CTN_AMAX_SLOTS, stream)))) return rc;
@@ -637,7 +678,7 @@ int ctn_tcn_cln_bwd(const void* const* params, void* const* grads, const int* di
         const unsigned* const an = h3 ? amax + (size_t)(2 * i + 1) * M * CTN_AMAX_SLOTS : nullptr;
         unsigned* const ady = amax_b + (size_t)(2 * i) * M * CTN_AMAX_SLOTS;                             // backward: max |dy|, max |dh1|
         unsigned* const adh = amax_b + (size_t)(2 * i + 1) * M * CTN_AMAX_SLOTS;
-        const float* const h1 = h1s + (size_t)i * hsz; const float* const n1 = n1s + (size_t)i * hsz;
+        const float* const h1 = h1s + (size_t)i * hsz; const float* const n1 = cum ? nullptr : n1s + (size_t)i * hsz;
         const float* const d = ds + (size_t)i * hsz; const float* const n2 = n2s + (size_t)i * hsz;
         const float* const stb = st + (size_t)i * 4 * ssz;
         const float* const dy = i == nblocks - 1 ? dout : dxs + (size_t)(i + 1) * xsz;
@@ -660,7 +701,9 @@ int ctn_tcn_cln_bwd(const void* const* params, void* const* grads, const int* di
             if ((rc = wgrad2(i))) return rc;
         }
         if (fuse) {
-            if ((rc = PROBED(F_FRAME, stream, ctn_cln_bwd_frame(colp, w.ncol, stb + 2 * ssz, stb + 3 * ssz, fc, M, H, Kp, stream)))) return rc;
+            if (cum) rc = PROBED(F_FRAME, stream, ctn_cumln_bwd_frame(colp, w.ncol, stb + 2 * ssz, stb + 3 * ssz, fc, M, H, K, Kp, stream));
+            else rc = PROBED(F_FRAME, stream, ctn_cln_bwd_frame(colp, w.ncol, stb + 2 * ssz, stb + 3 * ssz, fc, M, H, Kp, stream));
+            if (rc) return rc;
             if (fuse1) rc = PROBED(F_B3, stream, ctn_dw_bwd_cln(dn2, d, h1, dn1, p[P_D], M, H, K, Kp, P, dilation[i], causal, p[P_G2], p[P_A2], fc,
                                                                 p[P_G1], p[P_B1], p[P_A1], stb, stb + ssz, pcw, stream));
             else rc = PROBED(F_B3, stream, ctn_dw_bwd_cln(dn2, d, n1, dn1, p[P_D], M, H, K, Kp, P, dilation[i], causal, p[P_G2], p[P_A2], fc,
@@ -671,7 +714,9 @@ int ctn_tcn_cln_bwd(const void* const* params, void* const* grads, const int* di
             if ((rc = PROBED(F_B3, stream, ctn_dw_bwd(dd, nullptr, n1, dn1, p[P_D], M, H, K, Kp, P, dilation[i], causal, 0, nullptr, nullptr, nullptr, nullptr,
                                  nullptr, nullptr, nullptr, nullptr, 0, pcw, nullptr, stream)))) return rc;
         }
-        if ((rc = PROBED(F_CLN_BWD, stream, ctn_cln_bwd(dn1, h1, dh1, stb, stb + ssz, M, H, K, Kp, p[P_G1], p[P_A1], nullptr, nullptr, dap1, pcn1, h3 ? adh : nullptr, stream)))) return rc;
+        if (cum) rc = PROBED(F_CLN_BWD, stream, ctn_cumln_bwd_amax(dn1, h1, dh1, stb, stb + ssz, M, H, K, Kp, p[P_G1], p[P_A1], dap1, pcn1, cwork, h3 ? adh : nullptr, stream));
+        else rc = PROBED(F_CLN_BWD, stream, ctn_cln_bwd(dn1, h1, dh1, stb, stb + ssz, M, H, K, Kp, p[P_G1], p[P_A1], nullptr, nullptr, dap1, pcn1, h3 ? adh : nullptr, stream));
+        if (rc) return rc;
         // the fixed-order parameter-gradient sums of this block feed only the optimiser: weight-gradient stream
         void* const fst = wst;
         auto fins = [&]() -> int {
@@ -709,6 +754,24 @@ int ctn_tcn_cln_bwd(const void* const* params, void* const* grads, const int* di
     // all-reduce -- and joins later; it must then give every un-joined call a workspace of its own)
     if (side_stream && !(flags & 1) && (rc = ctn_stream_order(side_stream, stream))) return rc;
     return CTN_OK;
+}
+
+int ctn_tcn_cln_bwd(const void* const* params, void* const* grads, const int* dilation, int nblocks,
+                    const float* x0, const float* xs, const float* h1s, const float* n1s, const float* ds, const float* n2s,
+                    const float* st, const unsigned* amax, const float* dout, float* dxs, float* dh1s,
+                    int M, int B, int H, int K, int Kp, int P, int causal,
+                    void* workspace, size_t workspace_bytes, void* stream, void* side_stream, int flags) {
+    return frame_stack_bwd(false, "ctn_tcn_cln_bwd", params, grads, dilation, nblocks, x0, xs, h1s, n1s, ds, n2s, st, amax, dout, dxs, dh1s,
+                           M, B, H, K, Kp, P, causal, workspace, workspace_bytes, stream, side_stream, flags);
+}
+
+int ctn_tcn_cumln_bwd(const void* const* params, void* const* grads, const int* dilation, int nblocks,
+                      const float* x0, const float* xs, const float* h1s, const float* n1s, const float* ds, const float* n2s,
+                      const float* st, const unsigned* amax, const float* dout, float* dxs, float* dh1s,
+                      int M, int B, int H, int K, int Kp, int P, int causal,
+                      void* workspace, size_t workspace_bytes, void* stream, void* side_stream, int flags) {
+    return frame_stack_bwd(true, "ctn_tcn_cumln_bwd", params, grads, dilation, nblocks, x0, xs, h1s, n1s, ds, n2s, st, amax, dout, dxs, dh1s,
+                           M, B, H, K, Kp, P, causal, workspace, workspace_bytes, stream, side_stream, flags);
 }
 
 }  // extern "C"

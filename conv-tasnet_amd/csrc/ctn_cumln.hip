@@ -272,11 +272,15 @@ __global__ __launch_bounds__(CU_NT) void cumln_sums_kernel(const float* __restri
     }
 }
 
-template <int VEC>
+// TRACK (16-byte form only: no thread of it leaves early): the maximum of |Out| per utterance, merged into amax_out [M][CTN_AMAX_SLOTS]
+// as cln_fwd_v4_kernel does (h3 arithmetic of the GEMM that reads Out).  The stores are those of the untracked form.
+template <int VEC, bool TRACK = false>
 __global__ __launch_bounds__(CU_NT) void cumln_apply_kernel(const float* __restrict__ Y, float* __restrict__ Out,
                                                             const float* __restrict__ mean_i, const float* __restrict__ rstd_i, int M,
                                                             int Ch, int K, int Kp, const float* __restrict__ gamma,
-                                                            const float* __restrict__ beta, const float* __restrict__ alpha_p) {
+                                                            const float* __restrict__ beta, const float* __restrict__ alpha_p,
+                                                            unsigned* __restrict__ amax_out) {
+    static_assert(!TRACK || VEC == 4, "tracked maxima: the 16-byte form");
     constexpr int FR = CU_NQ * VEC;
     const int tid = threadIdx.x, q = tid % CU_NQ, g = tid / CU_NQ;
     const int kb = (Kp + FR - 1) / FR;
@@ -289,6 +293,7 @@ __global__ __launch_bounds__(CU_NT) void cumln_apply_kernel(const float* __restr
     ld_slot<VEC>(mean_i + (size_t)m * Kp + k0, mu);
     ld_slot<VEC>(rstd_i + (size_t)m * Kp + k0, rs);
     const size_t off = (size_t)m * Ch * Kp + k0;
+    float amax = 0.f;
 #pragma unroll 4
     for (int c = g; c < Ch; c += CU_NG) {
         float v[VEC], r[VEC];
@@ -298,8 +303,13 @@ __global__ __launch_bounds__(CU_NT) void cumln_apply_kernel(const float* __restr
         for (int e = 0; e < VEC; ++e) {
             const float a = has_a ? prelu_f(v[e], al) : v[e];
             r[e] = k0 + e < K ? ga * ((a - mu[e]) * rs[e]) + be : 0.f;
+            if constexpr (TRACK) amax = fmaxf(amax, fabsf(r[e]));
         }
         st_slot<VEC>(Out + off + (size_t)c * Kp, r);
+    }
+    if constexpr (TRACK) {
+        __shared__ double sc[CU_NW];
+        block_amax_atomic<CU_NT>(amax, sc, amax_out + (size_t)m * CTN_AMAX_SLOTS, bx % kb);
     }
 }
 
@@ -370,11 +380,12 @@ __global__ __launch_bounds__(NTB) void cumln_bwd_sums_kernel(const float* __rest
     }
 }
 
-template <int NTB>
+// TRACK: the maximum of |dY| per utterance, merged into amax_out [M][CTN_AMAX_SLOTS] as cln_bwd_v4_kernel does; same stores and partials
+template <int NTB, bool TRACK = false>
 __global__ __launch_bounds__(NTB) void cumln_bwd_apply_kernel(const float* __restrict__ dOut, const float* __restrict__ Y,
                                                               float* __restrict__ dY, const float* __restrict__ fc, int M, int Ch, int K,
                                                               int Kp, const float* __restrict__ gamma, const float* __restrict__ alpha_p,
-                                                              float* __restrict__ dalpha_part) {
+                                                              float* __restrict__ dalpha_part, unsigned* __restrict__ amax_out) {
     constexpr int NQ = NTB / 64, FR = 4 * NQ;
     __shared__ float red[NTB / 64];
     const int tid = threadIdx.x, q = tid % NQ, g = tid / NQ;
@@ -390,7 +401,7 @@ __global__ __launch_bounds__(NTB) void cumln_bwd_apply_kernel(const float* __res
     ld_slot<4>(fm + (size_t)Kp, f1);
     ld_slot<4>(fm + (size_t)2 * Kp, f2);
     ld_slot<4>(fm + (size_t)3 * Kp, f3);
-    float dal = 0.f;
+    float dal = 0.f, amax = 0.f;
 #pragma unroll 2
     for (int c = g; c < Ch; c += 64) {
         float y[4], d[4], r[4];
@@ -409,12 +420,17 @@ __global__ __launch_bounds__(NTB) void cumln_bwd_apply_kernel(const float* __res
                 x = neg ? al * da : da;
             }
             r[e] = x;
+            if constexpr (TRACK) amax = fmaxf(amax, fabsf(x));
         }
         st_slot<4>(dY + off + (size_t)c * Kp, r);
     }
     if (dalpha_part != nullptr) {
         dal = block_sum<float, NTB>(dal, red);
         if (tid == 0) dalpha_part[bx] = dal;
+    }
+    if constexpr (TRACK) {
+        __shared__ double sc[NTB / 64];
+        block_amax_atomic<NTB>(amax, sc, amax_out + (size_t)m * CTN_AMAX_SLOTS, bx % kb);
     }
 }
 
@@ -549,8 +565,11 @@ int ctn_cumln_bwd_frame(const double* col_part, int nparts, const float* mean, c
 // work: [M][Kp][2] fp64 per-frame sums, then (backward) fc [M][4][Kp] fp32
 size_t ctn_cumln_work_bytes(int M, int Kp) { return (size_t)M * Kp * (2 * sizeof(double) + 4 * sizeof(float)); }
 
-int ctn_cumln_fwd(const float* Y, float* Out, float* mean, float* rstd, int M, int Ch, int K, int Kp, const float* gamma,
-                  const float* beta, const float* alpha, double* carry, long long* count, void* work, void* stream) {
+// amax_out != NULL: the slots of amax_out[m] also receive the bits of max |Out[m]| (merged: the caller zeroes them), from the apply pass
+// itself in the 16-byte form, from a ctn_absmax_rows pass behind the scalar form (as ctn_cln_fwd's fallbacks)
+int ctn_cumln_fwd_amax(const float* Y, float* Out, float* mean, float* rstd, int M, int Ch, int K, int Kp, const float* gamma,
+                       const float* beta, const float* alpha, double* carry, long long* count, void* work, unsigned* amax_out,
+                       void* stream) {
     CTN_REQUIRE(Y && Out && mean && rstd && gamma && beta && work, "ctn_cumln_fwd: null pointer");
     CTN_REQUIRE(M > 0 && Ch > 0 && K > 0 && Kp >= K, "ctn_cumln_fwd: bad sizes");
     CTN_REQUIRE(ctn_aligned16(work), "ctn_cumln_fwd: work must be 16-byte aligned");
@@ -564,15 +583,25 @@ int ctn_cumln_fwd(const float* Y, float* Out, float* mean, float* rstd, int M, i
     CTN_CHECK_LAUNCH("ctn_cumln_fwd/sums");
     hipLaunchKernelGGL(cumln_scan_kernel, dim3((unsigned)M), dim3(SC_NT), 0, st, sums, 1, mean, rstd, carry, count, M, Ch, K, Kp);
     CTN_CHECK_LAUNCH("ctn_cumln_fwd/scan");
-    if (v4) hipLaunchKernelGGL(cumln_apply_kernel<4>, grid, dim3(CU_NT), 0, st, Y, Out, mean, rstd, M, Ch, K, Kp, gamma, beta, alpha);
-    else hipLaunchKernelGGL(cumln_apply_kernel<1>, grid, dim3(CU_NT), 0, st, Y, Out, mean, rstd, M, Ch, K, Kp, gamma, beta, alpha);
+    if (v4 && amax_out != nullptr)
+        hipLaunchKernelGGL((cumln_apply_kernel<4, true>), grid, dim3(CU_NT), 0, st, Y, Out, mean, rstd, M, Ch, K, Kp, gamma, beta, alpha, amax_out);
+    else if (v4) hipLaunchKernelGGL((cumln_apply_kernel<4>), grid, dim3(CU_NT), 0, st, Y, Out, mean, rstd, M, Ch, K, Kp, gamma, beta, alpha, nullptr);
+    else hipLaunchKernelGGL((cumln_apply_kernel<1>), grid, dim3(CU_NT), 0, st, Y, Out, mean, rstd, M, Ch, K, Kp, gamma, beta, alpha, nullptr);
     CTN_CHECK_LAUNCH("ctn_cumln_fwd/apply");
+    if (!v4 && amax_out != nullptr) return ctn_absmax_rows(Out, M, (long long)Ch * Kp, amax_out, stream);      // scalar form: a pass of its own
     return CTN_OK;
 }
 
+int ctn_cumln_fwd(const float* Y, float* Out, float* mean, float* rstd, int M, int Ch, int K, int Kp, const float* gamma,
+                  const float* beta, const float* alpha, double* carry, long long* count, void* work, void* stream) {
+    return ctn_cumln_fwd_amax(Y, Out, mean, rstd, M, Ch, K, Kp, gamma, beta, alpha, carry, count, work, nullptr, stream);
+}
+
 // pc [2][ctn_cln_bwd_blocks(M, Kp)][Ch] and dalpha_part [ctn_cln_bwd_blocks(M, Kp)]: ctn_cln_bwd's layout, finished by ctn_cln_bwd_finalize
-int ctn_cumln_bwd(const float* dOut, const float* Y, float* dY, const float* mean, const float* rstd, int M, int Ch, int K, int Kp,
-                  const float* gamma, const float* alpha, float* dalpha_part, float* pc, void* work, void* stream) {
+// amax_out != NULL: the slots of amax_out[m] also receive the bits of max |dY[m]| (merged), as for ctn_cumln_fwd_amax
+int ctn_cumln_bwd_amax(const float* dOut, const float* Y, float* dY, const float* mean, const float* rstd, int M, int Ch, int K, int Kp,
+                       const float* gamma, const float* alpha, float* dalpha_part, float* pc, void* work, unsigned* amax_out,
+                       void* stream) {
     CTN_REQUIRE(dOut && Y && dY && mean && rstd && gamma && pc && work, "ctn_cumln_bwd: null pointer");
     CTN_REQUIRE(M > 0 && Ch > 0 && K > 0 && Kp >= K, "ctn_cumln_bwd: bad sizes");
     CTN_REQUIRE(!alpha || dalpha_part, "ctn_cumln_bwd: dalpha_part required with alpha");
@@ -599,14 +628,24 @@ int ctn_cumln_bwd(const float* dOut, const float* Y, float* dY, const float* mea
     hipLaunchKernelGGL(cumln_bwd_scan_kernel, dim3((unsigned)M), dim3(SC_NT), 0, st, sums, 1, mean, rstd, fc, M, Ch, K, Kp);
     CTN_CHECK_LAUNCH("ctn_cumln_bwd/scan");
     if (v4) {
-        if (fr == 16) hipLaunchKernelGGL(cumln_bwd_apply_kernel<256>, dim3((unsigned)rows), dim3(256), 0, st, dOut, Y, dY, fc, M, Ch, K, Kp, gamma, alpha, dap);
-        else hipLaunchKernelGGL(cumln_bwd_apply_kernel<512>, dim3((unsigned)rows), dim3(512), 0, st, dOut, Y, dY, fc, M, Ch, K, Kp, gamma, alpha, dap);
+        const dim3 grid((unsigned)rows);
+        if (amax_out != nullptr) {
+            if (fr == 16) hipLaunchKernelGGL((cumln_bwd_apply_kernel<256, true>), grid, dim3(256), 0, st, dOut, Y, dY, fc, M, Ch, K, Kp, gamma, alpha, dap, amax_out);
+            else hipLaunchKernelGGL((cumln_bwd_apply_kernel<512, true>), grid, dim3(512), 0, st, dOut, Y, dY, fc, M, Ch, K, Kp, gamma, alpha, dap, amax_out);
+        } else if (fr == 16) hipLaunchKernelGGL((cumln_bwd_apply_kernel<256>), grid, dim3(256), 0, st, dOut, Y, dY, fc, M, Ch, K, Kp, gamma, alpha, dap, nullptr);
+        else hipLaunchKernelGGL((cumln_bwd_apply_kernel<512>), grid, dim3(512), 0, st, dOut, Y, dY, fc, M, Ch, K, Kp, gamma, alpha, dap, nullptr);
     } else {
         hipLaunchKernelGGL(cumln_bwd_apply_gen_kernel, dim3((unsigned)(M * ctn_cdiv(Kp, 64))), dim3(GN_NT), 0, st, dOut, Y, dY, fc, M, Ch, K, Kp,
                            gamma, alpha, dap);
     }
     CTN_CHECK_LAUNCH("ctn_cumln_bwd/apply");
+    if (!v4 && amax_out != nullptr) return ctn_absmax_rows(dY, M, (long long)Ch * Kp, amax_out, stream);       // general form: a pass of its own
     return CTN_OK;
+}
+
+int ctn_cumln_bwd(const float* dOut, const float* Y, float* dY, const float* mean, const float* rstd, int M, int Ch, int K, int Kp,
+                  const float* gamma, const float* alpha, float* dalpha_part, float* pc, void* work, void* stream) {
+    return ctn_cumln_bwd_amax(dOut, Y, dY, mean, rstd, M, Ch, K, Kp, gamma, alpha, dalpha_part, pc, work, nullptr, stream);
 }
 
 }  // extern "C"

@@ -14,6 +14,8 @@ autograd node:
              of the paper's causal model (norm_type='cumLN', csrc/ctn_cumln.hip).  ONE node (_frame_block_forward / _backward) over
              a _FrameNorm record of the four calls that differ; the first norm's forward and the second norm's backward ride in the
              neighbouring GEMM epilogues / depthwise kernels (cLN: by ctn_tune("cln_fuse"), include/ctn_hip.h; cumLN: always)
+  TcnGln, TcnCln, TcnCumLn : the whole stack of TemporalBlocks behind one C call per direction (ctn_tcn_*_fwd / _bwd), bitwise the
+             chain of the block nodes above
   Backend  : mask 1x1 -> relu|softmax -> mask*w -> basis -> OLA   (src/conv_tasnet.py:191,206-215,131-146)
   SiSnrPit : PIT SI-SNR loss                                      (src/pit_criterion.py:12-77)
 """
@@ -581,7 +583,8 @@ def cumln_bwd(dOut, Y, mean, rstd, gamma, alpha, K, sinks=None):
 # all that differs: stats_frame(col_part, Ch, K) -> (mean, rstd): the first norm's statistics from ctn_pw_gemm_cln's column partials;
 # bwd_frame(col_part, mean, rstd, Ch, K) -> fc: the second norm's backward constants from ctn_pw_dgrad_cln's; fwd(Y, gamma, beta,
 # alpha, K) and bwd(dOut, Y, mean, rstd, gamma, alpha, K, sinks=): the norm passes.  fused: the block runs the fused chain whatever
-# ctn_tune("cln_fuse") says (the cumulative norm has no other; there is no composite stack for it either).
+# ctn_tune("cln_fuse") says (the cumulative norm has no other; its composite stack, TcnCumLn over ctn_tcn_cumln_fwd / _bwd, issues this
+# chain from C++ with ctn_cumln_fwd_amax / ctn_cumln_bwd_amax in the place of fwd / bwd + absmax_rows).
 _FrameNorm = collections.namedtuple("_FrameNorm", "name stats_frame bwd_frame fwd bwd fused")
 NORM_CLN = _FrameNorm("cLN", lambda col_part, Ch, K: cln_stats_frame(col_part, Ch),
                       lambda col_part, mean, rstd, Ch, K: cln_bwd_frame(col_part, mean, rstd, Ch), cln_fwd, cln_bwd, False)
@@ -869,7 +872,7 @@ def _ptr_table(tensors):
     return (ctypes.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
 
 
-# ---- one routine for both stacks.  They differ in what is listed here: the entry points (include/ctn_hip.h: `entry`_fwd, _bwd and
+# ---- one routine for the three stacks (gLN, cLN, cumLN).  They differ in what is listed here: the entry points (include/ctn_hip.h: `entry`_fwd, _bwd and
 # their _workspace functions), the tags of the cached workspaces (forward, backward, backward call i of a bucketed pass), the
 # activations kept per block -- handed to both C calls in this order, between xs and amax --, whether the weight-gradient stream
 # also honours CTN_CLN_SIDE, and the cLN stack's guard on ctn_tune("cln_fuse").
@@ -896,9 +899,18 @@ def _cln_fuse_guard(ctx, backward):
                        "norm's output is stored only below level 2" % (ctx.fuse, lib.ctn_cln_fuse()))
 
 
+def _cumln_acts(n, M, H, Kp, dev):
+    """h1, (n1 = h1's pointer: the cumLN stack neither writes nor reads it), d, n2 [n,M,H,Kp] and the four statistics [n,4,M,Kp]:
+    always the three-tensor form that _cln_acts has at level 2."""
+    hs = torch.empty((3, n, M, H, Kp), dtype=F32, device=dev)
+    return (hs[0], hs[0], hs[1], hs[2], torch.empty((n, 4, M, Kp), dtype=F32, device=dev))
+
+
 _Stack = collections.namedtuple("_Stack", "name entry tags acts cln_side guard")
 _GLN = _Stack("TcnGln", "ctn_tcn_gln", ("tcn_fwd", "tcn_bwd", "tcn_bwd_bucket%d"), _gln_acts, False, None)
 _CLN = _Stack("TcnCln", "ctn_tcn_cln", ("tcn_cln_fwd", "tcn_cln_bwd", "tcn_cln_bwd_bucket%d"), _cln_acts, True, _cln_fuse_guard)
+# (no guard: ctn_tune("cln_fuse") does not reach the cumulative norm's chain)
+_CUMLN = _Stack("TcnCumLn", "ctn_tcn_cumln", ("tcn_cumln_fwd", "tcn_cumln_bwd", "tcn_cumln_bwd_bucket%d"), _cumln_acts, True, None)
 
 
 def _stack_forward(S, ctx, x0, K, dilations, causal, params):
@@ -1013,6 +1025,20 @@ class TcnCln(torch.autograd.Function):
         return _stack_backward(_CLN, ctx, dout)
 
 
+class TcnCumLn(torch.autograd.Function):
+    """The stack of cumLN TemporalBlocks (the paper's causal model) as one autograd node over ctn_tcn_cumln_fwd / _bwd: the kernels
+    and their order are CumLnBlock's, issued from C++ (bitwise the per-kernel path), with the h3 maxima of n2 and dh1 tracked by the
+    norm passes that store them (ctn_cumln_fwd_amax / ctn_cumln_bwd_amax) instead of measured in passes of their own."""
+
+    @staticmethod
+    def forward(ctx, x0, K, dilations, causal, *params):
+        return _stack_forward(_CUMLN, ctx, x0, K, dilations, causal, params)
+
+    @staticmethod
+    def backward(ctx, dout):
+        return _stack_backward(_CUMLN, ctx, dout)
+
+
 def tcn_gln_infer(x0, K, dilations, causal, params):
     """Forward of the gLN stack without saving activations (torch.no_grad paths)."""
     return _stack_forward(_GLN, None, x0, K, dilations, causal, params)
@@ -1021,6 +1047,11 @@ def tcn_gln_infer(x0, K, dilations, causal, params):
 def tcn_cln_infer(x0, K, dilations, causal, params):
     """cLN stack without saving activations (torch.no_grad paths)."""
     return _stack_forward(_CLN, None, x0, K, dilations, causal, params)
+
+
+def tcn_cumln_infer(x0, K, dilations, causal, params):
+    """cumLN stack without saving activations (torch.no_grad paths)."""
+    return _stack_forward(_CUMLN, None, x0, K, dilations, causal, params)
 
 
 # ---------------------------------------------------------------------------------------

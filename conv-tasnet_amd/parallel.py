@@ -56,7 +56,7 @@ class GradientBuckets:
 
     A flat optimiser's gradient (FlatAdam, FlatSGD) is contiguous per TemporalBlock (9 tensors each, model order), so the blocks of one repeat
     are one slice of it.  With this object installed (enable_overlap) the composite backward of the stack (ops.TcnGln /
-    ops.TcnCln) is issued repeat by repeat -- each call ends with the weight-gradient stream joined into the main stream --
+    ops.TcnCln / ops.TcnCumLn) is issued repeat by repeat -- each call ends with the weight-gradient stream joined into the main stream --
     and after each one `bucket_ready(sinks)` starts an asynchronous all-reduce of that repeat's slice: with the RCCL backend
     it runs on the process group's own stream behind an event of the current stream, i.e. beside the backward kernels of
     the next repeat (34.8 MB at the paper config = 4 x 8.4 MB + the front / back-end layers).  `finish()` reduces whatever

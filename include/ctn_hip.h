@@ -412,6 +412,41 @@ int ctn_cumln_fwd(const float* Y, float* Out, float* mean, float* rstd, int M, i
 int ctn_cumln_bwd(const float* dOut, const float* Y, float* dY, const float* mean, const float* rstd,
                   int M, int Ch, int K, int Kp, const float* gamma, const float* alpha,
                   float* dalpha_part, float* pc, void* work, void* stream);
+/* The two passes with the h3 maximum of what they store tracked on the way (what the composite cumLN stack calls): the same
+ * arguments plus amax_out [M][CTN_AMAX_SLOTS] -- its slots receive max |Out[m]| (forward) / max |dY[m]| (backward), merged into what
+ * they hold, bit for bit what ctn_absmax_rows of the stored tensor gives.  The 16-byte forms take the maximum in their apply pass (a
+ * few VALU max per element, one atomic per workgroup); the scalar / general forms finish with a ctn_absmax_rows pass (the stored
+ * tensor must then be 16-byte aligned with Ch * Kp % 4 == 0).  Every other output has the bits of the untracked entry points, which
+ * are these with amax_out = NULL. */
+int ctn_cumln_fwd_amax(const float* Y, float* Out, float* mean, float* rstd, int M, int Ch, int K, int Kp,
+                       const float* gamma, const float* beta, const float* alpha, double* carry, long long* count,
+                       void* work, unsigned* amax_out, void* stream);
+int ctn_cumln_bwd_amax(const float* dOut, const float* Y, float* dY, const float* mean, const float* rstd,
+                       int M, int Ch, int K, int Kp, const float* gamma, const float* alpha,
+                       float* dalpha_part, float* pc, void* work, unsigned* amax_out, void* stream);
+
+/* The stack of cumLN TemporalBlocks (norm_type = 'cumLN': the paper's causal model) behind one call per direction: the parameter
+ * lists, the params / grads layout, the saved activations, amax, save, flags, the streams and the half-batch chains of the cLN stack
+ * above.  Per block it is the cLN stack's fully fused chain whatever ctn_tune("cln_fuse") says, with the per-frame kernels of the
+ * cumulative norm:
+ *   forward : ctn_pw_gemm_cln -> ctn_cumln_stats_frame (whole utterances: carry = count = NULL) -> ctn_dw_fwd_cln ->
+ *             ctn_cumln_fwd_amax (second norm; n2's maximum tracked) -> 1x1 + residual
+ *   backward: ctn_pw_dgrad_cln -> [dW2] -> ctn_cumln_bwd_frame -> ctn_dw_bwd_cln (first norm applied on the fly) ->
+ *             ctn_cumln_bwd_amax (first norm; dh1's maximum tracked) -> [ctn_dw_bwd_cln_finalize, ctn_cln_bwd_finalize, dW1] -> 1x1 + dy
+ * ([..]: on side_stream when given) -- the calls of ops.CumLnBlock, so the results are bitwise the per-block path's.
+ * n1s is never written or read (may be NULL).  causal must be 1 (CTN_ERR_ARG otherwise).  The workspaces are the cLN stack's
+ * layouts followed by ctn_cumln_work_bytes(M, Kp) regions: two forward (one per chain), one backward. */
+int ctn_tcn_cumln_fwd(const void* const* params, const int* dilation, int nblocks, const float* x0,
+                      float* xs, float* h1s, float* n1s, float* ds, float* n2s, float* st, unsigned* amax, int save,
+                      int M, int B, int H, int K, int Kp, int P, int causal,
+                      void* workspace, size_t workspace_bytes, void* stream, void* side_stream);
+size_t ctn_tcn_cumln_fwd_workspace(int M, int B, int H, int Kp, int nblocks);
+int ctn_tcn_cumln_bwd(const void* const* params, void* const* grads, const int* dilation, int nblocks,
+                      const float* x0, const float* xs, const float* h1s, const float* n1s, const float* ds, const float* n2s,
+                      const float* st, const unsigned* amax, const float* dout, float* dxs, float* dh1s,
+                      int M, int B, int H, int K, int Kp, int P, int causal,
+                      void* workspace, size_t workspace_bytes, void* stream, void* side_stream, int flags);
+size_t ctn_tcn_cumln_bwd_workspace(int M, int B, int H, int Kp, int P, int nblocks);
 
 /* ---- BatchNorm1d over (utterances, frames) per channel, optionally behind PReLU ------------------
  * replaces nn.BatchNorm1d as returned by chose_norm's else-branch, src/conv_tasnet.py:305-309, at its two uses
