@@ -140,7 +140,12 @@ class FlatAdam(FlatOptimizer):
 
         grad_scale multiplies the gradient first (1/world after a summing all-reduce).
         The total gradient norm (after grad_scale) is left in ``last_total_norm`` (device scalar).
-        weight_decay > 0 adds the coupled L2 term after the clip (ctn_clip_adam_l2_step)."""
+        weight_decay > 0 adds the coupled L2 term after the clip (ctn_clip_adam_l2_step).
+
+        Non-finite gradients, unlike clip_grad_norm_ (which multiplies every gradient by a NaN or zero coefficient): a NaN
+        element makes ``last_total_norm`` NaN and, by C's fminf, the clip coefficient 1, so only that element of the
+        parameters and moments turns NaN; an infinite element makes the norm inf and the coefficient 0, so that element
+        turns NaN (inf * 0) and every other sees a zero gradient.  Check ``last_total_norm`` to skip such a step."""
         loss = None
         if closure is not None:
             with torch.enable_grad():
@@ -227,7 +232,9 @@ class FlatSGD(FlatOptimizer):
     @torch.no_grad()
     def step(self, closure=None, max_grad_norm=0.0, grad_scale=1.0):
         """SGD step; with max_grad_norm > 0 the clip_grad_norm_ rule is fused in front of it (same contract as
-        FlatAdam.step).  The hyper-parameters are read from param_groups[0] on every call (LR halving edits them)."""
+        FlatAdam.step, non-finite gradients included: a NaN element reaches only its own parameter and momentum slot, an
+        infinite one zeroes every other gradient of the step).  The hyper-parameters are read from param_groups[0] on every
+        call (LR halving edits them)."""
         loss = None
         if closure is not None:
             with torch.enable_grad():
