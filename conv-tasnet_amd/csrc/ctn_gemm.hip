@@ -172,7 +172,8 @@ __global__ __launch_bounds__(TL::NTH) void pw_gemm_kernel(PwArgs a) {
         }
     }
 
-    gemm_epilogue<TL, EPI>(a, acc, smem, red, m, rt, ct);
+    // (two row groups per wave: two batches of auxiliary loads would cost these tiles a resident wave -- loads in their passes)
+    gemm_epilogue<TL, EPI, TL::MT == 1>(a, acc, smem, red, m, rt, ct);
 }
 
 

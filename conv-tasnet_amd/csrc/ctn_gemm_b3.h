@@ -785,11 +785,13 @@ void pw_gemm_b3p_kernel(PwArgs a) {
 #ifdef CTN_EXP_B3_NOEPI
     if (a.K < 0) a.Out[tid] = acc[0][0][0] + acc[MT - 1][NTL - 1][15];      // never taken: keeps the accumulators live
 #else
-    if constexpr (Ar<AR>::F16) {
+    // (h3_unscale runs inside the epilogue, behind the first row group's auxiliary loads: their latency lies under it)
+    gemm_epilogue<TL, EPI, true>(a, acc, reinterpret_cast<float*>(smem_raw), red, m, rt, ct, [&]() {
+        if constexpr (Ar<AR>::F16) {
 #pragma unroll
-        for (int i = 0; i < MT; ++i) h3_unscale<Ar<AR>::W2>(acc[i], acc2[Ar<AR>::W2 ? i : 0], ew, ex);
-    }
-    gemm_epilogue<TL, EPI>(a, acc, reinterpret_cast<float*>(smem_raw), red, m, rt, ct);
+            for (int i = 0; i < MT; ++i) h3_unscale<Ar<AR>::W2>(acc[i], acc2[Ar<AR>::W2 ? i : 0], ew, ex);
+        }
+    });
 #endif
     CTN_TL_STAMP(3);
 }

@@ -120,9 +120,33 @@ __device__ __forceinline__ float4 pro_apply(float4 v, int k, int K, float g, flo
 // Global traffic goes through buffer descriptors of this utterance's [R, Kp] matrices: rows >= R are dropped /
 // read as 0 by the hardware range check (their accumulators are exact zeros, so the statistics need no row
 // predicate either); only a tile that overhangs Kp -- a uniform condition -- masks its columns per lane.
-template <typename TL, int EPI>
+//
+// The auxiliary operand (residual / bwd_y, and gamma of the norm backward forms) of a whole 32-row group is loaded into registers
+// in one batch ahead of the group's first store: the first group's before `unscale` (the caller's last touch of the accumulators:
+// h3_unscale of the h3 kernels) and the staging writes, the next group's before the current group's stores.  gfx950 counts loads
+// and stores in ONE in-order vmcnt, so a load issued in the pass that needs it is waited for together with the previous pass's
+// store -- a dependent round trip per pass; with the batch in front, pass p waits on a count that never reaches back to a store.
+// The predicate of a tile that overhangs Kp does not depend on the pass: it is taken once, outside the pass loop, which is
+// then one basic block (profiles/README.md, "GEMM epilogues: auxiliary loads ahead of the stores").
+// AHEAD = false keeps the loads in their passes: the callers' choice where the batch does not fit the registers (the fp32-MFMA tiles
+// with two row groups per wave, which would lose a resident wave).  EPI_GLN_BWD2 (ctn_tune("gln_fuse", 1), off by default) stays as
+// it was, predicate in the pass included: its six extra sums leave no room on the h3 tiles -- a batch, half a batch and the hoisted
+// predicate alone each cost 56 bytes of scratch per lane.
+template <typename TL, int EPI, bool AHEAD>
+struct EpiAux {
+    static constexpr bool PRED_IN_PASS = EPI == EPI_GLN_BWD2;
+    static constexpr int NPASS = 32 / (64 / (TL::WN / 4));
+    static constexpr bool Y = EPI == EPI_RESIDUAL || EPI == EPI_GLN_BWD || EPI == EPI_GLN_BWD2 || EPI == EPI_CLN_BWD;   // has a 16-byte operand
+    static constexpr bool G = EPI == EPI_GLN_BWD || EPI == EPI_CLN_BWD;                  // and a gamma dword (EPI_GLN_BWD2: from LDS)
+    static constexpr bool PRE = AHEAD && Y && EPI != EPI_GLN_BWD2;
+    float4 y[PRE ? NPASS : 1];
+    float g[PRE && G ? NPASS : 1];
+};
+struct EpiNoUnscale { __device__ __forceinline__ void operator()() const {} };
+
+template <typename TL, int EPI, bool AHEAD = true, typename Unscale = EpiNoUnscale>
 __device__ __forceinline__ void gemm_epilogue(const PwArgs& a, f32x16 (&acc)[TL::MT][TL::NTL], float* smem, double* red,
-                                              int m, int rt, int ct) {
+                                              int m, int rt, int ct, Unscale unscale = Unscale()) {
     constexpr int MT = TL::MT, NTL = TL::NTL, WM = TL::WM, WN = TL::WN, TM = TL::TM, TN = TL::TN;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave / TL::WGN, wn = wave % TL::WGN;
@@ -151,6 +175,25 @@ __device__ __forceinline__ void gemm_epilogue(const PwArgs& a, f32x16 (&acc)[TL:
         rsAux = make_rsrc(a.bwd_y + mbase, mat_bytes);
         rsGam = make_rsrc(a.bwd_gamma, (unsigned)a.R * 4u);
     }
+    const bool ragged = c0 + TN > a.Kp;     // uniform
+    const int rl0 = lane / C4, cl = (lane % C4) * 4;
+    const int kcol = c0 + wn * WN + cl;
+    const bool live = !ragged || kcol < a.Kp;       // a masked-out thread loads nothing, adds nothing to any sum and stores nothing
+    const int vo0 = ((r0 + wm * WM + rl0) * a.Kp + kcol) * 4;
+    using Aux = EpiAux<TL, EPI, AHEAD>;
+    constexpr int NPASS = Aux::NPASS;
+    Aux aux[MT > 1 ? 2 : 1];                        // two sets with two row groups: the next group's loads before this group's stores
+    auto aux_load = [&](Aux& x, int mt) {
+#pragma unroll
+        for (int p = 0; p < NPASS; ++p) {
+            x.y[p] = buf_ld4(rsAux, vo0, (mt * 32 + p * RPP) * a.Kp * 4);
+            if constexpr (Aux::G) x.g[p] = buf_ld1(rsGam, (r0 + wm * WM + rl0) * 4, (mt * 32 + p * RPP) * 4);
+        }
+    };
+    if constexpr (Aux::PRE) {
+        if (live) aux_load(aux[0], 0);
+    }
+    unscale();
     // EPI_GLN_BWD2: per-row constants of the first norm and the depthwise taps through range-checked descriptors (rows >= R read 0)
     __amdgpu_buffer_rsrc_t rsG1 = rsOut, rsB1 = rsOut, rsD = rsOut;
     float q3 = 0.f, q4 = 0.f, q5 = 0.f, q6 = 0.f, q7 = 0.f, q8 = 0.f;
@@ -180,19 +223,15 @@ __device__ __forceinline__ void gemm_epilogue(const PwArgs& a, f32x16 (&acc)[TL:
         }
         __syncthreads();
     }
-    const bool ragged = c0 + TN > a.Kp;     // uniform
-    const int rl0 = lane / C4, cl = (lane % C4) * 4;
-    const int kcol = c0 + wn * WN + cl;
     // EPI_CLN_BWD: this thread's four frames keep their columns through every pass: per-frame statistics once, column sums in registers
     float4 c_mu = make_float4(0.f, 0.f, 0.f, 0.f), c_rs = c_mu;
     float cs1[4] = {0.f, 0.f, 0.f, 0.f}, cs2[4] = {0.f, 0.f, 0.f, 0.f};
     if constexpr (EPI == EPI_CLN_BWD) {
-        if (!ragged || kcol < a.Kp) {
+        if (live) {
             c_mu = ld4(a.cln_mean + (size_t)m * a.Kp + kcol);
             c_rs = ld4(a.cln_rstd + (size_t)m * a.Kp + kcol);
         }
     }
-    const int vo0 = ((r0 + wm * WM + rl0) * a.Kp + kcol) * 4;
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt) {
 #pragma unroll
@@ -204,15 +243,31 @@ __device__ __forceinline__ void gemm_epilogue(const PwArgs& a, f32x16 (&acc)[TL:
                 else
                     stage[((e & 3) + 8 * (e >> 2) + 4 * lhi) * LST + nt * 32 + l31] = acc[mt][nt][e];
         __builtin_amdgcn_wave_barrier();
+        if (Aux::PRED_IN_PASS || live) {
+            const Aux& ax = aux[mt & 1];
+            if constexpr (Aux::PRE && MT > 1) {
+                if (mt + 1 < MT) aux_load(aux[(mt + 1) & 1], mt + 1);
+            }
 #pragma unroll
-        for (int p = 0; p < 32 / RPP; ++p) {
-            const int rl = p * RPP + rl0;
-            const int so = (mt * 32 + p * RPP) * a.Kp * 4;                  // scalar byte offset of this pass
-            float4 v = *reinterpret_cast<const float4*>(stage + rl * LST + cl);
-            if (!ragged || kcol < a.Kp) {
+            for (int p = 0; p < NPASS; ++p) {
+                const int rl = p * RPP + rl0;
+                const int so = (mt * 32 + p * RPP) * a.Kp * 4;                  // scalar byte offset of this pass
+                float4 v = *reinterpret_cast<const float4*>(stage + rl * LST + cl);
+                if constexpr (Aux::PRED_IN_PASS) {
+                    if (!live) continue;
+                }
+                // this pass's auxiliary operand: out of the batch, or loaded here
+                float4 y = make_float4(0.f, 0.f, 0.f, 0.f);
+                float g = 0.f;
+                if constexpr (Aux::PRE) {
+                    y = ax.y[p];
+                    if constexpr (Aux::G) g = ax.g[p];
+                } else {
+                    if constexpr (Aux::Y) y = buf_ld4(rsAux, vo0, so);
+                    if constexpr (Aux::G) g = buf_ld1(rsGam, (r0 + wm * WM + rl0) * 4, (mt * 32 + p * RPP) * 4);
+                }
                 if constexpr (EPI == EPI_RESIDUAL) {
-                    const float4 q = buf_ld4(rsAux, vo0, so);
-                    v.x += q.x; v.y += q.y; v.z += q.z; v.w += q.w;
+                    v.x += y.x; v.y += y.y; v.z += y.z; v.w += y.w;
                     amax = fmaxf(fmaxf(amax, fmaxf(fabsf(v.x), fabsf(v.y))), fmaxf(fabsf(v.z), fabsf(v.w)));
                 }
                 if constexpr (EPI == EPI_RELU) {
@@ -229,8 +284,6 @@ __device__ __forceinline__ void gemm_epilogue(const PwArgs& a, f32x16 (&acc)[TL:
                     }
                 }
                 if constexpr (EPI == EPI_GLN_BWD) {
-                    const float4 y = buf_ld4(rsAux, vo0, so);
-                    const float g = buf_ld1(rsGam, (r0 + wm * WM + rl0) * 4, (mt * 32 + p * RPP) * 4);
                     const float t0 = g * v.x, t1 = g * v.y, t2 = g * v.z, t3 = g * v.w;
                     const float x0 = (prelu_f(y.x, e_alpha) - b_mean) * b_rstd, x1 = (prelu_f(y.y, e_alpha) - b_mean) * b_rstd;
                     const float x2 = (prelu_f(y.z, e_alpha) - b_mean) * b_rstd, x3 = (prelu_f(y.w, e_alpha) - b_mean) * b_rstd;
@@ -238,10 +291,9 @@ __device__ __forceinline__ void gemm_epilogue(const PwArgs& a, f32x16 (&acc)[TL:
                     s2 += (t0 * x0 + t1 * x1) + (t2 * x2 + t3 * x3);
                 }
                 if constexpr (EPI == EPI_GLN_BWD2) {
-                    const float4 y = buf_ld4(rsAux, vo0, so);
                     const int rloc = wm * WM + mt * 32 + rl;                    // row of this pass inside the tile
                     const float4 rc = *reinterpret_cast<const float4*>(&rowc[rloc][0]);
-                    const float g = rc.x, g1v = rc.y, b1v = rc.z;
+                    const float g2v = rc.x, g1v = rc.y, b1v = rc.z;
                     const float vv[4] = {v.x, v.y, v.z, v.w}, yy[4] = {y.x, y.y, y.z, y.w};
                     // V of this thread's four frames: the sum of the taps whose source frame lies in [0, K)
                     float V[4] = {rc.w, rc.w, rc.w, rc.w};
@@ -258,7 +310,7 @@ __device__ __forceinline__ void gemm_epilogue(const PwArgs& a, f32x16 (&acc)[TL:
                     // with u = prelu'(y): u y = prelu(y) = pp, so  sum u (y - b1 V) f = sum pp f - b1 sum u V f  for f in {t, 1, xh}
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
-                        const float t = g * vv[e], pp = prelu_f(yy[e], e_alpha);
+                        const float t = g2v * vv[e], pp = prelu_f(yy[e], e_alpha);
                         const float xh = (pp - b_mean) * b_rstd;
                         s1 += t;
                         s2 += t * xh;
@@ -271,8 +323,6 @@ __device__ __forceinline__ void gemm_epilogue(const PwArgs& a, f32x16 (&acc)[TL:
                 }
                 if constexpr (EPI == EPI_CLN_BWD) {
                     // (rows >= R: gamma reads 0 through the range check and y reads 0: both sums get exact zeros)
-                    const float4 y = buf_ld4(rsAux, vo0, so);
-                    const float g = buf_ld1(rsGam, (r0 + wm * WM + rl0) * 4, (mt * 32 + p * RPP) * 4);
                     const float t0 = g * v.x, t1 = g * v.y, t2 = g * v.z, t3 = g * v.w;
                     cs1[0] += t0; cs1[1] += t1; cs1[2] += t2; cs1[3] += t3;
                     cs2[0] += t0 * ((prelu_f(y.x, e_alpha) - c_mu.x) * c_rs.x);
@@ -296,6 +346,9 @@ __device__ __forceinline__ void gemm_epilogue(const PwArgs& a, f32x16 (&acc)[TL:
                 // profiles/r04_a_store_hazard_evidence.txt).  With a zero soffset the compiler's hazard recogniser inserts the
                 // wait states itself.
                 __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4s, f32x4v{v.x, v.y, v.z, v.w}), rsOut, vo0 + so, 0, 0);
+                // loads in their passes: keep each pass's instructions together, as the per-pass predicate did -- left free, the
+                // scheduler gathers the passes' loads and LDS reads in front and the register count goes up
+                if constexpr (Aux::Y && !Aux::PRE && !Aux::PRED_IN_PASS) __builtin_amdgcn_sched_barrier(0);
             }
         }
         __builtin_amdgcn_wave_barrier();
