@@ -12,6 +12,7 @@
 // call ends by ordering `stream` after `side_stream`, so every gradient is complete in stream order when it returns.
 #include "ctn_common.h"
 #include "../../include/ctn_hip.h"
+#include <atomic>
 #include <mutex>
 #include <stdlib.h>
 #include <vector>
@@ -26,14 +27,45 @@ struct ProbeRec { int fam; hipEvent_t e0, e1; };
 std::vector<ProbeRec> g_probe;          // guarded by g_probe_mu: a second host thread that drives the library while a recording is
 std::mutex g_probe_mu;                  // on appends its launch groups too (they are attributed by family, not by thread)
 bool g_probe_on = false;
+
+// ---- schedule-perturbation hook (tests/sched_harness.py): ONE launch group of the composite stacks is held back by a bounded delay
+// on its own stream, so that a consumer on the other stream that is not ordered behind it reads what the buffer held before.  The
+// delay kernel is one wave that stores nothing: it polls the constant-rate wall clock (s_memrealtime, 100 MHz) with s_sleep between
+// the reads until `ticks` have passed, and gives up after DELAY_MAX_POLLS reads whatever the clock says (a poll is about a
+// microsecond, so ~0.1 s at the very most: a delay is never anything like a hang).  Independent of the probe: no record is added.
+constexpr int DELAY_MAX_MICROS = 20000, DELAY_MAX_POLLS = 1 << 17;
+__global__ void __launch_bounds__(64) ctn_delay_kernel(long long ticks) {
+    const long long t0 = wall_clock64();
+    for (int i = 0; i < DELAY_MAX_POLLS; ++i) {
+        if ((long long)wall_clock64() - t0 >= ticks) break;
+        __builtin_amdgcn_s_sleep(32);           // ~2048 clocks
+    }
+}
+int delay_launch(hipStream_t st, int micros) {
+    ctn_delay_kernel<<<1, 64, 0, st>>>((long long)micros * 100);
+    return hipGetLastError() == hipSuccess ? CTN_OK : CTN_ERR_LAUNCH;
+}
+std::atomic<bool> g_delay_on{false};    // relaxed load in ProbeMark: disarmed, one predictable branch per launch group; re-checked under the lock
+int g_delay_group = -1, g_delay_micros = 0, g_delay_count = 0, g_delay_rc = CTN_OK;      // guarded by g_probe_mu
+void delay_hook(hipStream_t st) {
+    std::lock_guard<std::mutex> lk(g_probe_mu);
+    if (!g_delay_on.load(std::memory_order_relaxed)) return;
+    if (g_delay_count++ != g_delay_group) return;
+    g_delay_rc = delay_launch(st, g_delay_micros);
+    g_delay_on = false;                 // one shot: the count stays at group + 1, which tells the caller that the delay was issued
+}
+
 struct ProbeMark {
     hipEvent_t e0 = nullptr, e1 = nullptr;
     hipStream_t st;
     int fam;
     ProbeMark(int f, void* stream) : st((hipStream_t)stream), fam(f) {
-        if (!g_probe_on) return;
-        if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) { e0 = e1 = nullptr; return; }
-        hipEventRecord(e0, st);
+        if (g_probe_on) {
+            if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) e0 = e1 = nullptr;
+            else hipEventRecord(e0, st);
+        }
+        // behind e0: while a recording is on, the delayed group's own record shows the delay (how the harness checks that it lasted)
+        if (g_delay_on.load(std::memory_order_relaxed)) delay_hook(st);
     }
     ~ProbeMark() {
         if (e0 == nullptr) return;
@@ -66,6 +98,43 @@ extern "C" int ctn_probe_read(int* fam, float* us, int cap) {
     g_probe.clear();
     g_probe_on = false;
     return n;
+}
+
+extern "C" int ctn_delay(void* stream, int micros) {
+    if (micros < 0 || micros > DELAY_MAX_MICROS) {
+        ctn_set_error("ctn_delay: micros must be in [0, %d] (got %d)", DELAY_MAX_MICROS, micros);
+        return CTN_ERR_ARG;
+    }
+    if (delay_launch((hipStream_t)stream, micros) != CTN_OK) {
+        ctn_set_error("ctn_delay: launch failed");
+        return CTN_ERR_LAUNCH;
+    }
+    return CTN_OK;
+}
+
+extern "C" int ctn_delay_arm(int group, int micros) {
+    if (group < -1 || micros < 0 || micros > DELAY_MAX_MICROS) {
+        ctn_set_error("ctn_delay_arm: group must be >= -1 and micros in [0, %d] (got %d, %d)", DELAY_MAX_MICROS, group, micros);
+        return CTN_ERR_ARG;
+    }
+    std::lock_guard<std::mutex> lk(g_probe_mu);
+    g_delay_group = group;
+    g_delay_micros = micros;
+    g_delay_count = 0;
+    g_delay_rc = CTN_OK;
+    g_delay_on = true;
+    return CTN_OK;
+}
+
+extern "C" int ctn_delay_groups(void) {
+    std::lock_guard<std::mutex> lk(g_probe_mu);
+    g_delay_on = false;
+    if (g_delay_rc != CTN_OK) {
+        g_delay_rc = CTN_OK;
+        ctn_set_error("ctn_delay_groups: the armed delay could not be launched");
+        return CTN_ERR_LAUNCH;
+    }
+    return g_delay_count;
 }
 
 // lab builds only (-DCTN_EXP_SKIP; never in the product library): ctn_tune("exp_skip", mask) for TIMING experiments whose results are

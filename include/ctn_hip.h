@@ -315,6 +315,19 @@ size_t ctn_tcn_gln_bwd_workspace(int M, int B, int H, int Kp, int P, int nblocks
 int ctn_probe_enable(int on);
 int ctn_probe_read(int* fam, float* us, int cap);
 
+/* Schedule-perturbation hook for the tests of the two-stream ordering (tests/sched_harness.py); nothing in the package calls it.
+ * ctn_delay enqueues a delay kernel on `stream`: one wave that stores nothing and polls the constant-rate wall clock until `micros`
+ * microseconds have passed (0 <= micros <= 20000, CTN_ERR_ARG otherwise; a fixed cap on the polls ends it whatever the clock says).
+ * ctn_delay_arm(group, micros) resets a counter of the launch groups that ctn_tcn_*_fwd / _bwd issue (the groups of the probe above)
+ * and, with group >= 0, puts that delay ahead of the group-th one issued from now on, on the stream that group is launched to; the
+ * hook then disarms itself, the count staying at group + 1.  group = -1 only counts, until ctn_delay_groups.  ctn_delay_groups returns
+ * the count since the last arm and disarms (CTN_ERR_LAUNCH if the armed delay could not be launched).  Independent of
+ * ctn_probe_enable: no probe record is added (while a recording is on, the delayed group's own record includes the delay: it is
+ * enqueued behind that record's first event).  Disarmed (the default): one branch per launch group, no launch. */
+int ctn_delay(void* stream, int micros);
+int ctn_delay_arm(int group, int micros);
+int ctn_delay_groups(void);
+
 /* The same for a stack of cLN TemporalBlocks (norm_type = 'cLN': the causal BASELINE config), un-fused norms: per block
  * forward  1x1 -> cLN(PReLU) -> depthwise -> cLN(PReLU) -> 1x1 + residual,  backward the adjoint chain with the two weight
  * gradients on side_stream.  Saved by forward (slot per block): xs [nblocks][M,B,Kp]; h1s, n1s, ds, n2s [nblocks][M,H,Kp]

@@ -1,6 +1,8 @@
 """GPU: on-device dynamic mixing (csrc/ctn_dynmix.hip, dynmix.py) against the host restatement in dynmix_oracle.py -- levels
 within the fp64 summation-order bound, plans equal, gains and minibatches BITWISE equal, the loader's epoch / rank / resume
 semantics, graph replay, and a Solver run end to end."""
+import gc
+
 import numpy as np
 import pytest
 import torch
@@ -229,6 +231,7 @@ def test_loader_contract_epochs_ranks_and_fill(world):
     lengths = torch.zeros(B, dtype=torch.int64, device=DEV)
     c.fill(mixture, sources, lengths)
     assert torch.equal(mixture, ea[0][0]) and torch.equal(sources, ea[0][2]) and lengths.tolist() == [T] * B
+    gc.collect()                        # cyclic garbage of earlier tests must not be freed inside the window that counts allocations
     torch.cuda.synchronize()
     before = torch.cuda.memory_allocated()
     for step in range(1, 6):

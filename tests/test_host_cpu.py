@@ -44,6 +44,52 @@ def test_bad_arguments_return_error_codes_not_crashes():
         ctn.lib.call("ctn_im2col", 0, 0, 1, 100, 20, 20, 9, 64, 0)
 
 
+def test_delay_hook_parses_and_refuses_out_of_range_arguments_before_any_launch():
+    """The schedule-perturbation hook (tests/sched_harness.py): the header parses with its three prototypes, a delay outside
+    [0, 20000] microseconds or a group below -1 is refused with a message, and arming / reading the counter launches nothing (this
+    runs without a GPU)."""
+    import ctypes
+    protos = _lib.parse_header()
+    assert protos["ctn_delay"] == (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int], ["stream", "micros"])
+    assert protos["ctn_delay_arm"] == (ctypes.c_int, [ctypes.c_int, ctypes.c_int], ["group", "micros"])
+    assert protos["ctn_delay_groups"] == (ctypes.c_int, [], [])
+    L = ctn.lib.load()
+    try:
+        assert L.ctn_delay_arm(-1, 0) == 0 and L.ctn_delay_groups() == 0         # (resets the count that an earlier sweep left)
+        for micros in (-1, 20001, 2 ** 31 - 1):
+            assert L.ctn_delay(0, micros) == -1 and ctn.lib.ctn_last_error().startswith(b"ctn_delay: micros"), micros
+            assert L.ctn_delay_arm(0, micros) == -1 and ctn.lib.ctn_last_error().startswith(b"ctn_delay_arm:"), micros
+        assert L.ctn_delay_arm(-2, 100) == -1 and b"group" in ctn.lib.ctn_last_error()
+        assert L.ctn_delay_groups() == 0                    # a refused arm leaves the hook off
+        assert L.ctn_delay_arm(-1, 0) == 0 and L.ctn_delay_groups() == 0 and L.ctn_delay_groups() == 0
+        assert L.ctn_delay_arm(3, 20000) == 0 and L.ctn_delay_groups() == 0      # armed, no launch group issued, disarmed again
+    finally:
+        L.ctn_delay_groups()
+
+
+def test_schedule_harness_poisons_every_uninitialised_allocation_the_package_makes():
+    """tests/sched_harness.py can only show a race through a buffer that was poisoned: every function through which the package gets
+    uninitialised memory must be one that poisoned_allocations() wraps, and the wrappers must come off again."""
+    import re
+    import sched_harness as SH
+    pkg = os.path.join(ROOT, "conv-tasnet_amd")
+    used = set()
+    for fn in os.listdir(pkg):
+        if fn.endswith(".py"):
+            src = open(os.path.join(pkg, fn)).read()
+            used |= {"torch." + m for m in re.findall(r"\btorch\.(empty\w*)\(", src)}
+            used |= {"Tensor." + m for m in re.findall(r"\.(new_empty\w*)\(", src)}
+    assert "torch.empty" in used and "torch.empty_like" in used
+    assert used <= {"torch." + n for n in SH.UNINITIALISED} | {"Tensor." + n for n in SH.UNINITIALISED_METHODS}, used
+    before = [getattr(torch, n) for n in SH.UNINITIALISED] + [getattr(torch.Tensor, n) for n in SH.UNINITIALISED_METHODS]
+    with SH.poisoned_allocations():
+        assert all(getattr(torch, n).__name__ == "alloc" for n in SH.UNINITIALISED)
+        assert all(getattr(torch.Tensor, n).__name__ == "alloc" for n in SH.UNINITIALISED_METHODS)
+        x = torch.zeros(3)
+        assert torch.empty_like(x).shape == x.new_empty(3).shape == torch.empty(3).shape      # CPU tensors pass through untouched
+    assert before == [getattr(torch, n) for n in SH.UNINITIALISED] + [getattr(torch.Tensor, n) for n in SH.UNINITIALISED_METHODS]
+
+
 def test_tune_refuses_the_removed_keys_and_keeps_the_others():
     """The keys of the removed persistent GEMM and chained weight gradients are unknown keys now; the switches that stayed still
     take their default values (read from the sources: the mirror of the cLN dispatch and the lines that parse the environment)."""
