@@ -7,7 +7,7 @@ there (csrc/ctn_dynmix.hip: one plan launch + the gather per step, no host work,
 
 What a mixture is (include/ctn_hip.h has the contract, the tests restate it in numpy): C distinct speakers, one
 eligible utterance of each, a uniform start, levels +q / -q hundredths of a dB with q in [1, 250) as the reference's list
-generator draws them (tools/create_txt_file_like_wsj0.py:21-22), sources at unit RMS times 10^(q/2000), summed, everything
+generator draws them (tools/create_txt_file_like_wsj0.py:21-22), sources at unit level times 10^(q/2000), summed, everything
 rescaled to a peak of 0.9 (tools/matlab-code/create_wav_2speakers.m:111-112).  A minibatch is a pure function of
 (seed, rank, epoch, step): a resumed run sees the minibatches of an uninterrupted one.
 
@@ -18,8 +18,11 @@ Noise and reverberation (csrc/ctn_dynmix_aug.hip): `noise=` a second DeviceCorpu
 every mixture at an SNR drawn from `snr_db`; `rirs=` a rir.RirBank, every source convolved with a drawn room impulse response,
 the training targets being its direct path and early reflections.  Both compose with `speeds`.
 
-Differences from the MATLAB tool, on purpose: the level is the plain RMS of the whole utterance (not ITU-T P.56 active
-level) and the peak rescale is per drawn segment (not per whole utterance).
+The 0-dB level of an utterance: `level="rms"` (the default) is the plain RMS of the whole utterance; `level="active"` is the
+ITU-T P.56 active speech level, what the MATLAB tool normalises with (create_wav_2speakers.m:89-97, `activlev(s, fs, 'n')`),
+measured on the device when the corpus is built (levels.py, csrc/ctn_levels.hip): the energy over the time speech is active, so
+pauses in a file no longer move its level.  Noise corpora keep the RMS.
+Difference from the MATLAB tool, on purpose: the peak rescale is per drawn segment (not per whole utterance).
 There is no CPU fallback: like the rest of the product path the loader needs the GPU.
 """
 import json
@@ -117,8 +120,13 @@ def _ptr(t):
 class DeviceCorpus:
     """U single-speaker utterances back to back in one flat float32 device buffer, with their levels."""
 
-    def __init__(self, arrays, speakers, device, sample_rates=None, target_rate=None):
+    def __init__(self, arrays, speakers, device, sample_rates=None, target_rate=None, level="rms", sample_rate=None):
         device = torch.device(device)
+        if level not in ("rms", "active"):
+            raise ValueError("level must be 'rms' or 'active', got %r" % (level,))
+        rate = target_rate if target_rate is not None else sample_rate
+        if level == "active" and rate is None:
+            raise ValueError("level='active' needs the corpus' sample rate: pass sample_rate= (or target_rate= when resampling)")
         if device.type != "cuda":
             raise ValueError("DeviceCorpus lives on the GPU: got device %s" % device)
         if len(arrays) == 0 or len(arrays) != len(speakers):
@@ -145,7 +153,13 @@ class DeviceCorpus:
         lib.call("ctn_dynmix_levels", _ptr(self.corpus), self.corpus.numel(), _ptr(self.offsets), _ptr(self.lens), len(arrays),
                  _ptr(msq), torch.cuda.current_stream(device).cuda_stream)
         self._meansq = msq.cpu().numpy()
-        self.inv_rms = torch.from_numpy(inverse_rms(self._meansq)).to(device)
+        self.level = level
+        self._level_power, self._activity = self._meansq, None
+        if level == "active":
+            from . import levels as _levels
+            out = _levels.active_level_ragged(self.corpus, offsets, lens, int(rate))
+            self._level_power, self._activity = out["level"], out["activity"]
+        self.inv_rms = torch.from_numpy(inverse_rms(self._level_power)).to(device)
         self.w = torch.from_numpy(level_table()).to(device)
         self._tables = {}
 
@@ -174,15 +188,17 @@ class DeviceCorpus:
         return out_lens, offsets
 
     @classmethod
-    def from_arrays(cls, arrays, speakers, device, sample_rates=None, target_rate=None):
-        """sample_rates (one per utterance) and target_rate: utterances at another rate are resampled on the device."""
-        return cls(arrays, speakers, device, sample_rates, target_rate)
+    def from_arrays(cls, arrays, speakers, device, sample_rates=None, target_rate=None, level="rms", sample_rate=None):
+        """sample_rates (one per utterance) and target_rate: utterances at another rate are resampled on the device.
+        level: "rms" or "active" (the ITU-T P.56 active level; needs target_rate or sample_rate, the rate of `arrays`)."""
+        return cls(arrays, speakers, device, sample_rates, target_rate, level, sample_rate)
 
     @classmethod
-    def from_manifest(cls, json_path, sample_rate, device, reader=None, resample=False):
+    def from_manifest(cls, json_path, sample_rate, device, reader=None, resample=False, level="rms"):
         """json list of (wav_path, n_samples, speaker): every file is read once and uploaded.  reader(path, sample_rate) -> x
         (default data.read_wav: a file at another rate is a ValueError).  resample=True: reader(path) -> (x, file_rate)
-        (default data.read_wav_native), files at other rates are resampled on the device; n_samples counts the FILE's samples."""
+        (default data.read_wav_native), files at other rates are resampled on the device; n_samples counts the FILE's samples.
+        level: "rms" or "active", the 0-dB level of every utterance (measured at `sample_rate`)."""
         with open(json_path, "r") as f:
             infos = json.load(f)
         if reader is None:
@@ -198,13 +214,18 @@ class DeviceCorpus:
                 raise ValueError("%s has %d samples, the manifest says %d" % (path, x.shape[0], int(n)))
             arrays.append(x)
         if resample:
-            return cls(arrays, [i[2] for i in infos], device, rates, int(sample_rate))
-        return cls(arrays, [i[2] for i in infos], device)
+            return cls(arrays, [i[2] for i in infos], device, rates, int(sample_rate), level)
+        return cls(arrays, [i[2] for i in infos], device, level=level, sample_rate=int(sample_rate))
 
     num_utterances = property(lambda self: len(self.lens_host))
     num_speakers = property(lambda self: len(set(self.speakers)))
     num_samples = property(lambda self: int(self.corpus.numel()))
     meansq = property(lambda self: self._meansq)
+    # the power an utterance's 0-dB level stands for: meansq with level="rms", the active level with "active" (inv_rms =
+    # float32(1 / sqrt(level_power)), eligible utterances have level_power > 0); activity: the active level's share of time, None
+    # with "rms"
+    level_power = property(lambda self: self._level_power)
+    activity = property(lambda self: self._activity)
 
     def device_bytes(self):
         """4 * num_samples for the audio plus the per-utterance tables (offsets, lens, inv_rms) and the level table."""
@@ -214,7 +235,7 @@ class DeviceCorpus:
         """Sampler tables for one segment length: (host dict of build_tables, spk_ptr and utt_ids on the device)."""
         key = (int(segment_len), int(num_speakers))
         if key not in self._tables:
-            host = build_tables(self.lens_host, self._meansq, self.speakers, int(segment_len), int(num_speakers))
+            host = build_tables(self.lens_host, self._level_power, self.speakers, int(segment_len), int(num_speakers))
             self._tables[key] = (host, torch.from_numpy(host["spk_ptr"]).to(self.device),
                                  torch.from_numpy(host["utt_ids"]).to(self.device))
         return self._tables[key]
@@ -237,7 +258,8 @@ class DynamicMixLoader:
     source.  The reverberation sees the drawn segment only, not the utterance before it.
     noise: None, or a DeviceCorpus of noise recordings (labels ignored): one segment under every mixture (one more Philox block
     per mixture) at an SNR drawn uniformly from the tenths of a dB in snr_db = (lo, hi), relative to the sources' 0-dB reference
-    level (unit RMS, before the plan's +-q).  The peak rescale to 0.9 covers the noisy mixture and the targets.
+    level (unit RMS or unit active level, as the corpus was built; before the plan's +-q).  The peak rescale to 0.9 covers the
+    noisy mixture and the targets.
     With either option the mix is ctn_dynmix_gather_aug, which has the chunked form only (gather_mode plays no part).
     With rirs=None and noise=None the launches and the bits are those of a loader without these arguments.
     min_speakers: None, or m in [1, num_speakers]: every mixture holds a drawn number n_b in [m, C] of speakers (one more Philox
@@ -431,6 +453,8 @@ class _Augment:
         if noise is not None:
             if noise.device != device:
                 raise ValueError("the noise corpus is on %s, the corpus on %s" % (noise.device, device))
+            if noise.level != "rms":
+                raise ValueError("a noise corpus keeps level='rms': the active level is a speech measure")
             self.lo10, self.hi10 = snr_range(snr_db)
             self.noise_ids_host = noise_table(noise.lens_host, noise.meansq, T)
             self.noise_ids = torch.from_numpy(self.noise_ids_host).to(device)

@@ -11,8 +11,8 @@ target: the direct path and the reflections of the first `early_ms` behind it (e
 fully reverberant source; 0: the direct path alone).
 
 normalize=True divides every response by sqrt(sum h^2) before the single rounding to float32, so that the reverberant source
-keeps roughly the level the plan gave it.  A deliberate approximation, like the plain RMS the levels are taken with: it is
-exact for a white source only, and the early-taps target lies below that level by the energy of the late taps.
+keeps roughly the level the plan gave it.  A deliberate approximation (and one of the RMS: a corpus built with
+level="active" sees its active level move with the tail as well): it is exact for a white source only, and the early-taps target lies below that level by the energy of the late taps.
 """
 import json
 

@@ -121,6 +121,10 @@ def build_parser():
                     "integer percent of its speed in [LO, HI], e.g. 95:105 (resampled on the device); validation never perturbs")
     ap.add_argument("--corpus-rate", default="8000", choices=["8000", "auto"], help="rate of the --dynamic-mix files: 8000 (any "
                     "other rate is an error), or auto: files at other rates are resampled to 8 kHz on the device")
+    ap.add_argument("--level", default="rms", choices=["rms", "active"], help="--dynamic-mix / --dynamic-mix-cv: the 0-dB level of "
+                    "a source: rms, the plain RMS of the whole utterance, or active, the ITU-T P.56 active speech level the wsj0-2mix "
+                    "recipe normalises with (tools/matlab-code/create_wav_2speakers.m:89-97, activlev(s, fs, 'n')), measured on the "
+                    "device; noise keeps rms")
     ap.add_argument("--checkpoint", action="store_true", help="save checkpoint_models/epochN.pth.tar under --save-folder every epoch")
     ap.add_argument("--continue-from", default="", metavar="CHECKPOINT", help="resume from this checkpoint and run --epochs + 1 "
                     "more epochs (the Solver's arithmetic); a dynamic-mixing run sees the minibatches of the uninterrupted one")
@@ -221,11 +225,11 @@ def main(argv=None):
             if a.speed_perturb:
                 from .resample import parse_speed_range
                 speeds = parse_speed_range(a.speed_perturb)
-            tr = DynamicMixLoader(DeviceCorpus.from_manifest(a.dynamic_mix, 8000, device, resample=auto), a.batch_size, a.segment_len,
-                                  num_speakers=speakers, steps_per_epoch=a.steps_per_epoch, seed=a.seed, rank=rank, speeds=speeds,
-                                  rirs=rirs, noise=noise, snr_db=snr_db, min_speakers=a.min_speakers)
+            tr = DynamicMixLoader(DeviceCorpus.from_manifest(a.dynamic_mix, 8000, device, resample=auto, level=a.level), a.batch_size,
+                                  a.segment_len, num_speakers=speakers, steps_per_epoch=a.steps_per_epoch, seed=a.seed, rank=rank,
+                                  speeds=speeds, rirs=rirs, noise=noise, snr_db=snr_db, min_speakers=a.min_speakers)
         if a.dynamic_mix_cv:
-            cv = DynamicMixLoader(DeviceCorpus.from_manifest(a.dynamic_mix_cv, 8000, device, resample=auto), a.batch_size,
+            cv = DynamicMixLoader(DeviceCorpus.from_manifest(a.dynamic_mix_cv, 8000, device, resample=auto, level=a.level), a.batch_size,
                                   a.segment_len, num_speakers=speakers, steps_per_epoch=a.cv_steps, seed=a.seed + 1, rank=rank,
                                   reshuffle=False, rirs=rirs, noise=noise, snr_db=snr_db,
                                   min_speakers=a.min_speakers if a.dynamic_mix else None)

@@ -717,8 +717,9 @@ int ctn_stream_cum_reset_slots(void* cum, const int* slots, int nslots, int M, i
  *     ctn_dynmix_gather_workspace() bytes; then the scaled samples); mode 1: one launch of B workgroups that read their
  *     segments twice (no workspace).  Same values.  A plan entry outside its utterance (u outside [0, U), start < 0 or
  *     start + T > lens[u]) is never read: that source counts as silence and peak[b] = -1.
- * Deliberate differences from create_wav_2speakers.m: the level is the plain RMS of the whole utterance, not the ITU-T P.56
- * active level (activlev.m); the peak rescale is per drawn segment, not per whole utterance; no resampling. */
+ * The 0-dB level behind inv_rms is the caller's: the plain RMS of the whole utterance (ctn_dynmix_levels) or, as
+ * create_wav_2speakers.m:89-97 has it, the ITU-T P.56 active level (ctn_active_level below: inv_rms = 1 / sqrt(level)).
+ * Deliberate difference from create_wav_2speakers.m: the peak rescale is per drawn segment, not per whole utterance. */
 int ctn_dynmix_levels(const float* corpus, long long num_samples, const long long* offsets, const long long* lens, long long U,
                       double* meansq, void* stream);
 int ctn_dynmix_plan(const int* spk_ptr, const int* utt_ids, int S, const long long* lens, const float* inv_rms, const float* w,
@@ -830,8 +831,8 @@ int ctn_stream_carry(float* buf, long long ld, long long rows, const long long* 
  *   [0, n_r) is its direct path (the host takes the first index of max |h|); rir_early[r] in [0, n_r] is the number of leading
  *   taps that make the training target (direct path and early reflections; n_r: the fully reverberant source).  The host may
  *   divide every response by sqrt(sum h^2) in fp64 before the one rounding to fp32 (rir.RirBank(normalize=True)): the
- *   reverberant source then keeps ROUGHLY the level the plan gave it -- a deliberate approximation, in the spirit of "plain RMS,
- *   not P.56": exact for white sources only, and the early-taps target is below it by the energy of the late taps.
+ *   reverberant source then keeps ROUGHLY the level the plan gave it (its RMS; the active level, where the corpus was built with
+ *   it, moves with the reverberation's tail) -- a deliberate approximation: exact for white sources only, and the early-taps target is below it by the energy of the late taps.
  * Noise: an ordinary corpus (noise, noise_offsets, noise_lens [Un], noise_inv_rms [Un]; speaker labels play no part).
  *   noise_ids [Nn] int32: the eligible noise utterances, lens[v] >= seg_len and meansq[v] > 0.  SNR in integer tenths of a dB,
  *   lo10 .. lo10 + nsnr - 1 (1 <= nsnr <= 1024), table wn [nsnr] fp32, wn[i] = 10^(-(lo10 + i) / 200) rounded from fp64 on the
@@ -1055,6 +1056,49 @@ int ctn_varpit_bwd(const float* sources, const float* estimates, const long long
 int ctn_dynmix_plan_active(long long seed, int epoch, int rank, const unsigned* step, int B, int C, int min_speakers, int* n_active,
                            void* stream);
 int ctn_dynmix_mask_active(const int* n_active, int B, int C, float* gain, void* stream);
+
+/* ---- active speech level, ITU-T P.56 method B (csrc/ctn_levels.hip) ---------------------------------------------------------------
+ * what tools/matlab-code/create_wav_2speakers.m:89-97 normalises every source with (activlev(s, fs, 'n'), default mode), for U
+ * ragged utterances in device memory: samples [num_samples] fp32, offsets [U], lens [U] int64 as for ctn_dynmix_levels.
+ * Of utterance u the device produces  ssq [U] fp64, ns [U] int64, emax [U] int32, counts [U, 20] int64;  the level itself is a
+ * few fp64 operations per utterance on the host (levels.level_from_counts).  For one utterance x[0 .. len), all in fp64:
+ *   padding   nz zeros are appended (ceil(0.35 fs)); N = len + nz samples are processed and ns = N.
+ *   band      x -> y through a first-order section, two biquads and, if use_lp, one 5th-order section (the 200 Hz high-pass and
+ *             the 5.5 kHz low-pass, 5th-order Chebyshev-II, designed on the host: levels.design), every section direct form II
+ *             transposed from zero state, every product and every sum ONE rounding, no contraction, in this order:
+ *                 first order   y = b0 x + z0;  z0 = b1 x - a1 y
+ *                 biquad        y = b0 v + z1;  z1 = (b1 v + z2) - a1 y;  z2 = b2 v - a2 y                  (v: the section's input)
+ *                 5th order     y = b0 v + z1;  zk = (bk v + z(k+1)) - ak y, k = 1 .. 4;  z5 = b5 v - a5 y
+ *   energy    p = p + y y per sample, in order, from 0 at the start of every chunk; ssq = ((0 + p_0) + p_1) + ..., chunks ascending.
+ *   envelope  s = b0 |y| + z1;  z1 = z2 - a1 s;  z2 = -(a2 s)      (b0 = (1 - g)^2, a1 = -2 g, a2 = g^2, g = exp(-1 / (0.03 fs)))
+ *   exponent  e[n] = the frexp exponent of the one-rounding product s s (fp64 denormals kept); -32768 stands for -inf where it is 0.
+ *   hangover  h[n] = max e[n - nh + 1 .. n], indices below 0 absent (nh = ceil(0.2 fs) + 1;  CH <= nh <= 9601: the device form
+ *             splits a window once, at a chunk seam, so a window shorter than a chunk is CTN_ERR_ARG: rates from 5.12 kHz up).
+ *   bins      emax = max h + 1 (-32767 if every e is -inf);  counts[j - 1] = the samples with j = min(emax - h[n], 20), j = 1 .. 20.
+ * The device form: an utterance is cut into chunks of CH = ctn_active_level_chunk() samples by its own sample index.  Every chunk
+ * runs from zero state and leaves its end state z_c (band: 5 values, 10 with the low-pass, in section order; envelope: 2); one
+ * carry per utterance forms the true start states
+ *     s_0 = 0;   s_(c+1)[r] = (((T[r][0] s_c[0] + T[r][1] s_c[1]) + ...) + T[r][S-1] s_c[S-1]) + z_c[r]
+ * with T = A^CH (column k: the state CH zero-input samples after the unit state e_k) from the host; then every chunk is rerun from
+ * s_c.  By linearity that is the sequential filter in exact arithmetic; in fp64 it is THIS computation (tests/levels_oracle.py
+ * restates both).  No pow, tan, exp or log on the device.
+ * table [131] fp64: [0,3) first-order b0 b1 a1; [3,8), [8,13) biquads b0 b1 b2 a1 a2; [13,24) 5th-order b0..b5 a1..a5 (zeros without
+ * it); [24,27) envelope b0 a1 a2; [27,127) T of the band filter, row-major S x S (S = 5 or 10); [127,131) T of the envelope.
+ * chunk_ptr [U + 1] int64: chunk_ptr[0] = 0, chunk_ptr[u + 1] - chunk_ptr[u] = ceil((lens[u] + nz) / CH), total_chunks = chunk_ptr[U].
+ * Determinism: counts and maxima are integers (their atomics are order-free) and ssq has the fixed order above, so
+ * (ssq, ns, emax, counts) of an utterance is a bitwise function of its own samples, the table, nz, nh and CH: independent of the
+ * neighbours, of U, of the launch geometry and of how a caller groups utterances into calls to bound the workspace.
+ * An entry outside the buffer (offset < 0, len < 0, offset + len > num_samples) or a chunk range that is not the one its length asks
+ * for is never read: ns[u] = -1, ssq = 0, emax = -32767, counts = 0, and nothing else changes.
+ * workspace: ctn_active_level_workspace(total_chunks, U) bytes (8-byte aligned; 2 bytes per sample for the exponents, the chunk
+ * states and energy partials; a function of total_chunks alone, U is only checked to be positive).  U <= total_chunks <= 2^24 - 1
+ * per call (one workgroup per chunk in the last launch: 17 G samples, a workspace of 36 GB; group the utterances beyond that).
+ * Six launches on `stream`; bad sizes are CTN_ERR_ARG before any launch. */
+int ctn_active_level_chunk(void);
+size_t ctn_active_level_workspace(long long total_chunks, long long U);
+int ctn_active_level(const float* samples, long long num_samples, const long long* offsets, const long long* lens,
+                     const long long* chunk_ptr, long long U, long long total_chunks, const double* table, int use_lp, int nz, int nh,
+                     double* ssq, long long* ns, int* emax, long long* counts, void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }
