@@ -9,7 +9,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libctn_hip.so")
 SOURCES = ["ctn_api.hip", "ctn_gemm.hip", "ctn_dw.hip", "ctn_cln.hip", "ctn_cumln.hip", "ctn_bn.hip", "ctn_codec.hip", "ctn_loss.hip", "ctn_optim.hip",
            "ctn_block.hip", "ctn_bss.hip", "ctn_stream.hip", "ctn_dynmix.hip", "ctn_resample.hip", "ctn_dynmix_aug.hip",
-           "ctn_longform.hip", "ctn_stoi.hip", "ctn_mixit.hip", "ctn_varpit.hip", "ctn_dynmix_active.hip", "ctn_levels.hip"]
+           "ctn_longform.hip", "ctn_stoi.hip", "ctn_stoi_grad.hip", "ctn_mixit.hip", "ctn_varpit.hip", "ctn_dynmix_active.hip", "ctn_levels.hip"]
 # -amdgpu-mfma-vgpr-form: MFMA results stay in VGPRs (unified file on gfx950), so the epilogues read them without
 # v_accvgpr_read copies -- every VALU instruction serialises with the fp32 MFMAs (profiles/r02_a_mfma_probe.txt)
 # -fno-slp-vectorize: keeps the compiler from packing adjacent scalar f32 adds / subs into v_pk_add_f32, which costs more
@@ -33,7 +33,7 @@ def _stale(target, deps):
 
 def build_library(force=False, verbose=False):
     """Compile every .hip source for gfx950 and link libctn_hip.so next to this file."""
-    hdrs = [os.path.join(CSRC, h) for h in ("ctn_common.h", "ctn_gemm_common.h", "ctn_gemm_b3.h", "ctn_dynmix_common.h", "ctn_moment_loss.h")]
+    hdrs = [os.path.join(CSRC, h) for h in ("ctn_common.h", "ctn_gemm_common.h", "ctn_gemm_b3.h", "ctn_dynmix_common.h", "ctn_moment_loss.h", "ctn_stoi_common.h")]
     objs, jobs = [], []
     os.makedirs(os.path.join(CSRC, "build"), exist_ok=True)
     for s in SOURCES:

@@ -50,7 +50,8 @@ class SyntheticLoader:
 
 def train(data, epochs, model_path, save_folder="exp/models", continue_from="", config=None, lr=1e-3,
           max_grad_norm=5, half_lr=1, early_stop=1, print_freq=10, enable_checkpoint=0, optimizer_type='adam',
-          momentum=0.0, l2=0.0, loss='pit', snr_max=30.0, inactive_snr_max=20.0):
+          momentum=0.0, l2=0.0, loss='pit', snr_max=30.0, inactive_snr_max=20.0, stoi_weight=None, stoi_extended=False,
+          sample_rate=8000):
     """data = {'tr_loader': ..., 'cv_loader': ...}.  Returns the Solver after training.
 
     loss 'pit': the reference's permutation-invariant SI-SNR against [B,C,T] sources.  loss 'mixit': mixture invariant
@@ -58,15 +59,24 @@ def train(data, epochs, model_path, save_folder="exp/models", continue_from="", 
     [B,2,T] in place of the sources (mixit.MixtureOfMixtures) and config['C'] is the number of model outputs, 2 .. 8.
     loss 'varpit': PIT with inactive sources (varpit.cal_varpit_loss, soft thresholds snr_max and inactive_snr_max dB or None)
     for loaders whose mixtures hold 1 .. config['C'] speakers, the others' sources being zeros (DynamicMixLoader(min_speakers=)).
+    loss 'pit_stoi': the PIT SI-SNR loss plus stoi_weight * (1 - mean STOI) (ESTOI with stoi_extended) under the same pairing
+    (stoi.StoiPitCriterion), for any loader of [B,C,T] sources at sample_rate Hz; stoi_weight has no default.
 
     optimizer_type 'sgd' -> FlatSGD(lr, momentum, weight_decay=l2), 'adam' -> FlatAdam(lr, weight_decay=l2)
     (src/train.py:87-98); any other value prints 'Not support optimizer' and returns None, as the reference does."""
     if optimizer_type not in ('sgd', 'adam'):
         print("Not support optimizer")
         return None
-    if loss not in ('pit', 'mixit', 'varpit'):
-        raise ValueError("loss must be 'pit' or 'mixit' or 'varpit', got %r" % (loss,))
+    if loss not in ('pit', 'mixit', 'varpit', 'pit_stoi'):
+        raise ValueError("loss must be 'pit' or 'mixit' or 'varpit' or 'pit_stoi', got %r" % (loss,))
+    if (stoi_weight is not None or stoi_extended) and loss != 'pit_stoi':
+        raise ValueError("stoi_weight and stoi_extended apply to loss 'pit_stoi' only")
     criterion = None
+    if loss == 'pit_stoi':
+        if stoi_weight is None:
+            raise ValueError("loss 'pit_stoi' needs stoi_weight: the weight of (1 - mean score) beside the SI-SNR loss in dB")
+        from .stoi import StoiPitCriterion
+        criterion = StoiPitCriterion(sample_rate, stoi_weight, stoi_extended)
     if loss == 'mixit':
         from .mixit import MixItCriterion
         criterion = MixItCriterion(snr_max)
@@ -137,10 +147,14 @@ def build_parser():
     ap.add_argument("--rir-early-ms", default="50", metavar="MS | full", help="the training targets keep the direct path and the "
                     "reflections of this many milliseconds behind it; full: the reverberant sources.  --noise, --snr, --rirs and "
                     "--rir-early-ms also reach the --dynamic-mix-cv loader (the same banks, reshuffle=False: a fixed validation set)")
-    ap.add_argument("--loss", choices=("pit", "mixit", "varpit"), default="pit", help="pit: permutation-invariant SI-SNR against "
+    ap.add_argument("--loss", choices=("pit", "mixit", "varpit", "pit_stoi"), default="pit", help="pit: permutation-invariant SI-SNR against "
                     "the sources; mixit: mixture invariant training (needs --dynamic-mix and --dynamic-mix-cv): every minibatch is a "
                     "4-speaker mixture whose two 2-speaker halves are the only references the loss sees; varpit: PIT with inactive "
-                    "sources for mixtures of --min-speakers .. --speakers talkers (needs --dynamic-mix and --dynamic-mix-cv)")
+                    "sources for mixtures of --min-speakers .. --speakers talkers (needs --dynamic-mix and --dynamic-mix-cv); pit_stoi: the "
+                    "pit loss plus --stoi-weight times (1 - mean STOI) under the same pairing, with any loader")
+    ap.add_argument("--stoi-weight", type=float, default=None, metavar="W", help="--loss pit_stoi: the weight of (1 - mean score) "
+                    "beside the SI-SNR loss in dB (required, no default)")
+    ap.add_argument("--stoi-extended", action="store_true", help="--loss pit_stoi: score with ESTOI instead of STOI")
     ap.add_argument("--mixit-outputs", type=int, default=4, metavar="M", help="--loss mixit: the number of model outputs, 2 .. 8")
     ap.add_argument("--snr-max", default="30", metavar="DB | none", help="--loss mixit / varpit: the soft threshold of the SNR loss "
                     "in dB")
@@ -199,6 +213,10 @@ def main(argv=None):
                              "criterion against isolated sources, which is not the loss being trained")
         if not 2 <= a.mixit_outputs <= 8:
             raise SystemExit("--mixit-outputs must be 2 .. 8")
+    if (a.stoi_weight is not None or a.stoi_extended) and a.loss != "pit_stoi":
+        raise SystemExit("--stoi-weight and --stoi-extended apply to --loss pit_stoi only")
+    if a.loss == "pit_stoi" and (a.stoi_weight is None or not a.stoi_weight >= 0):
+        raise SystemExit("--loss pit_stoi needs --stoi-weight W with W >= 0")
     varpit = a.loss == "varpit"
     if a.min_speakers is not None and not a.dynamic_mix:
         raise SystemExit("--min-speakers applies to --dynamic-mix only")
@@ -257,6 +275,8 @@ def main(argv=None):
         config = dict(TINY if a.tiny else PAPER, C=speakers)
         extra = dict(loss="varpit", snr_max=None if a.snr_max.lower() == "none" else float(a.snr_max),
                      inactive_snr_max=None if a.inactive_snr_max.lower() == "none" else float(a.inactive_snr_max))
+    if a.loss == "pit_stoi":
+        extra = dict(loss="pit_stoi", stoi_weight=a.stoi_weight, stoi_extended=a.stoi_extended)
     if a.norm is not None or a.causal:          # (untouched otherwise: the configurations above as they are)
         config = dict(config if config is not None else PAPER)
         if a.norm is not None:

@@ -988,6 +988,57 @@ size_t ctn_stoi_score_workspace(long long B, int C, long long E, long long T);
 int ctn_stoi_score(const double* env, const int* kcount, long long B, int C, long long E, long long T, double* d_stoi,
                    double* d_estoi, int* m_out, int* k_out, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- STOI / ESTOI as a training loss: the backward pass in fp64 (csrc/ctn_stoi_grad.hip) -----------------------------------------
+ * The gradient of the scores above with respect to the ESTIMATE's samples (M. Kolbaek et al., "Monaural Speech Enhancement Using
+ * Deep Neural Networks by Maximizing a Short-Time Objective Intelligibility Measure", ICASSP 2018; S.-W. Fu et al., "End-to-End
+ * Waveform Utterance Enhancement for Direct Evaluation Metrics Optimization", IEEE/ACM TASLP 26(9), 2018).  Only chosen pairs are
+ * differentiated: est_of_ref [B,C] int32 on the device pairs reference c of utterance b with estimate row est_of_ref[b,c] (clamped
+ * to [0, E); the rows need not form a permutation).  A pair is laid out as an utterance of its own: P = B * C pair rows p = b C + c
+ * of one reference and one estimate, so the stage buffers are those of the forward stages called with (B, C, E) = (P, 1, 1):
+ * keep_idx [P,NF], kcount [P], env [P,2,15,MF] (set 0 the reference, set 1 the estimate), and the forward values are bitwise
+ * ctn_stoi_eval's for that pair.  Everything that depends on the reference alone is constant (energies, keep mask, index table,
+ * reference envelopes, clip bound); a cell the forward clipped (alpha y > bound) passes nothing through alpha y, the dependence
+ * of alpha on y is differentiated; a norm or an envelope that is exactly 0 passes 0; the eps terms are the forward's; a pair with
+ * M < 30 has gradient 0; samples at t >= lengths[b] are never read and get gradient 0.  All arithmetic fp64, every sum in a fixed
+ * order that depends on the pair alone; no atomics, no host read-back, no synchronisation: graph-capturable.
+ *   ctn_stoi_score_bwd: g_env [P,15,MF] fp64 = d(w_stoi[p] stoi_p + w_estoi[p] estoi_p) / d env[p,1] (0 at frames >= M); w_stoi,
+ *     w_estoi [P] fp64 on the device; a weight of 0 skips that measure.  One thread per segment writes the 15 x 30 cell gradients
+ *     of its segment, a second kernel sums the segments over a frame in ascending order.  workspace: ctn_stoi_score_bwd_workspace().
+ *   ctn_stoi_bands_bwd: g10 [P,T] fp64, the gradient with respect to the pair's 10 kHz estimate row est_p [P,T] fp32 (lengths_p
+ *     [P] int64).  The compacted windowed frames are rebuilt and their spectra recomputed as in ctn_stoi_bands; g_X = g_env X / env;
+ *     the transposed DFT-matrix product on v_mfma_f64_16x16x4_f64; then window, overlap-add and compaction are undone in gather
+ *     form (ascending frame order).  workspace: ctn_stoi_bands_bwd_workspace().
+ *   ctn_resample_rows_adjoint_f64: g_est [B,E,T] fp32 (and g_sum [B,E,T] fp64, nullable: the value before the one rounding):
+ *     g_est[b,e,i] = sum over c with est_of_ref[b,c] = e, ascending, of sum_t h[(t down) % up][i - (t down) / up + W - 1] g10[b,c,t],
+ *     t ascending, fp64 fused multiply-adds: the transpose of ctn_resample_ragged's tap table h [up, 2W] as a linear map from T
+ *     samples to T10 = ceil(T up / down).  lengths [B] are at the estimate's rate; i >= lengths[b] gives 0.  up = down = 1
+ *     (T10 = T, h unused): the sum over c alone.  It needs no workspace: ctn_resample_rows_adjoint_workspace() is 0 for every size
+ *     and stands beside the other stages' workspace functions.
+ *   ctn_stoi_pairs_fwd: ref [B,C,T], est [B,E,T], lengths [B], all at 10 kHz -> d_stoi, d_estoi [B,C] fp64, m_out [B,C] int32
+ *     (nullable); workspace (ctn_stoi_pairs_workspace(B, C, T) bytes) keeps what the backward pass needs.
+ *   ctn_stoi_pairs_bwd: score, bands and adjoint in one call from the forward's workspace (sized for T10) -> g_est [B,E,T] at the
+ *     estimate's own rate; workspace: ctn_stoi_pairs_bwd_workspace(B, C, T10).
+ * B * C <= 65535, B * E <= 65535, C <= 64, T, T10 <= 2^30, up / down in lowest terms.  Arguments are checked before any launch. */
+size_t ctn_stoi_score_bwd_workspace(long long P, long long T);
+int ctn_stoi_score_bwd(const double* env, const int* kcount, const double* w_stoi, const double* w_estoi, long long P, long long T,
+                       double* g_env, void* workspace, size_t workspace_bytes, void* stream);
+size_t ctn_stoi_bands_bwd_workspace(long long P, long long T);
+int ctn_stoi_bands_bwd(const float* est_p, const long long* lengths_p, const int* keep_idx, const int* kcount, const double* env,
+                       const double* g_env, long long P, long long T, double* g10, void* workspace, size_t workspace_bytes,
+                       void* stream);
+size_t ctn_resample_rows_adjoint_workspace(long long B, int C, long long E, long long T);
+int ctn_resample_rows_adjoint_f64(const double* g10, const int* est_of_ref, const long long* lengths, long long B, int C, long long E,
+                                  long long T, long long T10, int up, int down, const float* h, int W, float* g_est, double* g_sum,
+                                  void* stream);
+size_t ctn_stoi_pairs_workspace(long long B, int C, long long T);
+size_t ctn_stoi_pairs_bwd_workspace(long long B, int C, long long T);
+int ctn_stoi_pairs_fwd(const float* ref, const float* est, const long long* lengths, const int* est_of_ref, long long B, int C,
+                       long long E, long long T, double* d_stoi, double* d_estoi, int* m_out, void* workspace,
+                       size_t workspace_bytes, void* stream);
+int ctn_stoi_pairs_bwd(const void* fwd_workspace, size_t fwd_workspace_bytes, const double* w_stoi, const double* w_estoi,
+                       const int* est_of_ref, const long long* lengths, long long B, int C, long long E, long long T, long long T10,
+                       int up, int down, const float* h, int W, float* g_est, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- mixture invariant training loss (csrc/ctn_mixit.hip) --------------------------------------------------------------------
  * S. Wisdom et al., "Unsupervised Sound Separation Using Mixture Invariant Training", NeurIPS 2020 (MixIT), with the paper's
  * soft-thresholded SNR (no mean removal: SNR, not SI-SNR).  mixtures: [B,2,T] fp32, the two reference mixtures; estimates:
