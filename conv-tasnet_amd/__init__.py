@@ -21,5 +21,7 @@ from . import mixit  # noqa: F401
 from .mixit import cal_mixit_loss, remix, pair_batch, MixtureOfMixtures, MixItCriterion  # noqa: F401
 from . import varpit  # noqa: F401
 from .varpit import cal_varpit_loss, VarPitCriterion, output_levels, count_sources, evaluate_variable  # noqa: F401
+from . import assign  # noqa: F401
+from .assign import cal_assign_loss, linear_assignment, reorder_estimate, AssignPitCriterion  # noqa: F401
 
 __version__ = "0.1.0"

@@ -11,12 +11,14 @@ ESTOI (stoi.py, csrc/ctn_stoi.hip) the same way: one stoi_both call per batch, t
 import numpy as np
 import torch
 
+from .assign import cal_assign_loss, reorder_estimate
 from .bss_eval import bss_eval_batch, sdr_improvement
 from .conv_tasnet import ConvTasNet
 from .pit_criterion import cal_loss
 from .stoi import stoi_both, stoi_improvement
 from .utils import remove_pad
 
+PIT_MAX_SOURCES = 6          # cal_loss enumerates C! permutations up to here; beyond, evaluate_loader pairs with assign.py
 
 def cal_SISNR(ref_sig, out_sig, eps=1e-8):
     """Scale-invariant SNR in dB of one signal pair, float64 numpy (src/evaluate.py:114-130)."""
@@ -33,6 +35,11 @@ def cal_SISNRi(src_ref, src_est, mix):
     """Mean SI-SNR improvement over using the mixture itself; two speakers, like src/evaluate.py:94-111."""
     gains = [cal_SISNR(src_ref[c], src_est[c]) - cal_SISNR(src_ref[c], mix) for c in range(2)]
     return (gains[0] + gains[1]) / 2
+
+
+def cal_SISNRi_all(src_ref, src_est, mix):
+    """Mean SI-SNR improvement over all C speakers of src_ref, src_est [C, n] (cal_SISNRi is the reference's two)."""
+    return float(np.mean([cal_SISNR(r, o) - cal_SISNR(r, mix) for r, o in zip(src_ref, src_est)]))
 
 
 def cal_SDRi(src_ref, src_est, mix):
@@ -70,7 +77,9 @@ def evaluate_loader(model, data_loader, use_cuda=True, verbose=True, calc_sdr=Fa
     SDRs come out of the same call).  With calc_stoi the return value is followed by (average STOI, average ESTOI, average
     STOI improvement over the mixture): every batch scored by one stoi_both call at `sample_rate` on the reordered estimates
     plus the mixture row, an utterance's STOI / ESTOI being the mean over its speakers.  `model` is a ConvTasNet or a checkpoint
-    path."""
+    path.  Up to 6 speakers the pairing is cal_loss's, as ever; for more it comes from assign.cal_assign_loss, the estimates are put
+    into their references' order by assign.reorder_estimate (the inverse permutation), and an utterance's SI-SNRi is the mean over
+    all its speakers; calc_sdr and calc_stoi keep their own limits on C."""
     if isinstance(model, str):
         model = ConvTasNet.load_model(model)
     model.eval()
@@ -86,7 +95,12 @@ def evaluate_loader(model, data_loader, use_cuda=True, verbose=True, calc_sdr=Fa
             mixture_lengths = mixture_lengths.to(dev)
             padded_source = padded_source.to(dev)
             estimate_source = model(padded_mixture)
-            _, _, _, reorder = cal_loss(padded_source, estimate_source, mixture_lengths)
+            many = padded_source.size(1) > PIT_MAX_SOURCES
+            if many:                                         # beyond cal_loss's C! search: the assignment solver, and its inverse
+                _, _, _, perm = cal_assign_loss(padded_source, estimate_source, mixture_lengths)
+                reorder = reorder_estimate(estimate_source, perm)
+            else:
+                _, _, _, reorder = cal_loss(padded_source, estimate_source, mixture_lengths)
             mixture = remove_pad(padded_mixture, mixture_lengths)
             source = remove_pad(padded_source, mixture_lengths)
             est = remove_pad(reorder, mixture_lengths)       # NOTE: the reordered estimate, as the reference does
@@ -113,7 +127,8 @@ def evaluate_loader(model, data_loader, use_cuda=True, verbose=True, calc_sdr=Fa
                     total_stoii += scores[2][u]
                     if verbose:
                         print("\tSTOI=%.3f ESTOI=%.3f" % (scores[0][u], scores[1][u]))
-                v = cal_SISNRi(ref.astype(np.float64), out.astype(np.float64), mix.astype(np.float64))
+                ref, out, mix = ref.astype(np.float64), out.astype(np.float64), mix.astype(np.float64)
+                v = cal_SISNRi_all(ref, out, mix) if many else cal_SISNRi(ref, out, mix)
                 if verbose:
                     print("Utt %d\tSI-SNRi=%.2f" % (count + 1, v))
                 total += v

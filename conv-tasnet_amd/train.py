@@ -61,14 +61,16 @@ def train(data, epochs, model_path, save_folder="exp/models", continue_from="", 
     for loaders whose mixtures hold 1 .. config['C'] speakers, the others' sources being zeros (DynamicMixLoader(min_speakers=)).
     loss 'pit_stoi': the PIT SI-SNR loss plus stoi_weight * (1 - mean STOI) (ESTOI with stoi_extended) under the same pairing
     (stoi.StoiPitCriterion), for any loader of [B,C,T] sources at sample_rate Hz; stoi_weight has no default.
+    loss 'pit_assign': the 'pit' loss with the C! search replaced by an exact assignment solver on the device
+    (assign.AssignPitCriterion), for config['C'] = 2 .. 16 speakers and any loader of [B,C,T] sources.
 
     optimizer_type 'sgd' -> FlatSGD(lr, momentum, weight_decay=l2), 'adam' -> FlatAdam(lr, weight_decay=l2)
     (src/train.py:87-98); any other value prints 'Not support optimizer' and returns None, as the reference does."""
     if optimizer_type not in ('sgd', 'adam'):
         print("Not support optimizer")
         return None
-    if loss not in ('pit', 'mixit', 'varpit', 'pit_stoi'):
-        raise ValueError("loss must be 'pit' or 'mixit' or 'varpit' or 'pit_stoi', got %r" % (loss,))
+    if loss not in ('pit', 'mixit', 'varpit', 'pit_stoi', 'pit_assign'):
+        raise ValueError("loss must be 'pit' or 'mixit' or 'varpit' or 'pit_stoi' or 'pit_assign', got %r" % (loss,))
     if (stoi_weight is not None or stoi_extended) and loss != 'pit_stoi':
         raise ValueError("stoi_weight and stoi_extended apply to loss 'pit_stoi' only")
     criterion = None
@@ -83,6 +85,12 @@ def train(data, epochs, model_path, save_folder="exp/models", continue_from="", 
     if loss == 'varpit':
         from .varpit import VarPitCriterion
         criterion = VarPitCriterion(snr_max, inactive_snr_max)
+    if loss == 'pit_assign':
+        from .assign import AssignPitCriterion, MAX_SOURCES, MIN_SOURCES
+        n_out = (PAPER if config is None else config)['C']
+        if not MIN_SOURCES <= n_out <= MAX_SOURCES:
+            raise ValueError("loss 'pit_assign' takes %d .. %d speakers, config['C'] = %r" % (MIN_SOURCES, MAX_SOURCES, n_out))
+        criterion = AssignPitCriterion()
     world, rank, device = parallel.init_distributed()
     cfg = dict(PAPER if config is None else config)
     torch.manual_seed(0)
@@ -147,11 +155,13 @@ def build_parser():
     ap.add_argument("--rir-early-ms", default="50", metavar="MS | full", help="the training targets keep the direct path and the "
                     "reflections of this many milliseconds behind it; full: the reverberant sources.  --noise, --snr, --rirs and "
                     "--rir-early-ms also reach the --dynamic-mix-cv loader (the same banks, reshuffle=False: a fixed validation set)")
-    ap.add_argument("--loss", choices=("pit", "mixit", "varpit", "pit_stoi"), default="pit", help="pit: permutation-invariant SI-SNR against "
+    ap.add_argument("--loss", choices=("pit", "mixit", "varpit", "pit_stoi", "pit_assign"), default="pit", help="pit: permutation-invariant SI-SNR against "
                     "the sources; mixit: mixture invariant training (needs --dynamic-mix and --dynamic-mix-cv): every minibatch is a "
                     "4-speaker mixture whose two 2-speaker halves are the only references the loss sees; varpit: PIT with inactive "
                     "sources for mixtures of --min-speakers .. --speakers talkers (needs --dynamic-mix and --dynamic-mix-cv); pit_stoi: the "
-                    "pit loss plus --stoi-weight times (1 - mean STOI) under the same pairing, with any loader")
+                    "pit loss plus --stoi-weight times (1 - mean STOI) under the same pairing, with any loader; pit_assign: the pit loss for "
+                    "--speakers 2 .. 16 talkers, the pairing found by an exact assignment solver on the device instead of the C! "
+                    "search (--data-dir with s1.json .. sC.json, or the synthetic loader)")
     ap.add_argument("--stoi-weight", type=float, default=None, metavar="W", help="--loss pit_stoi: the weight of (1 - mean score) "
                     "beside the SI-SNR loss in dB (required, no default)")
     ap.add_argument("--stoi-extended", action="store_true", help="--loss pit_stoi: score with ESTOI instead of STOI")
@@ -161,7 +171,8 @@ def build_parser():
     ap.add_argument("--min-speakers", type=int, default=None, metavar="M", help="--dynamic-mix only: every mixture holds a drawn "
                     "number of speakers in [M, --speakers]; the sources of the others are zeros.  Also reaches --dynamic-mix-cv")
     ap.add_argument("--speakers", type=int, default=None, metavar="C", help="--loss varpit: the number of model outputs and the "
-                    "largest number of speakers in a mixture, 2 .. 4 (default 2)")
+                    "largest number of speakers in a mixture, 2 .. 4 (default 2); --loss pit_assign: the number of speakers, 2 .. 16 "
+                    "(default 2)")
     ap.add_argument("--inactive-snr-max", default="20", metavar="DB | none", help="--loss varpit: the soft threshold in dB of the "
                     "loss of an output paired with a silent reference")
     return ap
@@ -220,9 +231,17 @@ def main(argv=None):
     varpit = a.loss == "varpit"
     if a.min_speakers is not None and not a.dynamic_mix:
         raise SystemExit("--min-speakers applies to --dynamic-mix only")
-    if a.speakers is not None and not varpit:
-        raise SystemExit("--speakers applies to --loss varpit only")
+    assign = a.loss == "pit_assign"
+    if a.speakers is not None and not (varpit or assign):
+        raise SystemExit("--speakers applies to --loss varpit only (and to --loss pit_assign)")
     speakers = 4 if mixit else 2
+    if assign:
+        speakers = 2 if a.speakers is None else a.speakers
+        if not 2 <= speakers <= 16:
+            raise SystemExit("--loss pit_assign: --speakers must be 2 .. 16")
+        if (a.dynamic_mix or a.dynamic_mix_cv) and speakers > 4:
+            raise SystemExit("--loss pit_assign with --dynamic-mix takes --speakers 2 .. 4: the dynamic mixer plans at most 4 sources "
+                             "per mixture; train %d speakers from --data-dir (s1.json .. s%d.json)" % (speakers, speakers))
     if varpit:
         if not a.dynamic_mix or not a.dynamic_mix_cv:
             raise SystemExit("--loss varpit needs --dynamic-mix and --dynamic-mix-cv: mixtures with silent sources are drawn on "
@@ -254,18 +273,19 @@ def main(argv=None):
         if mixit:
             from .mixit import MixtureOfMixtures
             tr, cv = MixtureOfMixtures(tr), MixtureOfMixtures(cv)
+    n_src, n_syn = (dict(num_speakers=speakers), dict(C=speakers)) if assign else ({}, {})    # (every other loss: the loaders' defaults)
     if a.data_dir:
         from .data import AudioDataLoader, AudioDataset
         if tr is None:
-            tr = AudioDataLoader(AudioDataset(os.path.join(a.data_dir, "tr"), a.batch_size, segment=4.0, rank=rank, world=world),
-                                 shuffle=True, num_workers=4)
+            tr = AudioDataLoader(AudioDataset(os.path.join(a.data_dir, "tr"), a.batch_size, segment=4.0, rank=rank, world=world,
+                                              **n_src), shuffle=True, num_workers=4)
         if cv is None:
-            cv = AudioDataLoader(AudioDataset(os.path.join(a.data_dir, "cv"), 1, segment=-1, cv_maxlen=6, rank=rank, world=world),
-                                 num_workers=0)
+            cv = AudioDataLoader(AudioDataset(os.path.join(a.data_dir, "cv"), 1, segment=-1, cv_maxlen=6, rank=rank, world=world,
+                                              **n_src), num_workers=0)
     if tr is None:
-        tr = SyntheticLoader(a.batches, a.batch_size, rank=rank, world=world)
+        tr = SyntheticLoader(a.batches, a.batch_size, rank=rank, world=world, **n_syn)
     if cv is None:
-        cv = SyntheticLoader(1, a.batch_size, first_utt=10 ** 6, rank=rank, world=world)
+        cv = SyntheticLoader(1, a.batch_size, first_utt=10 ** 6, rank=rank, world=world, **n_syn)
     config = TINY if a.tiny else None
     extra = {}
     if mixit:
@@ -277,6 +297,9 @@ def main(argv=None):
                      inactive_snr_max=None if a.inactive_snr_max.lower() == "none" else float(a.inactive_snr_max))
     if a.loss == "pit_stoi":
         extra = dict(loss="pit_stoi", stoi_weight=a.stoi_weight, stoi_extended=a.stoi_extended)
+    if assign:
+        config = dict(TINY if a.tiny else PAPER, C=speakers)
+        extra = dict(loss="pit_assign")
     if a.norm is not None or a.causal:          # (untouched otherwise: the configurations above as they are)
         config = dict(config if config is not None else PAPER)
         if a.norm is not None:

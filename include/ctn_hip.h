@@ -1151,6 +1151,40 @@ int ctn_active_level(const float* samples, long long num_samples, const long lon
                      const long long* chunk_ptr, long long U, long long total_chunks, const double* table, int use_lp, int nz, int nh,
                      double* ssq, long long* ns, int* emax, long long* counts, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- optimal-assignment PIT: the SI-SNR loss for 2 .. 16 speakers, and the assignment solver (csrc/ctn_assign.hip) ---------------
+ * The loss of ctn_sisnr_pit_fwd with the C! enumeration replaced by an exact linear-assignment solver (Kuhn's Hungarian method in
+ * its shortest-augmenting-path form with row and column potentials, O(C^3)), as in Dovrat, Nachmani & Wolf, "Many-speakers single
+ * channel speech separation with optimal permutation training", 2021.  source, estimate: [B,C,T] fp32, 2 <= C <= 16; the estimate is
+ * NOT modified (unlike ctn_sisnr_pit_fwd's in-place mask); lengths: [B] int64, clamped to [0, T], only t < len counts.
+ *   pair    [B,C,C] fp32   pair[b,i,j] = (float) snr_ij, the SI-SNR in dB of estimate i against reference j: ctn_sisnr_pit_fwd's
+ *                          algebra on the centred fp64 moments, with its three EPS
+ *   perm    [B,C] int32    perm[b,i] = j: estimate i is matched to reference j; the permutation maximising sum_i pair[b,i,perm[i]]
+ *                          over the STORED fp32 values widened to fp64, so perm is a function of pair alone
+ *   max_snr [B] fp32       (float)((sum_i snr_{i,perm[i]} in fp64, ascending i) / C): one rounding
+ *   loss    [1] fp32       -(float)(mean_b of the fp64 values above, in a fixed order)
+ *   coef    [B,C,4] fp32   {A, B, mean e_i, mean s_j} of the matched pairs, for the backward pass
+ * The solver: rows enter in index order; a row's search grows an alternating tree over the reduced costs (c_ij - u_i) - v_j with
+ * c = -score when maximising, each step taking the FIRST column of least slack, until it meets a free column, and the path is
+ * flipped.  Its arithmetic is fp64 additions, subtractions and comparisons only, so tests/assign_oracle.py's solve() gives the same
+ * permutation bit for bit, ties included.  Every loop has a trip count fixed by C (at most C search steps per row, at most C
+ * steps back): NaN or infinite scores still end with some valid permutation.
+ * Forward: one sweep collects the 4C + C^2 fp64 moments per utterance and time chunk (ctn_sisnr_chunks(T) chunks; the cross
+ * moments on v_mfma_f64_16x16x4_f64 from tiles staged through LDS, 16-byte loads when T % 4 == 0 and the bases are aligned), then
+ * one wave per utterance sums the chunks, scores the pairs and solves.  An utterance's results are bitwise the same in any batch,
+ * at any batch index and for any pointer alignment.  workspace: ctn_sisnr_assign_workspace() bytes (0: bad sizes).
+ * Backward: d_estimate[b,i,t] = [t < len] * scale_b * (A (s_j[t] - mean s_j) + B (e_i[t] - mean e_i)), j = perm[b,i], scale_b =
+ * (-g_loss[0] / B + g_max[b]) / C for upstream gradients g_loss [1] and g_max [B] (either may be NULL); every fp32 operation rounded
+ * once.  Fixed-order reductions, no atomics, no read-back, no synchronisation: graph-capturable.
+ * ctn_assign_solve: the same device routine over N matrices score [N,C,C] fp32, 1 <= C <= 16, maximising (maximize != 0) or
+ * minimising -> perm [N,C] int32, one wave per matrix.
+ * Arguments are checked before any launch (CTN_ERR_ARG, CTN_ERR_WORKSPACE). */
+size_t ctn_sisnr_assign_workspace(int B, int C, int T);
+int ctn_sisnr_assign_fwd(const float* source, const float* estimate, const long long* lengths, int B, int C, int T, float* max_snr,
+                         int* perm, float* loss, float* pair, float* coef, void* workspace, size_t workspace_bytes, void* stream);
+int ctn_sisnr_assign_bwd(const float* source, const float* estimate, const long long* lengths, const int* perm, const float* coef,
+                         const float* g_loss, const float* g_max, int B, int C, int T, float* d_estimate, void* stream);
+int ctn_assign_solve(const float* score, int N, int C, int maximize, int* perm, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
