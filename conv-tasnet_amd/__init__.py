@@ -17,6 +17,8 @@ from .rir import RirBank  # noqa: F401
 from . import longform  # noqa: F401
 from .longform import separate_long, frame_ragged, stitch_ragged, plan_segments, fade_tables  # noqa: F401
 from .stoi import StoiPitCriterion, cal_stoi_loss, stoi, stoi_batch, stoi_both, stoi_improvement, stoi_pairs  # noqa: F401  (ctn.stoi is the function; the module: conv_tasnet_amd.stoi)
+from . import mrstft  # noqa: F401
+from .mrstft import MrStftPitCriterion, cal_mrstft_loss, mrstft_pairs  # noqa: F401
 from . import mixit  # noqa: F401
 from .mixit import cal_mixit_loss, remix, pair_batch, MixtureOfMixtures, MixItCriterion  # noqa: F401
 from . import varpit  # noqa: F401

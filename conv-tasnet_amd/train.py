@@ -51,7 +51,7 @@ class SyntheticLoader:
 def train(data, epochs, model_path, save_folder="exp/models", continue_from="", config=None, lr=1e-3,
           max_grad_norm=5, half_lr=1, early_stop=1, print_freq=10, enable_checkpoint=0, optimizer_type='adam',
           momentum=0.0, l2=0.0, loss='pit', snr_max=30.0, inactive_snr_max=20.0, stoi_weight=None, stoi_extended=False,
-          sample_rate=8000):
+          sample_rate=8000, mrstft_weight=None, mrstft_resolutions=None):
     """data = {'tr_loader': ..., 'cv_loader': ...}.  Returns the Solver after training.
 
     loss 'pit': the reference's permutation-invariant SI-SNR against [B,C,T] sources.  loss 'mixit': mixture invariant
@@ -63,17 +63,27 @@ def train(data, epochs, model_path, save_folder="exp/models", continue_from="", 
     (stoi.StoiPitCriterion), for any loader of [B,C,T] sources at sample_rate Hz; stoi_weight has no default.
     loss 'pit_assign': the 'pit' loss with the C! search replaced by an exact assignment solver on the device
     (assign.AssignPitCriterion), for config['C'] = 2 .. 16 speakers and any loader of [B,C,T] sources.
+    loss 'pit_mrstft': the PIT SI-SNR loss plus mrstft_weight * the multi-resolution STFT loss (spectral convergence plus
+    log-magnitude distance, mrstft.MrStftPitCriterion) under the same pairing, at mrstft_resolutions (triples (n_fft, hop,
+    win_length); None: mrstft.DEFAULT_RESOLUTIONS), for any loader of [B,C,T] sources; mrstft_weight has no default.
 
     optimizer_type 'sgd' -> FlatSGD(lr, momentum, weight_decay=l2), 'adam' -> FlatAdam(lr, weight_decay=l2)
     (src/train.py:87-98); any other value prints 'Not support optimizer' and returns None, as the reference does."""
     if optimizer_type not in ('sgd', 'adam'):
         print("Not support optimizer")
         return None
-    if loss not in ('pit', 'mixit', 'varpit', 'pit_stoi', 'pit_assign'):
-        raise ValueError("loss must be 'pit' or 'mixit' or 'varpit' or 'pit_stoi' or 'pit_assign', got %r" % (loss,))
+    if loss not in ('pit', 'mixit', 'varpit', 'pit_stoi', 'pit_assign', 'pit_mrstft'):
+        raise ValueError("loss must be 'pit' or 'mixit' or 'varpit' or 'pit_stoi' or 'pit_assign' or 'pit_mrstft', got %r" % (loss,))
     if (stoi_weight is not None or stoi_extended) and loss != 'pit_stoi':
         raise ValueError("stoi_weight and stoi_extended apply to loss 'pit_stoi' only")
+    if (mrstft_weight is not None or mrstft_resolutions is not None) and loss != 'pit_mrstft':
+        raise ValueError("mrstft_weight and mrstft_resolutions apply to loss 'pit_mrstft' only")
     criterion = None
+    if loss == 'pit_mrstft':
+        if mrstft_weight is None:
+            raise ValueError("loss 'pit_mrstft' needs mrstft_weight: the weight of the spectral loss beside the SI-SNR loss in dB")
+        from .mrstft import DEFAULT_RESOLUTIONS, MrStftPitCriterion
+        criterion = MrStftPitCriterion(mrstft_weight, DEFAULT_RESOLUTIONS if mrstft_resolutions is None else mrstft_resolutions)
     if loss == 'pit_stoi':
         if stoi_weight is None:
             raise ValueError("loss 'pit_stoi' needs stoi_weight: the weight of (1 - mean score) beside the SI-SNR loss in dB")
@@ -155,13 +165,18 @@ def build_parser():
     ap.add_argument("--rir-early-ms", default="50", metavar="MS | full", help="the training targets keep the direct path and the "
                     "reflections of this many milliseconds behind it; full: the reverberant sources.  --noise, --snr, --rirs and "
                     "--rir-early-ms also reach the --dynamic-mix-cv loader (the same banks, reshuffle=False: a fixed validation set)")
-    ap.add_argument("--loss", choices=("pit", "mixit", "varpit", "pit_stoi", "pit_assign"), default="pit", help="pit: permutation-invariant SI-SNR against "
+    ap.add_argument("--loss", choices=("pit", "mixit", "varpit", "pit_stoi", "pit_assign", "pit_mrstft"), default="pit", help="pit: permutation-invariant SI-SNR against "
                     "the sources; mixit: mixture invariant training (needs --dynamic-mix and --dynamic-mix-cv): every minibatch is a "
                     "4-speaker mixture whose two 2-speaker halves are the only references the loss sees; varpit: PIT with inactive "
                     "sources for mixtures of --min-speakers .. --speakers talkers (needs --dynamic-mix and --dynamic-mix-cv); pit_stoi: the "
                     "pit loss plus --stoi-weight times (1 - mean STOI) under the same pairing, with any loader; pit_assign: the pit loss for "
                     "--speakers 2 .. 16 talkers, the pairing found by an exact assignment solver on the device instead of the C! "
-                    "search (--data-dir with s1.json .. sC.json, or the synthetic loader)")
+                    "search (--data-dir with s1.json .. sC.json, or the synthetic loader); pit_mrstft: the pit loss plus "
+                    "--mrstft-weight times the multi-resolution STFT loss under the same pairing, with any loader")
+    ap.add_argument("--mrstft-weight", type=float, default=None, metavar="W", help="--loss pit_mrstft: the weight of the spectral "
+                    "loss (spectral convergence + log-magnitude distance, of order 1) beside the SI-SNR loss in dB (required, no default)")
+    ap.add_argument("--mrstft-resolutions", default=None, metavar="N_FFT:HOP:WIN,...", help="--loss pit_mrstft: up to 8 analysis "
+                    "resolutions, n_fft a power of two in 64 .. 2048 (default 1024:120:600,2048:240:1200,512:50:240)")
     ap.add_argument("--stoi-weight", type=float, default=None, metavar="W", help="--loss pit_stoi: the weight of (1 - mean score) "
                     "beside the SI-SNR loss in dB (required, no default)")
     ap.add_argument("--stoi-extended", action="store_true", help="--loss pit_stoi: score with ESTOI instead of STOI")
@@ -228,6 +243,17 @@ def main(argv=None):
         raise SystemExit("--stoi-weight and --stoi-extended apply to --loss pit_stoi only")
     if a.loss == "pit_stoi" and (a.stoi_weight is None or not a.stoi_weight >= 0):
         raise SystemExit("--loss pit_stoi needs --stoi-weight W with W >= 0")
+    if (a.mrstft_weight is not None or a.mrstft_resolutions is not None) and a.loss != "pit_mrstft":
+        raise SystemExit("--mrstft-weight and --mrstft-resolutions apply to --loss pit_mrstft only")
+    if a.loss == "pit_mrstft" and (a.mrstft_weight is None or not a.mrstft_weight >= 0):
+        raise SystemExit("--loss pit_mrstft needs --mrstft-weight W with W >= 0")
+    mrstft_res = None
+    if a.mrstft_resolutions is not None:
+        from .mrstft import parse_resolutions
+        try:
+            mrstft_res = parse_resolutions(a.mrstft_resolutions)
+        except ValueError as e:
+            raise SystemExit("--mrstft-resolutions: %s" % e)
     varpit = a.loss == "varpit"
     if a.min_speakers is not None and not a.dynamic_mix:
         raise SystemExit("--min-speakers applies to --dynamic-mix only")
@@ -297,6 +323,8 @@ def main(argv=None):
                      inactive_snr_max=None if a.inactive_snr_max.lower() == "none" else float(a.inactive_snr_max))
     if a.loss == "pit_stoi":
         extra = dict(loss="pit_stoi", stoi_weight=a.stoi_weight, stoi_extended=a.stoi_extended)
+    if a.loss == "pit_mrstft":
+        extra = dict(loss="pit_mrstft", mrstft_weight=a.mrstft_weight, mrstft_resolutions=mrstft_res)
     if assign:
         config = dict(TINY if a.tiny else PAPER, C=speakers)
         extra = dict(loss="pit_assign")

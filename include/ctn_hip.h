@@ -1185,6 +1185,39 @@ int ctn_sisnr_assign_bwd(const float* source, const float* estimate, const long 
                          const float* g_loss, const float* g_max, int B, int C, int T, float* d_estimate, void* stream);
 int ctn_assign_solve(const float* score, int N, int C, int maximize, int* perm, void* stream);
 
+/* ---- multi-resolution STFT loss in fp64, forward and backward (csrc/ctn_mrstft.hip) -----------------------------------------------
+ * Spectral convergence, log-magnitude and linear-magnitude distance (Yamamoto et al., "Parallel WaveGAN", ICASSP 2020; auraloss
+ * MultiResolutionSTFTLoss) of reference row c of utterance b against estimate row est_of_ref[b,c] (clamped to [0, E)), over R
+ * resolutions; resolutions: HOST pointer to R triples (n_fft, hop, win_length) of int, read before any launch.
+ * ref [B,C,T], est [B,E,T] fp32; lengths [B] int64, clamped to [0, T]: samples at t >= n = lengths[b] are never read.
+ * Accepted: 1 <= R <= 8; n_fft a power of two in 64 .. 2048; 1 <= win_length <= n_fft; 1 <= hop, ceil(win_length / hop) <= 64;
+ * B * C and B * E in 1 .. 65535, C <= 64, T in 1 .. 2^24; eps > 0.  Anything else: CTN_ERR_ARG before any launch.
+ * The transform of a row: torch.stft(x[:n], n_fft, hop, win_length, hann_window(win_length), center=True, pad_mode='reflect'):
+ * the periodic Hann window zero-padded to n_fft with (n_fft - win_length) / 2 zeros on the left, reflect padding of n_fft / 2
+ * samples about samples 0 and n - 1, F = 1 + n / hop frames.  |X| = sqrt(max(re^2 + im^2, eps)).  Over the F (n_fft / 2 + 1) bins
+ * of a (pair, resolution) cell, with D = sum (|S| - |S^|)^2 and A = sum |S|^2:
+ *   terms [B,C,R,3] fp64 = { sqrt(D) / sqrt(A) (0 where D = 0),  mean | log|S| - log|S^| |,  mean | |S| - |S^| | }.
+ * A cell with n <= n_fft / 2 (reflect padding undefined) has terms and gradient exactly 0.
+ * Forward: a radix-2 FFT in LDS (reference and estimate frame packed as one complex input), per-frame partial sums, then a
+ * fixed-order sum over a cell's frames; no spectrogram goes to memory.  workspace: ctn_mrstft_workspace() bytes; it keeps the
+ * twiddle and window tables (built on the device by the first launch of the call) and the cells' sums for the backward pass.
+ * Backward: g_terms [B,C,R,3] fp64 upstream -> g_est [B,E,T] fp32 = d sum(g_terms * terms) / d est: spectra recomputed per frame,
+ * the adjoint transform and window into a per-frame fp64 workspace (ctn_mrstft_bwd_workspace() bytes), then per sample t < n the
+ * frames that cover it and its mirror images in the padding, over the references that chose the row and the resolutions, in a
+ * fixed order in fp64, rounded once.  A clamped bin (re^2 + im^2 < eps) and a bin with |S| = |S^| pass no gradient; exactly 0 at
+ * t >= n and for rows no reference chose.  ref, est, lengths, est_of_ref, resolutions and eps must be those of the forward call.
+ * A pair's terms and gradient are bitwise the same alone or in any batch.  Fixed-order reductions, no atomics, no read-back, no
+ * synchronisation: graph-capturable.  The workspace functions return 0 for sizes or resolutions out of range. */
+size_t ctn_mrstft_workspace(long long B, int C, long long T, int R, const int* resolutions);
+size_t ctn_mrstft_bwd_workspace(long long B, int C, long long T, int R, const int* resolutions);
+int ctn_mrstft_pairs_fwd(const float* ref, const float* est, const long long* lengths, const int* est_of_ref, long long B, int C,
+                         long long E, long long T, const int* resolutions, int R, double eps, double* terms, void* workspace,
+                         size_t workspace_bytes, void* stream);
+int ctn_mrstft_pairs_bwd(const void* fwd_workspace, size_t fwd_workspace_bytes, const float* ref, const float* est,
+                         const long long* lengths, const int* est_of_ref, long long B, int C, long long E, long long T,
+                         const int* resolutions, int R, double eps, const double* g_terms, float* g_est, void* workspace,
+                         size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
