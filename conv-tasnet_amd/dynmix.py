@@ -16,7 +16,9 @@ the device (resample.py, csrc/ctn_resample.hip) before the levels are taken.  Sp
 replays every source at a drawn integer percent of its speed, resampled on the device by 100 / pct each step.
 Noise and reverberation (csrc/ctn_dynmix_aug.hip): `noise=` a second DeviceCorpus of noise recordings, one segment of it under
 every mixture at an SNR drawn from `snr_db`; `rirs=` a rir.RirBank, every source convolved with a drawn room impulse response,
-the training targets being its direct path and early reflections.  Both compose with `speeds`.
+the training targets being its direct path and early reflections.  Both compose with `speeds`.  With a bank of simulated rooms
+(rir.RirBank.from_rooms, csrc/ctn_ism.hip) `same_room=True` seats all talkers of a mixture at distinct positions of one drawn
+room, and `room_schedule=` refills the bank with new rooms at every epoch.
 
 The 0-dB level of an utterance: `level="rms"` (the default) is the plain RMS of the whole utterance; `level="active"` is the
 ITU-T P.56 active speech level, what the MATLAB tool normalises with (create_wav_2speakers.m:89-97, `activlev(s, fs, 'n')`),
@@ -265,10 +267,16 @@ class DynamicMixLoader:
     min_speakers: None, or m in [1, num_speakers]: every mixture holds a drawn number n_b in [m, C] of speakers (one more Philox
     block per mixture, csrc/ctn_dynmix_active.hip); the plan is that of min_speakers=None with gain[b, c >= n_b] = 0, so
     sources[b, c >= n_b] are zeros that add nothing to the mixture or its peak: training data for varpit.cal_varpit_loss.
-    `last_active()` returns the counts.  With None the launches and the bits are those of a loader without the argument."""
+    `last_active()` returns the counts.  With None the launches and the bits are those of a loader without the argument.
+    same_room: with a bank of simulated rooms (rir.RirBank.from_rooms, which records positions_per_room = P >= C) all sources of a
+    mixture get distinct positions of ONE drawn room (ctn_dynmix_plan_rooms in place of the RIR half of ctn_dynmix_plan_aug: same
+    key and counters, every other draw of a seed keeps its bits).  A bank without positions_per_room is a ValueError.
+    room_schedule: None, or a function epoch -> rooms (rir.draw_rooms): with reshuffle on, set_epoch(e) refills the bank in place
+    with rirs.refresh(room_schedule(e)).  With neither argument the launches and the bits are those of a loader without them."""
 
     def __init__(self, corpus, batch_size, segment_len, num_speakers=2, steps_per_epoch=1000, seed=0, rank=None,
-                 reshuffle=True, gather_mode=None, speeds=None, rirs=None, noise=None, snr_db=(-6, 3), min_speakers=None):
+                 reshuffle=True, gather_mode=None, speeds=None, rirs=None, noise=None, snr_db=(-6, 3), min_speakers=None,
+                 same_room=False, room_schedule=None):
         if rank is None:
             from . import parallel
             rank = torch.distributed.get_rank() if parallel.world_size() > 1 else parallel.env_world()[1]
@@ -310,7 +318,12 @@ class DynamicMixLoader:
             self._seg = _SegmentBuffer(self.B, self.C, self.T, dev)
         self._aug = None
         if rirs is not None or noise is not None:
-            self._aug = _Augment(self.B, self.C, self.T, dev, rirs, noise, snr_db)
+            self._aug = _Augment(self.B, self.C, self.T, dev, rirs, noise, snr_db, bool(same_room))
+        elif same_room:
+            raise ValueError("same_room=True needs rirs= (a rir.RirBank made by from_rooms)")
+        if room_schedule is not None and (rirs is None or getattr(rirs, "_ism", None) is None):
+            raise ValueError("room_schedule needs rirs= a rir.RirBank made by from_rooms")
+        self.room_schedule = room_schedule
         self.min_speakers = None if min_speakers is None else int(min_speakers)
         if self.min_speakers is not None:
             self._n_active = torch.zeros(self.B, dtype=torch.int32, device=dev)
@@ -326,6 +339,8 @@ class DynamicMixLoader:
         """Select the epoch and rewind the step word (reshuffle=False: the epoch stays 0)."""
         self.epoch = int(epoch) if self.reshuffle else 0
         self._step.zero_()
+        if self.room_schedule is not None and self.reshuffle:
+            self._aug.rirs.refresh(self.room_schedule(self.epoch))
 
     def fill(self, mixture, sources, lengths=None):
         """The next minibatch into caller buffers (float32, contiguous, on the corpus' device): the plan launch and the gather on
@@ -442,8 +457,15 @@ class _Rows:
 class _Augment:
     """The buffers and launches of the noise and reverberation stages of one loader (all allocated here, none per step)."""
 
-    def __init__(self, B, C, T, device, rirs, noise, snr_db):
-        self.B, self.C, self.T, self.rirs, self.noise = B, C, T, rirs, noise
+    def __init__(self, B, C, T, device, rirs, noise, snr_db, same_room=False):
+        self.B, self.C, self.T, self.rirs, self.noise, self.same_room = B, C, T, rirs, noise, same_room
+        if same_room:
+            P = None if rirs is None else getattr(rirs, "positions_per_room", None)
+            if P is None:
+                raise ValueError("same_room=True needs a bank that records positions_per_room (rir.RirBank.from_rooms)")
+            if not C <= P <= 64 or rirs.num_responses % P:
+                raise ValueError("same_room=True: %d positions per room for mixtures of %d (C <= P <= 64), %d responses"
+                                 % (P, C, rirs.num_responses))
         if rirs is not None:
             if rirs.device != device:
                 raise ValueError("the RIR bank is on %s, the corpus on %s" % (rirs.device, device))
@@ -468,7 +490,7 @@ class _Augment:
     def of_plan(cls, B, C, T, device, rirs, plan_rir, noise, noise_utt, noise_start, ngain):
         """The stages over a caller-written plan: nothing is drawn, so no tables."""
         self = cls.__new__(cls)
-        self.B, self.C, self.T, self.rirs, self.noise = B, C, T, rirs, noise
+        self.B, self.C, self.T, self.rirs, self.noise, self.same_room = B, C, T, rirs, noise, False
         if rirs is not None:
             self.plan_rir = plan_rir.to(device=device, dtype=torch.int32).contiguous()
             self.wet = _SegmentBuffer(B, C, T, device)
@@ -481,6 +503,13 @@ class _Augment:
 
     def plan(self, seed, epoch, rank, step, stream):
         r, n = self.rirs, self.noise
+        if self.same_room:                   # the RIR half from ctn_dynmix_plan_rooms, the noise half (if any) from plan_aug alone
+            P = r.positions_per_room
+            lib.call("ctn_dynmix_plan_rooms", seed, epoch, rank, _ptr(step), self.B, self.C, r.num_responses // P, P,
+                     _ptr(self.plan_rir), stream)
+            if n is None:
+                return
+            r = None
         if n is None:
             lib.call("ctn_dynmix_plan_aug", seed, epoch, rank, _ptr(step), self.B, self.C, self.T, r.num_responses, _ptr(self.plan_rir),
                      0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, stream)

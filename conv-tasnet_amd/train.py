@@ -160,8 +160,14 @@ def build_parser():
                     "from this manifest (the --dynamic-mix layout; labels ignored) under every mixture, at a drawn SNR")
     ap.add_argument("--snr", default="-6:3", metavar="LO:HI", help="range of the drawn SNR in dB (tenths of a dB are drawn "
                     "uniformly), relative to a source at its 0-dB reference level; with --noise")
-    ap.add_argument("--rirs", default=None, metavar="RIR_JSON | synthetic:N", help="--dynamic-mix only: convolve every source with "
-                    "a room impulse response drawn from this manifest of [wav_path, n_samples] at 8 kHz, or from N synthetic ones")
+    ap.add_argument("--rirs", default=None, metavar="RIR_JSON | synthetic:N | rooms:G[:P]", help="--dynamic-mix only: convolve every "
+                    "source with a room impulse response drawn from this manifest of [wav_path, n_samples] at 8 kHz, from N synthetic "
+                    "ones, or from G shoebox rooms simulated on the device by the image-source method with P source positions each "
+                    "(default P = 4); with P >= the number of speakers all talkers of a mixture sit in one room (same_room)")
+    ap.add_argument("--rt60", default="0.2:0.6", metavar="LO:HI", help="--rirs rooms: the range in seconds of the reverberation "
+                    "time the rooms' walls are designed for (Eyring); the simulated responses decay more slowly (DESIGN.md)")
+    ap.add_argument("--rooms-refresh", action="store_true", help="--rirs rooms: draw and simulate new rooms at every epoch "
+                    "(rir.draw_rooms(..., seed, epoch)); the validation loader keeps rooms of its own")
     ap.add_argument("--rir-early-ms", default="50", metavar="MS | full", help="the training targets keep the direct path and the "
                     "reflections of this many milliseconds behind it; full: the reverberant sources.  --noise, --snr, --rirs and "
                     "--rir-early-ms also reach the --dynamic-mix-cv loader (the same banks, reshuffle=False: a fixed validation set)")
@@ -202,20 +208,50 @@ def parse_snr(text):
     return lo, hi
 
 
-def _augmentations(a, device):
-    """(rirs, noise, snr_db) of --rirs / --noise / --snr / --rir-early-ms for the dynamic-mixing loaders."""
+def parse_rooms(text):
+    """'rooms:G[:P]' -> (G, P), P = 4 by default (train.py --rirs)."""
+    parts = str(text).split(":")
+    try:
+        if parts[0] != "rooms" or not 2 <= len(parts) <= 3:
+            raise ValueError
+        G, P = int(parts[1]), int(parts[2]) if len(parts) == 3 else 4
+    except ValueError:
+        raise ValueError("simulated rooms are rooms:G or rooms:G:P, got %r" % (text,))
+    if G < 1 or not 1 <= P <= 64:
+        raise ValueError("rooms:G:P needs G >= 1 and 1 <= P <= 64, got %r" % (text,))
+    return G, P
+
+
+def _augmentations(a, device, speakers=2):
+    """(rirs, noise, snr_db, rooms) of --rirs / --noise / --snr / --rir-early-ms for the dynamic-mixing loaders; rooms: the extra
+    loader arguments of --rirs rooms:G[:P] as (train kwargs, cv kwargs), two empty dicts otherwise."""
     from .dynmix import DeviceCorpus
+    import numpy as np
     from . import rir as _rir
     rirs = noise = None
+    rooms = ({}, {})
     if a.rirs:
         early = None if a.rir_early_ms == "full" else float(a.rir_early_ms)
-        if a.rirs.startswith("synthetic:"):
+        if a.rirs.startswith("rooms:"):
+            G, P = parse_rooms(a.rirs)
+            try:
+                rt60 = parse_snr(a.rt60)                                    # the same LO:HI form
+            except ValueError:
+                raise SystemExit("--rt60 must be LO:HI in seconds, got %r" % (a.rt60,))
+            draw = lambda seed, epoch=0: _rir.draw_rooms(G, P, 8000, rt60=rt60, seed=seed, epoch=epoch)
+            rirs = _rir.RirBank.from_rooms(draw(a.seed), device, early_ms=early, n_taps=min(_rir.MAX_TAPS, int(np.ceil(rt60[1] * 8000))))
+            same = P >= speakers
+            rooms = (dict(same_room=same, room_schedule=(lambda e: draw(a.seed, e)) if a.rooms_refresh else None),
+                     dict(same_room=same))
+            if a.rooms_refresh:                      # the validation set keeps rooms of its own: the training bank is refilled in place
+                rooms[1]["rirs"] = _rir.RirBank.from_rooms(draw(a.seed + 1), device, early_ms=early, n_taps=rirs._ism["n_taps"])
+        elif a.rirs.startswith("synthetic:"):
             rirs = _rir.RirBank.from_arrays(_rir.synthetic_bank(int(a.rirs.split(":", 1)[1]), 8000, seed=a.seed), device, 8000, early)
         else:
             rirs = _rir.RirBank.from_manifest(a.rirs, 8000, device, early_ms=early)
     if a.noise:
         noise = DeviceCorpus.from_manifest(a.noise, 8000, device, resample=a.corpus_rate == "auto")
-    return rirs, noise, parse_snr(a.snr)
+    return rirs, noise, parse_snr(a.snr), rooms
 
 
 TINY = dict(N=64, L=20, B=32, H=64, P=3, X=2, R=2, C=2)
@@ -230,6 +266,8 @@ def main(argv=None):
         raise SystemExit("--speed-perturb applies to --dynamic-mix only")
     if (a.noise or a.rirs) and not a.dynamic_mix:
         raise SystemExit("--noise and --rirs apply to --dynamic-mix only")
+    if a.rooms_refresh and not (a.rirs or "").startswith("rooms:"):
+        raise SystemExit("--rooms-refresh applies to --rirs rooms:G[:P] only")
     mixit = a.loss == "mixit"
     if mixit:
         if not a.dynamic_mix:
@@ -282,7 +320,7 @@ def main(argv=None):
     if a.dynamic_mix or a.dynamic_mix_cv:
         from .dynmix import DeviceCorpus, DynamicMixLoader
         auto = a.corpus_rate == "auto"
-        rirs, noise, snr_db = _augmentations(a, device) if a.dynamic_mix else (None, None, (-6, 3))
+        rirs, noise, snr_db, rooms = _augmentations(a, device, speakers) if a.dynamic_mix else (None, None, (-6, 3), ({}, {}))
         if a.dynamic_mix:
             speeds = None
             if a.speed_perturb:
@@ -290,12 +328,12 @@ def main(argv=None):
                 speeds = parse_speed_range(a.speed_perturb)
             tr = DynamicMixLoader(DeviceCorpus.from_manifest(a.dynamic_mix, 8000, device, resample=auto, level=a.level), a.batch_size,
                                   a.segment_len, num_speakers=speakers, steps_per_epoch=a.steps_per_epoch, seed=a.seed, rank=rank,
-                                  speeds=speeds, rirs=rirs, noise=noise, snr_db=snr_db, min_speakers=a.min_speakers)
+                                  speeds=speeds, rirs=rirs, noise=noise, snr_db=snr_db, min_speakers=a.min_speakers, **rooms[0])
         if a.dynamic_mix_cv:
             cv = DynamicMixLoader(DeviceCorpus.from_manifest(a.dynamic_mix_cv, 8000, device, resample=auto, level=a.level), a.batch_size,
                                   a.segment_len, num_speakers=speakers, steps_per_epoch=a.cv_steps, seed=a.seed + 1, rank=rank,
-                                  reshuffle=False, rirs=rirs, noise=noise, snr_db=snr_db,
-                                  min_speakers=a.min_speakers if a.dynamic_mix else None)
+                                  reshuffle=False, noise=noise, snr_db=snr_db,
+                                  min_speakers=a.min_speakers if a.dynamic_mix else None, **dict(dict(rirs=rirs), **rooms[1]))
         if mixit:
             from .mixit import MixtureOfMixtures
             tr, cv = MixtureOfMixtures(tr), MixtureOfMixtures(cv)

@@ -1218,6 +1218,61 @@ int ctn_mrstft_pairs_bwd(const void* fwd_workspace, size_t fwd_workspace_bytes, 
                          const int* resolutions, int R, double eps, const double* g_terms, float* g_est, void* workspace,
                          size_t workspace_bytes, void* stream);
 
+/* ---- image-source room simulator: shoebox rooms for the reverberant mixer (csrc/ctn_ism.hip) ---------------------------------------
+ * The image-source method of Allen & Berkley (JASA 65, 1979) for a rectangular room, one omnidirectional microphone, frequency-
+ * independent walls: R responses of n_taps taps each, h [R][n_taps] fp64, that rir.RirBank turns into a bank for ctn_dynmix_reverb.
+ * All device arithmetic is fp64, every operation ONE rounding in the order written here (no contraction into fused multiply-adds,
+ * IEEE division and square root), the device calls no transcendental function and uses no floating-point atomic: h is a BITWISE
+ * function of the tables, whatever the launch geometry.  tests/ism_oracle.py restates this text in numpy.
+ * Tables (fp64, prepared on the host; `tables` is ONE buffer of ctn_ism_table_doubles(G, R, K, Q, W) doubles, the four parts back
+ * to back; integers are stored as doubles):
+ *   room  [G][16]     L[3] the dimensions in metres, mic[3], beta[6] the wall reflection coefficients in the order x0, x1, y0, y1,
+ *                     z0, z1, each in [0, 1], N[3] the lattice bounds, N[a] = ceil(n_taps / fs * c / (2 L[a])) + 1 <= 4096, one 0.
+ *   pw    [G][6][K]   pw[g][w][0] = 1, pw[g][w][k] = pw[g][w][k-1] * beta[w]: the repeated product, K >= max N + 2.
+ *   resp  [R][4]      the room index g and src[3].  (A room of P source positions holds responses g * P .. g * P + P - 1.)
+ *   frac  [Q][2W]     the fractional-delay table: with tau = (j - W + 1) - q / Q, frac[q][j] = sinc(tau) * 0.5 * (1 + cos(pi tau / W)),
+ *                     0 where |tau| >= W (rir.design_fractional_delay).  1 <= Q <= 4096, 1 <= W <= 32.
+ *   scalars           fs_over_c = fs / c, four_pi = 4 pi as a double, 1 <= n_taps <= 8192.
+ * Images of response r in room g: the index ascends with nx outermost over [-N[0], N[0]], then ny, then nz, then
+ * p = 4 px + 2 py + pz over 0 .. 7, innermost.  For one image:
+ *   R_a  = ((1 - 2 p_a) * src[a] - mic[a]) + (2 * n_a) * L[a]                      per axis a
+ *   d2   = (Rx * Rx + Ry * Ry) + Rz * Rz;   d = sqrt(d2), correctly rounded
+ *   amp  = (((pw[0][|nx - px|] * pw[1][|nx|]) * (pw[2][|ny - py|] * pw[3][|ny|])) * (pw[4][|nz - pz|] * pw[5][|nz|])) / (d * four_pi)
+ *   tau  = d * fs_over_c;   i = floor(tau);   q = int(floor((tau - i) * Q))
+ *   (q < Q: tau - i <= 1 - 2^-52, and for Q = m * 2^e, 1 <= m < 2, the product lies within (m / 2) ulp < 1 ulp below Q and rounds
+ *   below it.)  An image with i >= n_taps contributes nothing.  Otherwise, for j in [0, 2W), tap k = i + j - W + 1 receives
+ *   amp * frac[q][j] when 0 <= k < n_taps.
+ * Taps: h[r][k] starts at +0 and the contributions are added in ascending image index, acc = acc + amp * frac[q][j], the product and
+ * the add one rounding each.  Images with amp == 0 may be skipped or added: their terms are +-0, and acc + (+-0) == acc bit for bit
+ * unless acc is -0, which it never is -- acc starts at +0, (+0) + (-0) = +0, two non-zero terms that cancel give +0 under
+ * round-to-nearest, and a non-zero acc plus a zero keeps its bits.  (The kernel skips them.)
+ * ctn_ism_simulate: tables_host is the HOST copy of the same buffer.  Every row is checked there before the launch and nothing is
+ *   launched on an error (CTN_ERR_ARG): the sizes above, the room index, 0 < L, N[a] an integer in [0, min(4096, K - 2)], at most 2^28
+ *   lattice entries 8 (2 N[0] + 1) (2 N[1] + 1) (2 N[2] + 1) per room (a walk stays within seconds), mic and src strictly inside the room, |src - mic| >= 1e-3 m, beta in [0, 1].  The kernel checks the device copy again: a bad row is
+ *   written as zeros with status[r] = -1, every other row gives status[r] = 0.  status [R] int32.
+ *   stats: null, or two int64 the CALLER zeroed: [0] += lattice entries the pruned walks visited (summed over the workgroups),
+ *   [1] += images that contributed (i < n_taps, amp != 0; each counted once).  Integer atomics; h does not depend on them.
+ *   Gather form: one workgroup of 256 threads per (response, ctn_ism_chunk_taps() consecutive taps), one tap per thread.  It walks
+ *   the lattice in index order, pruned to the spherical shell the chunk's images lie in (a tap wider on either side than the
+ *   arithmetic above can reach, so only images that contribute nothing to the chunk are skipped), compacts the images whose span
+ *   meets the chunk into an LDS list of ctn_ism_list_capacity() entries in that order (ballot and prefix, waves in fixed order),
+ *   and drains the list in order, whenever it is full and at the end (the products amp * frac[q][j] of a few images at a time are
+ *   staged in LDS, then every thread adds its tap's product or +0 per image).  No workspace, no read-back, no synchronisation.
+ * ctn_dynmix_plan_rooms: the RIR half of ctn_dynmix_plan_aug for a bank of G rooms with P source positions each (R = G * P): all
+ *   sources of a mixture in ONE room at DISTINCT positions.  Same key and counters as ctn_dynmix_plan_aug:
+ *       room of mixture b      g = (uint64(word 0 of block (512, b, step, epoch)) * G) >> 32
+ *       source c               k_c = (uint64(word 1 of block (c + 512, b, step, epoch)) * (P - c)) >> 32
+ *       pos_c = the k_c-th position, in ascending order, that sources 0 .. c - 1 have not taken;  plan_rir[b,c] = g * P + pos_c
+ *   2 <= C <= P <= 64.  It reads *step and leaves it alone.  It replaces only the RIR half: the noise half is still drawn by
+ *   ctn_dynmix_plan_aug with a null plan_rir, and every other draw of a seed keeps its bits. */
+int ctn_ism_list_capacity(void);
+int ctn_ism_chunk_taps(void);
+long long ctn_ism_table_doubles(int G, int R, int K, int Q, int W);
+int ctn_ism_simulate(const double* tables_host, const double* tables, int G, int R, int K, int Q, int W, int n_taps, double fs_over_c,
+                     double four_pi, double* h, int* status, long long* stats, void* stream);
+int ctn_dynmix_plan_rooms(long long seed, int epoch, int rank, const unsigned* step, int B, int C, int G, int P, int* plan_rir,
+                          void* stream);
+
 #ifdef __cplusplus
 }
 #endif
