@@ -10,7 +10,7 @@ LIB = os.path.join(HERE, "libctn_hip.so")
 SOURCES = ["ctn_api.hip", "ctn_gemm.hip", "ctn_dw.hip", "ctn_cln.hip", "ctn_cumln.hip", "ctn_bn.hip", "ctn_codec.hip", "ctn_loss.hip", "ctn_optim.hip",
            "ctn_block.hip", "ctn_bss.hip", "ctn_stream.hip", "ctn_dynmix.hip", "ctn_resample.hip", "ctn_dynmix_aug.hip",
            "ctn_longform.hip", "ctn_stoi.hip", "ctn_stoi_grad.hip", "ctn_mixit.hip", "ctn_varpit.hip", "ctn_dynmix_active.hip", "ctn_levels.hip",
-           "ctn_assign.hip", "ctn_mrstft.hip", "ctn_ism.hip"]
+           "ctn_assign.hip", "ctn_mrstft.hip", "ctn_ism.hip", "ctn_loudness.hip", "ctn_dynmix_loudness.hip"]
 # -amdgpu-mfma-vgpr-form: MFMA results stay in VGPRs (unified file on gfx950), so the epilogues read them without
 # v_accvgpr_read copies -- every VALU instruction serialises with the fp32 MFMAs (profiles/r02_a_mfma_probe.txt)
 # -fno-slp-vectorize: keeps the compiler from packing adjacent scalar f32 adds / subs into v_pk_add_f32, which costs more

@@ -242,8 +242,9 @@ __global__ __launch_bounds__(DM_NT) void dynmix_peak_kernel(DM_GATHER_ARGS, floa
 // chunked form, launch 2: the maximum over the mixture's workgroup maxima, then the scaled samples (recomputed from the
 // corpus: the same roundings, and 2 MB of re-reads that hit in L2 instead of 3 MB of unscaled outputs written and read back)
 template <int C>
-__global__ __launch_bounds__(DM_NT) void dynmix_write_kernel(DM_GATHER_ARGS, const float* __restrict__ wgmax, float* __restrict__ mixture,
-                                                             float* __restrict__ sources, float* __restrict__ peak) {
+__global__ __launch_bounds__(DM_NT) void dynmix_write_kernel(DM_GATHER_ARGS, const float* __restrict__ wgmax, float over,
+                                                             float* __restrict__ mixture, float* __restrict__ sources,
+                                                             float* __restrict__ peak) {
     __shared__ float scratch[DM_NT / 64];
     const int b = blockIdx.y, t0 = blockIdx.x * DM_CHUNK, nchunk = gridDim.x;
     const Rows<C> r = load_rows<C>(corpus, offsets, lens, U, plan_utt, plan_start, gain, b, T);
@@ -251,34 +252,34 @@ __global__ __launch_bounds__(DM_NT) void dynmix_write_kernel(DM_GATHER_ARGS, con
     for (int i = threadIdx.x; i < nchunk; i += DM_NT) a = fmaxf(a, wgmax[(long long)b * nchunk + i]);
     a = block_max<DM_NT>(a, scratch);
     if (blockIdx.x == 0 && threadIdx.x == 0) peak[b] = r.bad ? -1.0f : a;
-    range_write<C>(r, peak_scale(a), t0, min(T, t0 + DM_CHUNK), DM_NT, T, mixture + (long long)b * T, sources + (long long)b * C * T);
+    range_write<C>(r, peak_scale(a, over), t0, min(T, t0 + DM_CHUNK), DM_NT, T, mixture + (long long)b * T, sources + (long long)b * C * T);
 }
 
 // one-launch form: one workgroup per mixture, both phases in it
 template <int C>
-__global__ __launch_bounds__(DM_WIDE_NT) void dynmix_gather_wg_kernel(DM_GATHER_ARGS, float* __restrict__ mixture,
+__global__ __launch_bounds__(DM_WIDE_NT) void dynmix_gather_wg_kernel(DM_GATHER_ARGS, float over, float* __restrict__ mixture,
                                                                       float* __restrict__ sources, float* __restrict__ peak) {
     __shared__ float scratch[DM_WIDE_NT / 64];
     const int b = blockIdx.x;
     const Rows<C> r = load_rows<C>(corpus, offsets, lens, U, plan_utt, plan_start, gain, b, T);
     const float a = block_max<DM_WIDE_NT>(range_absmax<C>(r, 0, T, DM_WIDE_NT), scratch);
     if (threadIdx.x == 0) peak[b] = r.bad ? -1.0f : a;
-    range_write<C>(r, peak_scale(a), 0, T, DM_WIDE_NT, T, mixture + (long long)b * T, sources + (long long)b * C * T);
+    range_write<C>(r, peak_scale(a, over), 0, T, DM_WIDE_NT, T, mixture + (long long)b * T, sources + (long long)b * C * T);
 }
 
 template <int C>
-int gather_launch(DM_GATHER_ARGS, int B, float* mixture, float* sources, float* peak, float* wgmax, int mode, hipStream_t st) {
+int gather_launch(DM_GATHER_ARGS, int B, float* mixture, float* sources, float* peak, float* wgmax, int mode, float over, hipStream_t st) {
     if (mode == 1) {
-        dynmix_gather_wg_kernel<C><<<dim3(B), dim3(DM_WIDE_NT), 0, st>>>(corpus, offsets, lens, U, plan_utt, plan_start, gain, T, mixture,
-                                                                        sources, peak);
+        dynmix_gather_wg_kernel<C><<<dim3(B), dim3(DM_WIDE_NT), 0, st>>>(corpus, offsets, lens, U, plan_utt, plan_start, gain, T, over,
+                                                                        mixture, sources, peak);
         CTN_CHECK_LAUNCH("ctn_dynmix_gather");
         return CTN_OK;
     }
     const dim3 grid(ctn_cdiv(T, DM_CHUNK), B);
     dynmix_peak_kernel<C><<<grid, dim3(DM_NT), 0, st>>>(corpus, offsets, lens, U, plan_utt, plan_start, gain, T, wgmax);
     CTN_CHECK_LAUNCH("ctn_dynmix_gather (peak)");
-    dynmix_write_kernel<C><<<grid, dim3(DM_NT), 0, st>>>(corpus, offsets, lens, U, plan_utt, plan_start, gain, T, wgmax, mixture, sources,
-                                                        peak);
+    dynmix_write_kernel<C><<<grid, dim3(DM_NT), 0, st>>>(corpus, offsets, lens, U, plan_utt, plan_start, gain, T, wgmax, over, mixture,
+                                                        sources, peak);
     CTN_CHECK_LAUNCH("ctn_dynmix_gather (write)");
     return CTN_OK;
 }
@@ -342,9 +343,23 @@ size_t ctn_dynmix_gather_workspace(int B, int T) {
     return sizeof(float) * (size_t)B * (size_t)ctn_cdiv(T, DM_CHUNK);
 }
 
+int ctn_dynmix_gather_peak(const float* corpus, const long long* offsets, const long long* lens, long long U, const int* plan_utt,
+                           const long long* plan_start, const float* gain, int B, int C, int T, float* mixture, float* sources,
+                           float* peak, void* workspace, size_t workspace_bytes, int mode, int peak_mode, void* stream);
+
+// peak mode 0: the rule of every mixture before the LibriMix recipe, the same launches and bits
 int ctn_dynmix_gather(const float* corpus, const long long* offsets, const long long* lens, long long U, const int* plan_utt,
                       const long long* plan_start, const float* gain, int B, int C, int T, float* mixture, float* sources,
                       float* peak, void* workspace, size_t workspace_bytes, int mode, void* stream) {
+    return ctn_dynmix_gather_peak(corpus, offsets, lens, U, plan_utt, plan_start, gain, B, C, T, mixture, sources, peak, workspace,
+                                  workspace_bytes, mode, 0, stream);
+}
+
+// see include/ctn_hip.h ("LibriMix-recipe mixing")
+int ctn_dynmix_gather_peak(const float* corpus, const long long* offsets, const long long* lens, long long U, const int* plan_utt,
+                           const long long* plan_start, const float* gain, int B, int C, int T, float* mixture, float* sources,
+                           float* peak, void* workspace, size_t workspace_bytes, int mode, int peak_mode, void* stream) {
+    CTN_REQUIRE(peak_mode == 0 || peak_mode == 1, "ctn_dynmix_gather: peak_mode %d (0: always rescale; 1: only what would clip)", peak_mode);
     CTN_REQUIRE(corpus && offsets && lens && plan_utt && plan_start && gain && mixture && sources && peak,
                 "ctn_dynmix_gather: null pointer");
     CTN_REQUIRE(C >= 2 && C <= 4, "ctn_dynmix_gather: C = %d sources per mixture (2 .. 4)", C);
@@ -362,10 +377,11 @@ int ctn_dynmix_gather(const float* corpus, const long long* offsets, const long 
     }
     const hipStream_t st = (hipStream_t)stream;
     float* const wg = (float*)workspace;
+    const float over = peak_over(peak_mode);
     switch (C) {
-        case 2: return gather_launch<2>(corpus, offsets, lens, (int)U, plan_utt, plan_start, gain, T, B, mixture, sources, peak, wg, mode, st);
-        case 3: return gather_launch<3>(corpus, offsets, lens, (int)U, plan_utt, plan_start, gain, T, B, mixture, sources, peak, wg, mode, st);
-        default: return gather_launch<4>(corpus, offsets, lens, (int)U, plan_utt, plan_start, gain, T, B, mixture, sources, peak, wg, mode, st);
+        case 2: return gather_launch<2>(corpus, offsets, lens, (int)U, plan_utt, plan_start, gain, T, B, mixture, sources, peak, wg, mode, over, st);
+        case 3: return gather_launch<3>(corpus, offsets, lens, (int)U, plan_utt, plan_start, gain, T, B, mixture, sources, peak, wg, mode, over, st);
+        default: return gather_launch<4>(corpus, offsets, lens, (int)U, plan_utt, plan_start, gain, T, B, mixture, sources, peak, wg, mode, over, st);
     }
 }
 

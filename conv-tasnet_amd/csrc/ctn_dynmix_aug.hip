@@ -255,8 +255,9 @@ __global__ __launch_bounds__(DM_NT) void dynmix_aug_peak_kernel(AUG_GATHER_ARGS,
 
 // launch 2: the maximum over the mixture's workgroup maxima, then the scaled samples, recomputed with the same roundings
 template <int C>
-__global__ __launch_bounds__(DM_NT) void dynmix_aug_write_kernel(AUG_GATHER_ARGS, const float* __restrict__ wgmax, float* __restrict__ mixture,
-                                                                 float* __restrict__ sources, float* __restrict__ peak) {
+__global__ __launch_bounds__(DM_NT) void dynmix_aug_write_kernel(AUG_GATHER_ARGS, const float* __restrict__ wgmax, float over,
+                                                                 float* __restrict__ mixture, float* __restrict__ sources,
+                                                                 float* __restrict__ peak) {
     __shared__ float scratch[DM_NT / 64];
     const int b = blockIdx.y, t0 = blockIdx.x * DM_CHUNK, t1 = min(T, t0 + DM_CHUNK), nchunk = gridDim.x;
     const AugRows<C> r = aug_load_rows<C>(AUG_GATHER_PASS, b);
@@ -264,7 +265,7 @@ __global__ __launch_bounds__(DM_NT) void dynmix_aug_write_kernel(AUG_GATHER_ARGS
     for (int i = threadIdx.x; i < nchunk; i += DM_NT) a = fmaxf(a, wgmax[(long long)b * nchunk + i]);
     a = block_max<DM_NT>(a, scratch);
     if (blockIdx.x == 0 && threadIdx.x == 0) peak[b] = r.bad ? -1.0f : a;
-    const float scale = peak_scale(a);
+    const float scale = peak_scale(a, over);
     float* const mixrow = mixture + (long long)b * T;
     float* const srcrows = sources + (long long)b * C * T;
     const int t4 = t0 + 4 * (int)threadIdx.x;
@@ -291,11 +292,11 @@ __global__ __launch_bounds__(DM_NT) void dynmix_aug_write_kernel(AUG_GATHER_ARGS
 }
 
 template <int C>
-int aug_gather_launch(AUG_GATHER_ARGS, int B, float* mixture, float* sources, float* peak, float* wgmax, hipStream_t st) {
+int aug_gather_launch(AUG_GATHER_ARGS, int B, float* mixture, float* sources, float* peak, float* wgmax, float over, hipStream_t st) {
     const dim3 grid(ctn_cdiv(T, DM_CHUNK), B);
     dynmix_aug_peak_kernel<C><<<grid, dim3(DM_NT), 0, st>>>(AUG_GATHER_PASS, wgmax);
     CTN_CHECK_LAUNCH("ctn_dynmix_gather_aug (peak)");
-    dynmix_aug_write_kernel<C><<<grid, dim3(DM_NT), 0, st>>>(AUG_GATHER_PASS, wgmax, mixture, sources, peak);
+    dynmix_aug_write_kernel<C><<<grid, dim3(DM_NT), 0, st>>>(AUG_GATHER_PASS, wgmax, over, mixture, sources, peak);
     CTN_CHECK_LAUNCH("ctn_dynmix_gather_aug (write)");
     return CTN_OK;
 }
@@ -354,11 +355,31 @@ int ctn_dynmix_reverb(const float* corpus, const long long* offsets, const long 
     return CTN_OK;
 }
 
+int ctn_dynmix_gather_aug_peak(const float* corpus, const long long* offsets, const long long* lens, long long U, const int* plan_utt,
+                               const long long* plan_start, const float* gain, int B, int C, int T, const float* tgt_corpus,
+                               const float* noise, const long long* noise_offsets, const long long* noise_lens, long long Un,
+                               const int* noise_utt, const long long* noise_start, const float* ngain, float* mixture, float* sources,
+                               float* peak, void* workspace, size_t workspace_bytes, int peak_mode, void* stream);
+
+// peak mode 0: the rule of every mixture before the LibriMix recipe, the same launches and bits
 int ctn_dynmix_gather_aug(const float* corpus, const long long* offsets, const long long* lens, long long U, const int* plan_utt,
                           const long long* plan_start, const float* gain, int B, int C, int T, const float* tgt_corpus,
                           const float* noise, const long long* noise_offsets, const long long* noise_lens, long long Un,
                           const int* noise_utt, const long long* noise_start, const float* ngain, float* mixture, float* sources,
                           float* peak, void* workspace, size_t workspace_bytes, void* stream) {
+    return ctn_dynmix_gather_aug_peak(corpus, offsets, lens, U, plan_utt, plan_start, gain, B, C, T, tgt_corpus, noise, noise_offsets,
+                                      noise_lens, Un, noise_utt, noise_start, ngain, mixture, sources, peak, workspace, workspace_bytes, 0,
+                                      stream);
+}
+
+// see include/ctn_hip.h ("LibriMix-recipe mixing")
+int ctn_dynmix_gather_aug_peak(const float* corpus, const long long* offsets, const long long* lens, long long U, const int* plan_utt,
+                               const long long* plan_start, const float* gain, int B, int C, int T, const float* tgt_corpus,
+                               const float* noise, const long long* noise_offsets, const long long* noise_lens, long long Un,
+                               const int* noise_utt, const long long* noise_start, const float* ngain, float* mixture, float* sources,
+                               float* peak, void* workspace, size_t workspace_bytes, int peak_mode, void* stream) {
+    CTN_REQUIRE(peak_mode == 0 || peak_mode == 1, "ctn_dynmix_gather_aug: peak_mode %d (0: always rescale; 1: only what would clip)",
+                peak_mode);
     CTN_REQUIRE(corpus && offsets && lens && plan_utt && plan_start && gain && mixture && sources && peak,
                 "ctn_dynmix_gather_aug: null pointer");
     if (noise != nullptr) {
@@ -379,13 +400,14 @@ int ctn_dynmix_gather_aug(const float* corpus, const long long* offsets, const l
     const hipStream_t st = (hipStream_t)stream;
     float* const wg = (float*)workspace;
     const int Ui = (int)U, Uni = noise != nullptr ? (int)Un : 0;
+    const float over = peak_over(peak_mode);
     switch (C) {
         case 2: return aug_gather_launch<2>(corpus, offsets, lens, Ui, plan_utt, plan_start, gain, T, tgt_corpus, noise, noise_offsets, noise_lens,
-                                            Uni, noise_utt, noise_start, ngain, B, mixture, sources, peak, wg, st);
+                                            Uni, noise_utt, noise_start, ngain, B, mixture, sources, peak, wg, over, st);
         case 3: return aug_gather_launch<3>(corpus, offsets, lens, Ui, plan_utt, plan_start, gain, T, tgt_corpus, noise, noise_offsets, noise_lens,
-                                            Uni, noise_utt, noise_start, ngain, B, mixture, sources, peak, wg, st);
+                                            Uni, noise_utt, noise_start, ngain, B, mixture, sources, peak, wg, over, st);
         default: return aug_gather_launch<4>(corpus, offsets, lens, Ui, plan_utt, plan_start, gain, T, tgt_corpus, noise, noise_offsets,
-                                             noise_lens, Uni, noise_utt, noise_start, ngain, B, mixture, sources, peak, wg, st);
+                                             noise_lens, Uni, noise_utt, noise_start, ngain, B, mixture, sources, peak, wg, over, st);
     }
 }
 

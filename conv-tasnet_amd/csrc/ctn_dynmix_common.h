@@ -40,6 +40,9 @@ __device__ __forceinline__ float block_max(float v, float* scratch) {
     return r;
 }
 
-__device__ __forceinline__ float peak_scale(float a) { return a > 0.0f ? __fdiv_rn(0.9f, a) : 1.0f; }
+// The peak rule: 0.9 / a where the peak a lies above `over`, 1 elsewhere.  over = 0: every mixture is rescaled to a peak of 0.9
+// (peak mode 0, "always"); over = 0.9: only a mixture that would clip is (peak mode 1, "clip", the LibriMix rule).
+__device__ __forceinline__ float peak_scale(float a, float over) { return a > over ? __fdiv_rn(0.9f, a) : 1.0f; }
+static inline float peak_over(int peak_mode) { return peak_mode == 1 ? 0.9f : 0.0f; }
 
 }  // namespace

@@ -24,6 +24,13 @@ The 0-dB level of an utterance: `level="rms"` (the default) is the plain RMS of 
 ITU-T P.56 active speech level, what the MATLAB tool normalises with (create_wav_2speakers.m:89-97, `activlev(s, fs, 'n')`),
 measured on the device when the corpus is built (levels.py, csrc/ctn_levels.hip): the energy over the time speech is active, so
 pauses in a file no longer move its level.  Noise corpora keep the RMS.
+The LibriMix recipe (Cosentino et al. 2020), for LibriSpeech and WHAM! noise: `level="loudness"` measures every utterance's ITU-R
+BS.1770 integrated loudness on the device (loudness.py, csrc/ctn_loudness.hip) and `inv_rms` brings it to unit gated K-weighted
+power; `loudness_db=(-33, -25)` then gives every source an absolute loudness drawn uniformly from the tenths of a LU in the range
+(in place of the relative +-q), `noise_loudness_db=(-38, -30)` does the same for a noise corpus built with level="loudness" (in
+place of the SNR), and `peak="clip"` rescales a mixture to 0.9 only if its peak exceeds 0.9.  Differences from the LibriMix
+scripts, on purpose: the meter is BS.1770-4 with the Recommendation's filters and exact 100 ms hops (not pyloudnorm's), there is
+no per-source clip check before mixing, and the peak is that of the drawn segment.
 Difference from the MATLAB tool, on purpose: the peak rescale is per drawn segment (not per whole utterance).
 There is no CPU fallback: like the rest of the product path the loader needs the GPU.
 """
@@ -70,6 +77,38 @@ def snr_table(lo10, hi10):
     """wn[i] = 10^(-(lo10 + i) / 200), i = 0 .. hi10 - lo10: the noise gain at unit RMS for an SNR of (lo10 + i) / 10 dB relative
     to the sources' 0-dB reference level; float32 rounded from float64 on the host."""
     return np.array([10.0 ** (-(lo10 + i) / 200.0) for i in range(hi10 - lo10 + 1)], dtype=np.float64).astype(np.float32)
+
+
+LOUDNESS_OFFSET_DB = 0.691      # unit gated K-weighted power reads -0.691 LUFS (loudness.OFFSET_DB)
+PEAK_MODES = {"always": 0, "clip": 1}
+
+
+def loudness_range(loudness_db, name="loudness_db"):
+    """(lo, hi) in LUFS -> the integer tenths of a LU (lo10, hi10): at most 1024 values, lo10 <= hi10 (parsed like snr_range)."""
+    try:
+        lo, hi = loudness_db
+        lo10, hi10 = int(round(float(lo) * 10.0)), int(round(float(hi) * 10.0))
+    except (TypeError, ValueError, OverflowError):
+        raise ValueError("%s must be (lo, hi) in LUFS, got %r" % (name, loudness_db))
+    if lo10 > hi10:
+        raise ValueError("empty %s range %r" % (name, loudness_db))
+    if hi10 - lo10 + 1 > 1024:
+        raise ValueError("the %s range %r holds %d tenths of a LU, at most 1024 are supported" % (name, loudness_db, hi10 - lo10 + 1))
+    return lo10, hi10
+
+
+def loudness_table(lo10, hi10):
+    """wl[i] = 10^(((lo10 + i) / 10 + 0.691) / 20), i = 0 .. hi10 - lo10: the gain that takes an utterance of unit gated K-weighted
+    power (-0.691 LUFS) to (lo10 + i) / 10 LUFS; float32 rounded from float64 on the host."""
+    return np.array([10.0 ** (((lo10 + i) / 10.0 + LOUDNESS_OFFSET_DB) / 20.0) for i in range(hi10 - lo10 + 1)],
+                    dtype=np.float64).astype(np.float32)
+
+
+def peak_mode(peak):
+    """"always" -> 0 (every mixture is rescaled to a peak of 0.9), "clip" -> 1 (only one whose peak exceeds 0.9 is)."""
+    if peak not in PEAK_MODES:
+        raise ValueError("peak must be 'always' or 'clip', got %r" % (peak,))
+    return PEAK_MODES[peak]
 
 
 def noise_table(lens, meansq, segment_len):
@@ -124,11 +163,11 @@ class DeviceCorpus:
 
     def __init__(self, arrays, speakers, device, sample_rates=None, target_rate=None, level="rms", sample_rate=None):
         device = torch.device(device)
-        if level not in ("rms", "active"):
-            raise ValueError("level must be 'rms' or 'active', got %r" % (level,))
+        if level not in ("rms", "active", "loudness"):
+            raise ValueError("level must be 'rms', 'active' or 'loudness', got %r" % (level,))
         rate = target_rate if target_rate is not None else sample_rate
-        if level == "active" and rate is None:
-            raise ValueError("level='active' needs the corpus' sample rate: pass sample_rate= (or target_rate= when resampling)")
+        if level != "rms" and rate is None:
+            raise ValueError("level=%r needs the corpus' sample rate: pass sample_rate= (or target_rate= when resampling)" % level)
         if device.type != "cuda":
             raise ValueError("DeviceCorpus lives on the GPU: got device %s" % device)
         if len(arrays) == 0 or len(arrays) != len(speakers):
@@ -161,6 +200,11 @@ class DeviceCorpus:
             from . import levels as _levels
             out = _levels.active_level_ragged(self.corpus, offsets, lens, int(rate))
             self._level_power, self._activity = out["level"], out["activity"]
+        self._lufs = None
+        if level == "loudness":
+            from . import loudness as _loudness
+            out = _loudness.integrated_loudness_ragged(self.corpus, offsets, lens, int(rate))
+            self._level_power, self._lufs = out["power"], out["lufs"]
         self.inv_rms = torch.from_numpy(inverse_rms(self._level_power)).to(device)
         self.w = torch.from_numpy(level_table()).to(device)
         self._tables = {}
@@ -192,7 +236,8 @@ class DeviceCorpus:
     @classmethod
     def from_arrays(cls, arrays, speakers, device, sample_rates=None, target_rate=None, level="rms", sample_rate=None):
         """sample_rates (one per utterance) and target_rate: utterances at another rate are resampled on the device.
-        level: "rms" or "active" (the ITU-T P.56 active level; needs target_rate or sample_rate, the rate of `arrays`)."""
+        level: "rms", "active" (the ITU-T P.56 active level) or "loudness" (the ITU-R BS.1770 gated loudness); the last two need
+        target_rate or sample_rate, the rate of `arrays`."""
         return cls(arrays, speakers, device, sample_rates, target_rate, level, sample_rate)
 
     @classmethod
@@ -200,7 +245,7 @@ class DeviceCorpus:
         """json list of (wav_path, n_samples, speaker): every file is read once and uploaded.  reader(path, sample_rate) -> x
         (default data.read_wav: a file at another rate is a ValueError).  resample=True: reader(path) -> (x, file_rate)
         (default data.read_wav_native), files at other rates are resampled on the device; n_samples counts the FILE's samples.
-        level: "rms" or "active", the 0-dB level of every utterance (measured at `sample_rate`)."""
+        level: "rms", "active" or "loudness", the 0-dB level of every utterance (measured at `sample_rate`)."""
         with open(json_path, "r") as f:
             infos = json.load(f)
         if reader is None:
@@ -223,11 +268,12 @@ class DeviceCorpus:
     num_speakers = property(lambda self: len(set(self.speakers)))
     num_samples = property(lambda self: int(self.corpus.numel()))
     meansq = property(lambda self: self._meansq)
-    # the power an utterance's 0-dB level stands for: meansq with level="rms", the active level with "active" (inv_rms =
-    # float32(1 / sqrt(level_power)), eligible utterances have level_power > 0); activity: the active level's share of time, None
-    # with "rms"
+    # the power an utterance's 0-dB level stands for: meansq with level="rms", the active level with "active", the gated K-weighted
+    # power with "loudness" (inv_rms = float32(1 / sqrt(level_power)), eligible utterances have level_power > 0); activity: the
+    # active level's share of time ("active" only); lufs: the integrated loudness of every utterance ("loudness" only)
     level_power = property(lambda self: self._level_power)
     activity = property(lambda self: self._activity)
+    lufs = property(lambda self: self._lufs)
 
     def device_bytes(self):
         """4 * num_samples for the audio plus the per-utterance tables (offsets, lens, inv_rms) and the level table."""
@@ -272,11 +318,21 @@ class DynamicMixLoader:
     mixture get distinct positions of ONE drawn room (ctn_dynmix_plan_rooms in place of the RIR half of ctn_dynmix_plan_aug: same
     key and counters, every other draw of a seed keeps its bits).  A bank without positions_per_room is a ValueError.
     room_schedule: None, or a function epoch -> rooms (rir.draw_rooms): with reshuffle on, set_epoch(e) refills the bank in place
-    with rirs.refresh(room_schedule(e)).  With neither argument the launches and the bits are those of a loader without them."""
+    with rirs.refresh(room_schedule(e)).  With neither argument the launches and the bits are those of a loader without them.
+    loudness_db: None, or (lo, hi) in LUFS on a corpus built with level="loudness": every source gets an absolute loudness drawn
+    uniformly from the tenths of a LU in the range (at most 1024; one more Philox block per source, ctn_dynmix_plan_loudness behind the
+    plan): gain[b,c] = inv_rms[u] * wl[i] replaces the plan's; plan_q is still drawn and ignored, every other draw of a seed keeps its
+    bits; the masking by min_speakers comes after.  `last_loudness()` returns the drawn tenths.
+    noise_loudness_db: None, or (lo, hi) in LUFS with noise= a corpus built with level="loudness": the word that chooses the SNR
+    chooses the noise loudness instead (snr_db plays no part, the snr10 of last_aug_plan() holds its tenths of a LU),
+    ngain = noise.inv_rms[v] * wl_n[i]; noise utterance and start keep their bits.
+    peak: "always" (every mixture is rescaled to a peak of 0.9) or "clip" (scale = 0.9 / peak only where peak > 0.9, the LibriMix
+    rule), in every form of the gather; `last_peak()` is the unscaled peak either way.
+    With the three at their defaults the launches and the bits are those of a loader without them."""
 
     def __init__(self, corpus, batch_size, segment_len, num_speakers=2, steps_per_epoch=1000, seed=0, rank=None,
                  reshuffle=True, gather_mode=None, speeds=None, rirs=None, noise=None, snr_db=(-6, 3), min_speakers=None,
-                 same_room=False, room_schedule=None):
+                 same_room=False, room_schedule=None, loudness_db=None, noise_loudness_db=None, peak="always"):
         if rank is None:
             from . import parallel
             rank = torch.distributed.get_rank() if parallel.world_size() > 1 else parallel.env_world()[1]
@@ -294,6 +350,14 @@ class DynamicMixLoader:
         self.corpus, self.B, self.T, self.C = corpus, int(batch_size), int(segment_len), int(num_speakers)
         self.steps_per_epoch, self.seed, self.rank, self.reshuffle = int(steps_per_epoch), seed, rank, bool(reshuffle)
         self.gather_mode = GATHER_MODE if gather_mode is None else int(gather_mode)
+        self.peak, self.peak_mode = peak, peak_mode(peak)
+        self.loudness = None
+        if loudness_db is not None:
+            if corpus.level != "loudness":
+                raise ValueError("loudness_db needs a corpus built with level='loudness', this one has level=%r" % (corpus.level,))
+            self.loudness = loudness_range(loudness_db)
+        if noise_loudness_db is not None and (noise is None or noise.level != "loudness"):
+            raise ValueError("noise_loudness_db needs noise= a corpus built with level='loudness'")
         self.epoch = 0
         self.speeds = None
         if speeds is not None:
@@ -318,7 +382,7 @@ class DynamicMixLoader:
             self._seg = _SegmentBuffer(self.B, self.C, self.T, dev)
         self._aug = None
         if rirs is not None or noise is not None:
-            self._aug = _Augment(self.B, self.C, self.T, dev, rirs, noise, snr_db, bool(same_room))
+            self._aug = _Augment(self.B, self.C, self.T, dev, rirs, noise, snr_db, bool(same_room), noise_loudness_db, self.peak_mode)
         elif same_room:
             raise ValueError("same_room=True needs rirs= (a rir.RirBank made by from_rooms)")
         if room_schedule is not None and (rirs is None or getattr(rirs, "_ism", None) is None):
@@ -327,6 +391,9 @@ class DynamicMixLoader:
         self.min_speakers = None if min_speakers is None else int(min_speakers)
         if self.min_speakers is not None:
             self._n_active = torch.zeros(self.B, dtype=torch.int32, device=dev)
+        if self.loudness is not None:
+            self._wl = torch.from_numpy(loudness_table(*self.loudness)).to(dev)
+            self._plan_l10 = torch.zeros(self.B, self.C, dtype=torch.int32, device=dev)
 
     # Solver: loader.dataset.set_epoch(epoch).  A property, not an attribute: `self.dataset = self` is a reference cycle, and a
     # dropped loader's device buffers would then stay allocated until the cyclic collector happens to run
@@ -365,6 +432,10 @@ class DynamicMixLoader:
             lib.call("ctn_dynmix_plan", _ptr(self._spk_ptr), _ptr(self._utt_ids), len(self.tables["spk_ptr"]) - 1, _ptr(c.lens),
                      _ptr(c.inv_rms), _ptr(c.w), self.seed, self.epoch, self.rank, _ptr(self._step), B, C, T,
                      _ptr(self._plan_utt), _ptr(self._plan_start), _ptr(self._plan_q), _ptr(self._gain), stream)
+        if self.loudness is not None:                                               # behind the plan: it overwrites the plan's gains
+            lib.call("ctn_dynmix_plan_loudness", _ptr(self._plan_utt), _ptr(c.inv_rms), c.num_utterances, _ptr(self._wl),
+                     self._wl.numel(), self.loudness[0], self.seed, self.epoch, self.rank, _ptr(self._step), B, C,
+                     _ptr(self._plan_l10), _ptr(self._gain), stream)
         if self.min_speakers is not None:
             lib.call("ctn_dynmix_mask_active", _ptr(self._n_active), B, C, _ptr(self._gain), stream)
         if aug is not None:                  # speed_segments -> reverb -> gather_aug (include/ctn_hip.h: the pipeline of one step)
@@ -376,11 +447,10 @@ class DynamicMixLoader:
             aug.mix(rows, self._gain, mixture, sources, self._peak, self._ws, stream)
         elif self.speeds is not None:
             self._seg.mix(c, self._banks, self._plan_utt, self._plan_start, self._plan_pct, self._gain, mixture, sources,
-                          self._peak, self._ws, self.gather_mode, stream)
+                          self._peak, self._ws, self.gather_mode, stream, self.peak_mode)
         else:
-            lib.call("ctn_dynmix_gather", _ptr(c.corpus), _ptr(c.offsets), _ptr(c.lens), c.num_utterances, _ptr(self._plan_utt),
-                     _ptr(self._plan_start), _ptr(self._gain), B, C, T, _ptr(mixture), _ptr(sources), _ptr(self._peak),
-                     _ptr(self._ws), self._ws.numel(), self.gather_mode, stream)
+            _gather_call(c.corpus, c.offsets, c.lens, c.num_utterances, self._plan_utt, self._plan_start, self._gain, B, C, T, mixture,
+                         sources, self._peak, self._ws, self.gather_mode, self.peak_mode, stream)
         if lengths is not None:
             lengths.copy_(self._lengths)
 
@@ -398,6 +468,12 @@ class DynamicMixLoader:
         and with speeds the drawn percents plan_pct [B,C] i32 as a fifth element."""
         plan = self._plan_utt.clone(), self._plan_start.clone(), self._plan_q.clone(), self._gain.clone()
         return plan if self.speeds is None else plan + (self._plan_pct.clone(),)
+
+    def last_loudness(self):
+        """A copy of the last minibatch's drawn loudness plan_l10 [B,C] i32 in tenths of a LU (loudness_db only)."""
+        if self.loudness is None:
+            raise ValueError("this loader was built without loudness_db")
+        return self._plan_l10.clone()
 
     def last_active(self):
         """A copy of the last minibatch's speaker counts n_active [B] i32 (min_speakers only)."""
@@ -439,11 +515,21 @@ class _SegmentBuffer:
                  _ptr(plan_utt), _ptr(plan_start), _ptr(plan_pct), B, C, T, _ptr(banks.banks), banks.banks.numel(), _ptr(banks.table),
                  banks.span_cap, banks.bank_cap, _ptr(self.seg), _ptr(self.seg_utt), stream)
 
-    def mix(self, corpus, banks, plan_utt, plan_start, plan_pct, gain, mixture, sources, peak, ws, mode, stream):
+    def mix(self, corpus, banks, plan_utt, plan_start, plan_pct, gain, mixture, sources, peak, ws, mode, stream, peak_mode=0):
         B, C, T = self.B, self.C, self.T
         self.segments(corpus, banks, plan_utt, plan_start, plan_pct, stream)
-        lib.call("ctn_dynmix_gather", _ptr(self.seg), _ptr(self.offsets), _ptr(self.lens), B * C, _ptr(self.seg_utt),
-                 _ptr(self.start), _ptr(gain), B, C, T, _ptr(mixture), _ptr(sources), _ptr(peak), _ptr(ws), ws.numel(), mode, stream)
+        _gather_call(self.seg, self.offsets, self.lens, B * C, self.seg_utt, self.start, gain, B, C, T, mixture, sources, peak, ws,
+                     mode, peak_mode, stream)
+
+
+def _gather_call(data, offsets, lens, U, utt, start, gain, B, C, T, mixture, sources, peak, ws, mode, peak_mode, stream):
+    """ctn_dynmix_gather, or with another peak rule than "always" ctn_dynmix_gather_peak."""
+    args = (_ptr(data), _ptr(offsets), _ptr(lens), U, _ptr(utt), _ptr(start), _ptr(gain), B, C, T, _ptr(mixture), _ptr(sources),
+            _ptr(peak), _ptr(ws), ws.numel(), mode)
+    if peak_mode == 0:
+        lib.call("ctn_dynmix_gather", *args, stream)
+    else:
+        lib.call("ctn_dynmix_gather_peak", *args, peak_mode, stream)
 
 
 class _Rows:
@@ -457,8 +543,9 @@ class _Rows:
 class _Augment:
     """The buffers and launches of the noise and reverberation stages of one loader (all allocated here, none per step)."""
 
-    def __init__(self, B, C, T, device, rirs, noise, snr_db, same_room=False):
+    def __init__(self, B, C, T, device, rirs, noise, snr_db, same_room=False, noise_loudness_db=None, peak_mode=0):
         self.B, self.C, self.T, self.rirs, self.noise, self.same_room = B, C, T, rirs, noise, same_room
+        self.peak_mode = peak_mode
         if same_room:
             P = None if rirs is None else getattr(rirs, "positions_per_room", None)
             if P is None:
@@ -475,12 +562,20 @@ class _Augment:
         if noise is not None:
             if noise.device != device:
                 raise ValueError("the noise corpus is on %s, the corpus on %s" % (noise.device, device))
-            if noise.level != "rms":
-                raise ValueError("a noise corpus keeps level='rms': the active level is a speech measure")
-            self.lo10, self.hi10 = snr_range(snr_db)
-            self.noise_ids_host = noise_table(noise.lens_host, noise.meansq, T)
+            if noise.level != "rms" and not (noise.level == "loudness" and noise_loudness_db is not None):
+                raise ValueError("a noise corpus keeps level='rms' (the active level is a speech measure), or has level='loudness' "
+                                 "together with noise_loudness_db")
+            if noise_loudness_db is not None:        # the word that chooses the SNR chooses the noise loudness: snr10 holds its tenths
+                if noise.level != "loudness":
+                    raise ValueError("noise_loudness_db needs noise= a corpus built with level='loudness'")
+                self.lo10, self.hi10 = loudness_range(noise_loudness_db, "noise_loudness_db")
+                wn = loudness_table(self.lo10, self.hi10)
+            else:
+                self.lo10, self.hi10 = snr_range(snr_db)
+                wn = snr_table(self.lo10, self.hi10)
+            self.noise_ids_host = noise_table(noise.lens_host, noise.level_power, T)
             self.noise_ids = torch.from_numpy(self.noise_ids_host).to(device)
-            self.wn = torch.from_numpy(snr_table(self.lo10, self.hi10)).to(device)
+            self.wn = torch.from_numpy(wn).to(device)
             self.noise_utt = torch.zeros(B, dtype=torch.int32, device=device)
             self.noise_start = torch.zeros(B, dtype=torch.int64, device=device)
             self.snr10 = torch.zeros(B, dtype=torch.int32, device=device)
@@ -490,7 +585,7 @@ class _Augment:
     def of_plan(cls, B, C, T, device, rirs, plan_rir, noise, noise_utt, noise_start, ngain):
         """The stages over a caller-written plan: nothing is drawn, so no tables."""
         self = cls.__new__(cls)
-        self.B, self.C, self.T, self.rirs, self.noise, self.same_room = B, C, T, rirs, noise, False
+        self.B, self.C, self.T, self.rirs, self.noise, self.same_room, self.peak_mode = B, C, T, rirs, noise, False, 0
         if rirs is not None:
             self.plan_rir = plan_rir.to(device=device, dtype=torch.int32).contiguous()
             self.wet = _SegmentBuffer(B, C, T, device)
@@ -533,15 +628,20 @@ class _Augment:
         else:
             noise_args = (_ptr(n.corpus), _ptr(n.offsets), _ptr(n.lens), n.num_utterances, _ptr(self.noise_utt), _ptr(self.noise_start),
                           _ptr(self.ngain))
-        lib.call("ctn_dynmix_gather_aug", _ptr(rows.data), _ptr(rows.offsets), _ptr(rows.lens), rows.U, _ptr(rows.utt), _ptr(rows.start),
-                 _ptr(gain), B, C, T, _ptr(tgt), *noise_args, _ptr(mixture), _ptr(sources), _ptr(peak), _ptr(ws), ws.numel(), stream)
+        args = (_ptr(rows.data), _ptr(rows.offsets), _ptr(rows.lens), rows.U, _ptr(rows.utt), _ptr(rows.start), _ptr(gain), B, C, T,
+                _ptr(tgt)) + noise_args + (_ptr(mixture), _ptr(sources), _ptr(peak), _ptr(ws), ws.numel())
+        if self.peak_mode == 0:
+            lib.call("ctn_dynmix_gather_aug", *args, stream)
+        else:
+            lib.call("ctn_dynmix_gather_aug_peak", *args, self.peak_mode, stream)
 
 
 def gather_aug(corpus, plan_utt, plan_start, gain, segment_len, rirs=None, plan_rir=None, noise=None, noise_utt=None,
-               noise_start=None, ngain=None, plan_pct=None):
+               noise_start=None, ngain=None, plan_pct=None, peak="always"):
     """The minibatch of a caller-written plan with reverberation and noise: gather()'s arguments, plus rirs (a rir.RirBank) with
     plan_rir [B,C] int32, and noise (a DeviceCorpus) with noise_utt [B] int32, noise_start [B] int64, ngain [B] float32 (the noise
-    gain itself, nothing is drawn or looked up) -> (mixture [B,T], sources [B,C,T], peak [B]).  Either half may be left out."""
+    gain itself, nothing is drawn or looked up) -> (mixture [B,T], sources [B,C,T], peak [B]).  Either half may be left out.
+    peak: "always" or "clip", the peak rule (DynamicMixLoader)."""
     dev = corpus.device
     B, C = plan_utt.shape
     T = int(segment_len)
@@ -554,6 +654,7 @@ def gather_aug(corpus, plan_utt, plan_start, gain, segment_len, rirs=None, plan_
     gain = gain.to(device=dev, dtype=torch.float32).contiguous()
     stream = torch.cuda.current_stream(dev).cuda_stream
     aug = _Augment.of_plan(B, C, T, dev, rirs, plan_rir, noise, noise_utt, noise_start, ngain)
+    aug.peak_mode = peak_mode(peak)
     rows = _Rows(corpus.corpus, corpus.offsets, corpus.lens, corpus.num_utterances, plan_utt, plan_start)
     if plan_pct is not None:
         from . import resample as _rs
@@ -570,13 +671,15 @@ def gather_aug(corpus, plan_utt, plan_start, gain, segment_len, rirs=None, plan_
     return mixture, sources, peak
 
 
-def gather(corpus, plan_utt, plan_start, gain, segment_len, mode=None, plan_pct=None):
+def gather(corpus, plan_utt, plan_start, gain, segment_len, mode=None, plan_pct=None, peak="always"):
     """The minibatch of a caller-written plan: plan_utt [B,C] int32, plan_start [B,C] int64, gain [B,C] float32 on the
     corpus' device -> (mixture [B,T], sources [B,C,T], peak [B]).  plan_pct [B,C] int32: speed percents in [50, 200], the
-    sources replayed at these (plan_start + ceil(T * pct / 100) <= the utterance's length)."""
+    sources replayed at these (plan_start + ceil(T * pct / 100) <= the utterance's length).  peak: "always" (every mixture is
+    rescaled to a peak of 0.9) or "clip" (only one whose peak exceeds 0.9 is)."""
     dev = corpus.device
     B, C = plan_utt.shape
     T = int(segment_len)
+    pm = peak_mode(peak)
     plan_utt = plan_utt.to(device=dev, dtype=torch.int32).contiguous()
     plan_start = plan_start.to(device=dev, dtype=torch.int64).contiguous()
     gain = gain.to(device=dev, dtype=torch.float32).contiguous()
@@ -590,9 +693,8 @@ def gather(corpus, plan_utt, plan_start, gain, segment_len, mode=None, plan_pct=
         banks = _rs.speed_banks([p for p in pcts if _rs.PCT_LO <= p <= _rs.PCT_HI] or [100], dev)
         plan_pct = plan_pct.to(device=dev, dtype=torch.int32).contiguous()
         _SegmentBuffer(B, C, T, dev).mix(corpus, banks, plan_utt, plan_start, plan_pct, gain, mixture, sources, peak, ws,
-                                         GATHER_MODE if mode is None else int(mode), torch.cuda.current_stream(dev).cuda_stream)
+                                         GATHER_MODE if mode is None else int(mode), torch.cuda.current_stream(dev).cuda_stream, pm)
         return mixture, sources, peak
-    lib.call("ctn_dynmix_gather", _ptr(corpus.corpus), _ptr(corpus.offsets), _ptr(corpus.lens), corpus.num_utterances,
-             _ptr(plan_utt), _ptr(plan_start), _ptr(gain), B, C, T, _ptr(mixture), _ptr(sources), _ptr(peak), _ptr(ws),
-             ws.numel(), GATHER_MODE if mode is None else int(mode), torch.cuda.current_stream(dev).cuda_stream)
+    _gather_call(corpus.corpus, corpus.offsets, corpus.lens, corpus.num_utterances, plan_utt, plan_start, gain, B, C, T, mixture,
+                 sources, peak, ws, GATHER_MODE if mode is None else int(mode), pm, torch.cuda.current_stream(dev).cuda_stream)
     return mixture, sources, peak

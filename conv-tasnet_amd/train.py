@@ -51,8 +51,15 @@ class SyntheticLoader:
 def train(data, epochs, model_path, save_folder="exp/models", continue_from="", config=None, lr=1e-3,
           max_grad_norm=5, half_lr=1, early_stop=1, print_freq=10, enable_checkpoint=0, optimizer_type='adam',
           momentum=0.0, l2=0.0, loss='pit', snr_max=30.0, inactive_snr_max=20.0, stoi_weight=None, stoi_extended=False,
-          sample_rate=8000, mrstft_weight=None, mrstft_resolutions=None):
+          sample_rate=8000, mrstft_weight=None, mrstft_resolutions=None, level=None, loudness_db=None, noise_loudness_db=None,
+          peak=None):
     """data = {'tr_loader': ..., 'cv_loader': ...}.  Returns the Solver after training.
+
+    Either loader may be given as a dict instead, the description of a dynamic-mixing loader that is built here on this rank's
+    device: dict(arrays=, speakers=, batch_size=, segment_len=, noise_arrays=None, **DynamicMixLoader keywords), the corpus at
+    sample_rate Hz.  level ('rms', 'active', 'loudness'), loudness_db, noise_loudness_db and peak ('always', 'clip') are passed
+    through to such loaders (the corpora and DynamicMixLoader: the LibriMix recipe is level='loudness', loudness_db=(-33, -25),
+    peak='clip'); with loaders that are built already they are a ValueError.
 
     loss 'pit': the reference's permutation-invariant SI-SNR against [B,C,T] sources.  loss 'mixit': mixture invariant
     training (mixit.cal_mixit_loss, soft threshold snr_max dB or None): both loaders yield the two reference mixtures
@@ -101,7 +108,15 @@ def train(data, epochs, model_path, save_folder="exp/models", continue_from="", 
         if not MIN_SOURCES <= n_out <= MAX_SOURCES:
             raise ValueError("loss 'pit_assign' takes %d .. %d speakers, config['C'] = %r" % (MIN_SOURCES, MAX_SOURCES, n_out))
         criterion = AssignPitCriterion()
+    recipe = dict(level=level, loudness_db=loudness_db, noise_loudness_db=noise_loudness_db, peak=peak)
+    specs = [k for k in ('tr_loader', 'cv_loader') if isinstance(data.get(k), dict)]
+    if not specs and any(v is not None for v in recipe.values()):
+        raise ValueError("level, loudness_db, noise_loudness_db and peak apply to loaders given as a dict (built here); these are built")
     world, rank, device = parallel.init_distributed()
+    if specs:
+        data = dict(data)
+        for k in specs:
+            data[k] = _loader_from_spec(data[k], device, rank, sample_rate, recipe)
     cfg = dict(PAPER if config is None else config)
     torch.manual_seed(0)
     model = ConvTasNet(cfg['N'], cfg['L'], cfg['B'], cfg['H'], cfg['P'], cfg['X'], cfg['R'], cfg['C'],
@@ -117,6 +132,26 @@ def train(data, epochs, model_path, save_folder="exp/models", continue_from="", 
     solver = Solver(data, model, optimizer, arg_solver, criterion=criterion)
     solver.train()
     return solver
+
+
+def _loader_from_spec(spec, device, rank, sample_rate, recipe):
+    """The dynamic-mixing loader a dict describes (train()): the corpus (and the noise corpus of noise_arrays) at the recipe's level."""
+    from .dynmix import DeviceCorpus, DynamicMixLoader
+    spec = dict(spec)
+    try:
+        arrays, speakers = spec.pop("arrays"), spec.pop("speakers")
+        batch_size, segment_len = spec.pop("batch_size"), spec.pop("segment_len")
+    except KeyError as e:
+        raise ValueError("a loader given as a dict needs arrays, speakers, batch_size and segment_len: %s is missing" % e)
+    level = recipe["level"] or "rms"
+    corpus = DeviceCorpus.from_arrays(arrays, speakers, device, level=level, sample_rate=sample_rate)
+    noise_arrays = spec.pop("noise_arrays", None)
+    if noise_arrays is not None:
+        spec["noise"] = DeviceCorpus.from_arrays(noise_arrays, ["noise"] * len(noise_arrays), device, sample_rate=sample_rate,
+                                                 level="loudness" if recipe["noise_loudness_db"] is not None else "rms")
+    spec.setdefault("rank", rank)
+    return DynamicMixLoader(corpus, batch_size, segment_len, loudness_db=recipe["loudness_db"],
+                            noise_loudness_db=recipe["noise_loudness_db"], peak=recipe["peak"] or "always", **spec)
 
 
 def build_parser():
@@ -149,10 +184,21 @@ def build_parser():
                     "integer percent of its speed in [LO, HI], e.g. 95:105 (resampled on the device); validation never perturbs")
     ap.add_argument("--corpus-rate", default="8000", choices=["8000", "auto"], help="rate of the --dynamic-mix files: 8000 (any "
                     "other rate is an error), or auto: files at other rates are resampled to 8 kHz on the device")
-    ap.add_argument("--level", default="rms", choices=["rms", "active"], help="--dynamic-mix / --dynamic-mix-cv: the 0-dB level of "
-                    "a source: rms, the plain RMS of the whole utterance, or active, the ITU-T P.56 active speech level the wsj0-2mix "
-                    "recipe normalises with (tools/matlab-code/create_wav_2speakers.m:89-97, activlev(s, fs, 'n')), measured on the "
-                    "device; noise keeps rms")
+    ap.add_argument("--level", default="rms", choices=["rms", "active", "loudness"], help="--dynamic-mix / --dynamic-mix-cv: the 0-dB "
+                    "level of a source: rms, the plain RMS of the whole utterance, active, the ITU-T P.56 active speech level the wsj0-2mix "
+                    "recipe normalises with (tools/matlab-code/create_wav_2speakers.m:89-97, activlev(s, fs, 'n')), or loudness, the "
+                    "ITU-R BS.1770 integrated loudness the LibriMix recipe normalises with, measured on the device; noise keeps rms "
+                    "unless --noise-loudness is given")
+    ap.add_argument("--loudness", default=None, metavar="LO:HI", help="--level loudness: every source at an absolute loudness drawn "
+                    "uniformly from the tenths of a LU in [LO, HI] LUFS, e.g. --loudness=-33:-25 (in place of the relative +-q levels)")
+    ap.add_argument("--noise-loudness", default=None, metavar="LO:HI", help="with --noise: the noise at an absolute loudness drawn "
+                    "from [LO, HI] LUFS, e.g. --noise-loudness=-38:-30 (in place of --snr); the noise corpus is measured with the "
+                    "loudness meter")
+    ap.add_argument("--peak", default=None, choices=["always", "clip"], help="--dynamic-mix / --dynamic-mix-cv: always (the default) "
+                    "rescales every mixture to a peak of 0.9, clip only a mixture whose peak exceeds 0.9")
+    ap.add_argument("--librimix", action="store_true", help="the LibriMix recipe: short for --level loudness --loudness=-33:-25 "
+                    "--peak clip, plus --noise-loudness=-38:-30 when --noise is given (--loudness, --noise-loudness and "
+                    "--peak given beside it win)")
     ap.add_argument("--checkpoint", action="store_true", help="save checkpoint_models/epochN.pth.tar under --save-folder every epoch")
     ap.add_argument("--continue-from", default="", metavar="CHECKPOINT", help="resume from this checkpoint and run --epochs + 1 "
                     "more epochs (the Solver's arithmetic); a dynamic-mixing run sees the minibatches of the uninterrupted one")
@@ -208,6 +254,31 @@ def parse_snr(text):
     return lo, hi
 
 
+LIBRIMIX = dict(loudness="-33:-25", noise_loudness="-38:-30", peak="clip")      # Cosentino et al. 2020, the LibriMix scripts
+
+
+def recipe_args(a):
+    """(level, loudness_db, noise_loudness_db, peak) of --level / --loudness / --noise-loudness / --peak / --librimix; the ranges
+    as (lo, hi) floats or None.  What the flags cannot mean is a SystemExit."""
+    level, loud, nloud, peak = a.level, a.loudness, a.noise_loudness, a.peak
+    if a.librimix:
+        level = "loudness"
+        loud = LIBRIMIX["loudness"] if loud is None else loud
+        peak = LIBRIMIX["peak"] if peak is None else peak
+        if a.noise and nloud is None:
+            nloud = LIBRIMIX["noise_loudness"]
+    if loud is not None and level != "loudness":
+        raise SystemExit("--loudness needs --level loudness")
+    if nloud is not None and not a.noise:
+        raise SystemExit("--noise-loudness needs --noise")
+    try:
+        loud = None if loud is None else parse_snr(loud)
+        nloud = None if nloud is None else parse_snr(nloud)
+    except ValueError:
+        raise SystemExit("--loudness and --noise-loudness must be LO:HI in LUFS")
+    return level, loud, nloud, "always" if peak is None else peak
+
+
 def parse_rooms(text):
     """'rooms:G[:P]' -> (G, P), P = 4 by default (train.py --rirs)."""
     parts = str(text).split(":")
@@ -250,7 +321,8 @@ def _augmentations(a, device, speakers=2):
         else:
             rirs = _rir.RirBank.from_manifest(a.rirs, 8000, device, early_ms=early)
     if a.noise:
-        noise = DeviceCorpus.from_manifest(a.noise, 8000, device, resample=a.corpus_rate == "auto")
+        noise = DeviceCorpus.from_manifest(a.noise, 8000, device, resample=a.corpus_rate == "auto",
+                                           level="loudness" if recipe_args(a)[2] is not None else "rms")
     return rirs, noise, parse_snr(a.snr), rooms
 
 
@@ -268,6 +340,9 @@ def main(argv=None):
         raise SystemExit("--noise and --rirs apply to --dynamic-mix only")
     if a.rooms_refresh and not (a.rirs or "").startswith("rooms:"):
         raise SystemExit("--rooms-refresh applies to --rirs rooms:G[:P] only")
+    if (a.loudness or a.noise_loudness or a.peak or a.librimix) and not (a.dynamic_mix or a.dynamic_mix_cv):
+        raise SystemExit("--loudness, --noise-loudness, --peak and --librimix apply to --dynamic-mix / --dynamic-mix-cv only")
+    level, loudness_db, noise_loudness_db, peak = recipe_args(a)
     mixit = a.loss == "mixit"
     if mixit:
         if not a.dynamic_mix:
@@ -326,13 +401,15 @@ def main(argv=None):
             if a.speed_perturb:
                 from .resample import parse_speed_range
                 speeds = parse_speed_range(a.speed_perturb)
-            tr = DynamicMixLoader(DeviceCorpus.from_manifest(a.dynamic_mix, 8000, device, resample=auto, level=a.level), a.batch_size,
+            tr = DynamicMixLoader(DeviceCorpus.from_manifest(a.dynamic_mix, 8000, device, resample=auto, level=level), a.batch_size,
                                   a.segment_len, num_speakers=speakers, steps_per_epoch=a.steps_per_epoch, seed=a.seed, rank=rank,
-                                  speeds=speeds, rirs=rirs, noise=noise, snr_db=snr_db, min_speakers=a.min_speakers, **rooms[0])
+                                  speeds=speeds, rirs=rirs, noise=noise, snr_db=snr_db, min_speakers=a.min_speakers,
+                                  loudness_db=loudness_db, noise_loudness_db=noise_loudness_db, peak=peak, **rooms[0])
         if a.dynamic_mix_cv:
-            cv = DynamicMixLoader(DeviceCorpus.from_manifest(a.dynamic_mix_cv, 8000, device, resample=auto, level=a.level), a.batch_size,
+            cv = DynamicMixLoader(DeviceCorpus.from_manifest(a.dynamic_mix_cv, 8000, device, resample=auto, level=level), a.batch_size,
                                   a.segment_len, num_speakers=speakers, steps_per_epoch=a.cv_steps, seed=a.seed + 1, rank=rank,
-                                  reshuffle=False, noise=noise, snr_db=snr_db,
+                                  reshuffle=False, noise=noise, snr_db=snr_db, loudness_db=loudness_db,
+                                  noise_loudness_db=noise_loudness_db if noise is not None else None, peak=peak,
                                   min_speakers=a.min_speakers if a.dynamic_mix else None, **dict(dict(rirs=rirs), **rooms[1]))
         if mixit:
             from .mixit import MixtureOfMixtures

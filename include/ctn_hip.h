@@ -1273,6 +1273,76 @@ int ctn_ism_simulate(const double* tables_host, const double* tables, int G, int
 int ctn_dynmix_plan_rooms(long long seed, int epoch, int rank, const unsigned* step, int B, int C, int G, int P, int* plan_rir,
                           void* stream);
 
+/* ---- integrated loudness, ITU-R BS.1770-4, mono (csrc/ctn_loudness.hip) -------------------------------------------------------------
+ * what the LibriMix recipe normalises every source and noise file with, for U ragged utterances in device memory: samples
+ * [num_samples] fp32, offsets [U], lens [U] int64 as for ctn_dynmix_levels.  Of utterance u the device produces  ns, n_blocks, n_abs,
+ * n_rel [U] int64 and sum_all, sum_abs, sum_rel [U] fp64;  the loudness itself is one division and one logarithm per utterance on the
+ * host (loudness.loudness_from_stats).  For one utterance x[0 .. len), all in fp64, nothing appended, ns = len:
+ *   weighting  x -> y through two biquads (the high shelf, then the high-pass; designed on the host from the analog prototype by the
+ *              bilinear transform: loudness.design), direct form II transposed from zero state at sample 0, every product and every
+ *              sum ONE rounding, no contraction, in this order:
+ *                  y = b0 v + z1;  z1 = (b1 v + z2) - a1 y;  z2 = b2 v - a2 y                              (v: the section's input)
+ *   sub-blocks h = hop = fs / 10 samples (800 <= h <= 4800), sub-block i = samples [i h, (i + 1) h), i < nsub = floor(len / h).  A chunk
+ *              (below) meets at most three sub-blocks; a PIECE is what a chunk and a sub-block share, its sum p = p + y y per sample,
+ *              in order, from 0.  S_i = ((0 + p) + p') + ..., the pieces of sub-block i, chunks ascending.
+ *   blocks     n_blocks = max(nsub - 3, 0);  z_j = (((S_j + S_(j+1)) + S_(j+2)) + S_(j+3)) / (4 h): 400 ms every 100 ms in exact
+ *              integers, a trailing partial block is dropped.
+ *   gates      absolute: z_j > Ga (table[26] = 10^((-70 + 0.691) / 10), from the host);  relative: z_j > Ga and
+ *              z_j > (sum_abs / n_abs) / 10.0 (none if n_abs = 0).  Both strict, in the power domain.
+ *   sums       sum_all over all blocks, sum_abs over the absolute-gated ones, sum_rel over those that pass both; n_abs, n_rel count
+ *              them.  Each sum: lane l = j mod 64 adds its blocks from 0, j ascending, then ((lane 0 + lane 1) + ...) + lane 63.
+ * The device form: an utterance is cut into chunks of CH = ctn_loudness_chunk() samples by its own sample index.  Every chunk runs
+ * from zero state and leaves its end state z_c (4 values, section order); one carry per utterance forms the true start states
+ *     s_0 = 0;   s_(c+1)[r] = (((T[r][0] s_c[0] + T[r][1] s_c[1]) + T[r][2] s_c[2]) + T[r][3] s_c[3]) + z_c[r]
+ * with T = A^CH (column k: the state CH zero-input samples after the unit state e_k) from the host; then every chunk is rerun from
+ * s_c.  By linearity that is the sequential filter in exact arithmetic; in fp64 it is THIS computation (tests/loudness_oracle.py
+ * restates it).  No pow, tan, exp or log on the device, no atomics on device memory, no read-back.
+ * table [27] fp64: [0,5) shelf b0 b1 b2 a1 a2; [5,10) high-pass b0 b1 b2 a1 a2; [10,26) T row-major 4 x 4; [26] Ga.
+ * chunk_ptr [U + 1] int64: chunk_ptr[0] = 0, chunk_ptr[u + 1] - chunk_ptr[u] = ceil(lens[u] / CH), total_chunks = chunk_ptr[U] (0 is
+ * allowed: empty utterances only).
+ * Determinism: the seven statistics of an utterance are a bitwise function of its own samples, the table, hop and CH: independent of
+ * the neighbours, of U, of the launch geometry and of how a caller groups utterances into calls to bound the workspace.
+ * An entry outside the buffer (offset < 0, len < 0, offset + len > num_samples) or a chunk range that is not the one its length asks
+ * for is never read: ns[u] = -1, the other six are 0, and nothing else changes.
+ * workspace: ctn_loudness_workspace(total_chunks, U) bytes (8-byte aligned; 7 fp64 words per chunk: a function of total_chunks alone,
+ * U is only checked to be positive).  total_chunks <= 2^31 - 65 per call.  Four launches on `stream` (one if total_chunks = 0); bad
+ * sizes are CTN_ERR_ARG before any launch. */
+int ctn_loudness_chunk(void);
+size_t ctn_loudness_workspace(long long total_chunks, long long U);
+int ctn_loudness(const float* samples, long long num_samples, const long long* offsets, const long long* lens,
+                 const long long* chunk_ptr, long long U, long long total_chunks, const double* table, int hop, long long* ns,
+                 long long* n_blocks, long long* n_abs, long long* n_rel, double* sum_all, double* sum_abs, double* sum_rel,
+                 void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- LibriMix-recipe mixing: absolute loudness per source, a noise loudness, rescale only what clips ------------------------------
+ * (csrc/ctn_dynmix_loudness.hip, the gathers of csrc/ctn_dynmix.hip and csrc/ctn_dynmix_aug.hip).  The corpus' inv_rms is
+ * float32(1 / sqrt(gated K-weighted power)) from ctn_loudness: an utterance times inv_rms reads 0.691 dB above 0 LUFS.
+ * ctn_dynmix_plan_loudness: launched BEHIND ctn_dynmix_plan / ctn_dynmix_plan_speed on the same stream (and before
+ *   ctn_dynmix_mask_active): those have advanced the step word, so the minibatch's step is *step - 1, which it reads and leaves alone.
+ *       i = below(r.w[0], nl),  r = philox4x32_10(1280 + c, b, *step - 1, epoch, k0, k1), key and below() as in ctn_dynmix_plan
+ *       plan_l10[b,c] = lo10 + i (tenths of a LU);   gain[b,c] = wl[i] * inv_rms[plan_utt[b,c]]  (one fp32 multiply; 0 for a
+ *       flagged entry, plan_utt outside [0, U))
+ *   wl [nl] fp32, 1 <= nl <= 1024, from the host: wl[i] = float32(10^(((lo10 + i) / 10 + 0.691) / 20)).  It OVERWRITES the gains of
+ *   the plan; plan_q is still drawn and plays no part.  The c0 words c, 256 + c, 512 + c, 768 and 1024 belong to the other draws,
+ *   which keep their bits; 1280 + c is used by no other draw.
+ * The noise loudness needs no entry point of its own: ctn_dynmix_plan_aug with wn = the loudness table of the noise range
+ *   (wn[k] = float32(10^(((lo10 + k) / 10 + 0.691) / 20))), so the word that chooses the SNR chooses the noise loudness, snr10 holds
+ *   its tenths of a LU and ngain = wn[k] * noise_inv_rms[v] with the noise corpus' loudness inv_rms.
+ * ctn_dynmix_gather_peak / ctn_dynmix_gather_aug_peak: ctn_dynmix_gather / ctn_dynmix_gather_aug with the peak rule as an argument:
+ *       peak_mode 0   scale = a > 0 ? 0.9f / a : 1      every mixture to a peak of 0.9: what the plain entry points do (they forward)
+ *       peak_mode 1   scale = a > 0.9f ? 0.9f / a : 1   only a mixture that would clip (the LibriMix rule)
+ *   a = peak[b], the unscaled maximum, is stored as before; every other word of their contracts holds. */
+int ctn_dynmix_plan_loudness(const int* plan_utt, const float* inv_rms, long long U, const float* wl, int nl, int lo10, long long seed,
+                             int epoch, int rank, const unsigned* step, int B, int C, int* plan_l10, float* gain, void* stream);
+int ctn_dynmix_gather_peak(const float* corpus, const long long* offsets, const long long* lens, long long U, const int* plan_utt,
+                           const long long* plan_start, const float* gain, int B, int C, int T, float* mixture, float* sources,
+                           float* peak, void* workspace, size_t workspace_bytes, int mode, int peak_mode, void* stream);
+int ctn_dynmix_gather_aug_peak(const float* corpus, const long long* offsets, const long long* lens, long long U, const int* plan_utt,
+                               const long long* plan_start, const float* gain, int B, int C, int T, const float* tgt_corpus,
+                               const float* noise, const long long* noise_offsets, const long long* noise_lens, long long Un,
+                               const int* noise_utt, const long long* noise_start, const float* ngain, float* mixture, float* sources,
+                               float* peak, void* workspace, size_t workspace_bytes, int peak_mode, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
